@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the SSN fixed-point hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2|c2nb8|c1]
+    python bench.py --gpus N --steps K --warmup W [--workload c2|c2nb8|c1] [--full] [--dump-outputs DIR]
 
 Metric (BASELINE.json): SSN-steps/sec = neurons x batch x Euler-steps / s.
 Workload at N=1 (BASELINE config 2, the one `metric` is quoted on): 2N=200 neurons,
@@ -13,8 +13,13 @@ solve.  N>1: one process per GPU (torch.distributed / RCCL), every rank solves i
 batch of 4096 draws (the path partitions over draws, no data-path collective) ->
 "scaling": "weak"; value = all ranks' units / max-over-ranks time.
 
-Prints ONE JSON line on rank 0, with `roofline` (dominant kernel, HIP-event timed) and
-`cpu_baseline` (the reference's own C file, oracle/_ref, on the host cores).
+Prints ONE JSON line on rank 0, with `roofline` (dominant kernel, HIP-event timed).  A plain
+run sets up, warms up, times the K steps and prints the line.  `--full` adds everything that
+takes runs of its own: `cpu_baseline` (the reference's own C file, oracle/_ref, on the host
+cores), the short C3 run as `secondary` and the other workloads as `extras` (C2 workload),
+the comparison loops, kernel-alone and critic timings (C3), the dense entry point (C5).
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy
+(float32 / float64; the inputs are seeded, so two builds can be compared output for output).
 """
 import argparse
 import ctypes
@@ -158,6 +163,23 @@ def _traffic(key):
         return json.load(open(os.path.join(ROOT, 'profiles', 'hbm_traffic.json'))).get(key)
     except Exception:
         return None
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array (host or device) as <path>/<name>.npy, float64 kept as such and everything else as
+    float32 (codes and step counts are small integers: exact in float32); at most 64 MB in all."""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
+        host[name] = np.array(a, dtype=np.float64 if a.dtype == np.float64 else np.float32, order='C')
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT_BYTES, 'bench.py --dump-outputs: %d bytes, over the %d limit' % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def make_c3_gan(world=1, rank=0, paper=False, disc_precision='bf16', critic_iters_init=5, critic_iters=5, models=None,
@@ -309,6 +331,12 @@ def run_c3(args, rank, world, local_rank, paper=False, z_mode='refstream', compa
     gan, (N, models, NB, T, skip), bandwidths, elapsed, info, phases = timed_loop(os.environ.get('BENCH_GEN_KERNEL', 'auto'))    # (A/B runs only)
     forward_ms_in_loop = timed_loop.forward_ms_in_loop
     host_draw_ms = timed_loop.host_draw_ms
+    if args.dump_outputs and rank == 0:
+        # what the last GAN iteration hands back: the generator's parameters after its update, the critic's flat parameters
+        # after the last critic update, the generator loss
+        disc = gan.discriminator if hasattr(gan, 'discriminator') else gan.disc
+        dump_outputs(args.dump_outputs, dict(dict(gan.gen.get_all_params()), critic_params=getattr(disc, 'critic', disc).get_flat(),
+                                             gen_loss=np.float64(info.gen_loss)))
     # the same loop -- same seeds, fresh GAN, same warm-up, steps and max-over-ranks -- with the generator's W.r on the fp32
     # matrix instructions (W and state carried with all 24 bits), so that the line holds both numbers (`fp32_mfma` below)
     fp32_ms = None
@@ -323,23 +351,25 @@ def run_c3(args, rank, world, local_rank, paper=False, z_mode='refstream', compa
     philox_ms = None
     if comparisons and z_mode == 'refstream' and args.steps >= 2:
         philox_ms = timed_loop(os.environ.get('BENCH_GEN_KERNEL', 'auto'), z_mode='philox')[3] / args.steps * 1e3
-    # dominant kernel: gen_forward_kernel, timed alone with HIP events on the launch stream
-    bw = np.tile(np.asarray(bandwidths, dtype='float32')[None], (models, 1))
-    kw = dict(stimulator_bandwidths=bw, stimulator_contrasts=np.full_like(bw, 20.0), prober_norm_probes=np.zeros(models),
-              prober_model_ids=np.arange(models), prober_cell_types=np.zeros(models))
     from tc_gan_amd import genops
-    noise = gan.gen.gen_noise(gan.rng, bw)
-    ext, z, W = gan.gen._device_inputs(bw, kw['stimulator_contrasts'], noise['model_zs'], noise.get('model_zs_in'))
     gp = gan.gen.gen_params(200.0)
-    genops.gen_forward(W, ext, gp)
     out_extra_kernel = gan.gen.gen_kernel
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(3):
+    kernel_ms_alone = None
+    if args.full or not forward_ms_in_loop:
+        # dominant kernel: gen_forward_kernel, timed alone with HIP events on the launch stream
+        bw = np.tile(np.asarray(bandwidths, dtype='float32')[None], (models, 1))
+        kw = dict(stimulator_bandwidths=bw, stimulator_contrasts=np.full_like(bw, 20.0), prober_norm_probes=np.zeros(models),
+                  prober_model_ids=np.arange(models), prober_cell_types=np.zeros(models))
+        noise = gan.gen.gen_noise(gan.rng, bw)
+        ext, z, W = gan.gen._device_inputs(bw, kw['stimulator_contrasts'], noise['model_zs'], noise.get('model_zs_in'))
         genops.gen_forward(W, ext, gp)
-    e1.record()
-    torch.cuda.synchronize()
-    kernel_ms_alone = e0.elapsed_time(e1) / 3
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(3):
+            genops.gen_forward(W, ext, gp)
+        e1.record()
+        torch.cuda.synchronize()
+        kernel_ms_alone = e0.elapsed_time(e1) / 3
     # the roofline is priced on the kernel as it runs INSIDE the loop (mean over the plain forwards of the timed iterations:
     # the card is at its power limit there and the clock lower than for the kernel alone)
     kernel_ms = forward_ms_in_loop if forward_ms_in_loop else kernel_ms_alone
@@ -372,7 +402,8 @@ def run_c3(args, rank, world, local_rank, paper=False, z_mode='refstream', compa
     }
     # (kernel_ms: mean duration of the plain forwards inside the timed loop; kernel_ms_alone: the same launch repeated by
     # itself after the loop, on an idle card)
-    out['roofline']['kernel_ms_alone'] = kernel_ms_alone
+    if kernel_ms_alone is not None:
+        out['roofline']['kernel_ms_alone'] = kernel_ms_alone
     # host time per iteration inside the loop's RNG draws (minibatch choice, eps, and -- z_mode 'numpy' -- z itself; in 'refstream'
     # mode the part of ssn_mt19937_random_sample_f32 the host waits for: the state after the draw)
     out['z_mode'] = z_mode
@@ -391,7 +422,7 @@ def run_c3(args, rank, world, local_rank, paper=False, z_mode='refstream', compa
                                    "NOT the reference's noise stream; the difference to ms_per_step is what continuing the RandomState costs"}
     if phases is not None:
         out['phases'] = phases
-    if not paper and rank == 0:
+    if args.full and not paper and rank == 0:
         out['critic'] = _critic_update_roofline(gan, models)
     out['world_size'] = world
     return out
@@ -490,22 +521,26 @@ def run_c5(args, rank, world, local_rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert bool(torch.isfinite(out).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'ff_output': out})
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
-    # the dense entry point on the same inputs (FF_con / FF_str as arrays): same outputs, three per-point streams
-    con = torch.zeros((nsam, nhid, G), device='cuda')
-    rows = torch.arange(nsam * nhid, device='cuda').reshape(nsam, nhid, 1).expand_as(idx)
-    ok = idx >= 0
-    con.view(nsam * nhid, G)[rows[ok], idx[ok].long()] = 1.0
-    dense = ff_model.ff_forward(ff_model.START_PARAMS, wid, con, strn, ths, stim, box)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(3):
+    dense_ms = None
+    if args.full:
+        # the dense entry point on the same inputs (FF_con / FF_str as arrays): same outputs, three per-point streams
+        con = torch.zeros((nsam, nhid, G), device='cuda')
+        rows = torch.arange(nsam * nhid, device='cuda').reshape(nsam, nhid, 1).expand_as(idx)
+        ok = idx >= 0
+        con.view(nsam * nhid, G)[rows[ok], idx[ok].long()] = 1.0
         dense = ff_model.ff_forward(ff_model.START_PARAMS, wid, con, strn, ths, stim, box)
-    e1.record()
-    torch.cuda.synchronize()
-    dense_ms = e0.elapsed_time(e1) / 3
-    assert float((dense - out).abs().max()) <= 1e-4 * max(float(dense.abs().max()), 1.0)
-    del con, dense
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(3):
+            dense = ff_model.ff_forward(ff_model.START_PARAMS, wid, con, strn, ths, stim, box)
+        e1.record()
+        torch.cuda.synchronize()
+        dense_ms = e0.elapsed_time(e1) / 3
+        assert float((dense - out).abs().max()) <= 1e-4 * max(float(dense.abs().max()), 1.0)
+        del con, dense
     # The pass over the widths is bound by the vector unit, not by HBM: per (sample, point) 27 FMAs (the 3 x 3 x 3 sums of
     # exp products) + 18 multiplies + 9 exponentials + ~6 = 87 flop against 4 bytes
     flops_alg = float(nsam) * G * 87.0
@@ -521,7 +556,9 @@ def run_c5(args, rank, world, local_rank):
                         'traffic': _traffic('c5'), 'kernel': 'ff_forward_sparse_lattice_kernel', 'kernel_ms': kernel_ms,
                         'flops_per_unit': 87, 'algorithmic_hbm_bytes': bytes_alg,
                         'hbm_GBps': bytes_alg / (kernel_ms * 1e-3) * 1e-9, 'hbm_frac': bytes_alg / (kernel_ms * 1e-3) * 1e-9 / 8000.0,
-                        'dense_entry_ms': dense_ms, 'dense_entry_hbm_bytes': float(nsam) * nhid * G * 12}}
+                        'dense_entry_hbm_bytes': float(nsam) * nhid * G * 12}}
+    if dense_ms is not None:
+        res['roofline']['dense_entry_ms'] = dense_ms
     res['world_size'] = world
     return res
 
@@ -546,7 +583,6 @@ def run_c1_dropin(args):
     Ws = list(weight_gen.generate_weight_batch(N, J, D, S, rs.rand(sample, M, M), dtype='float64').cpu().numpy())
     exts = stimuli.input([1.0], np.linspace(-.5, .5, N), 0.25 / 8, [20.])
     t_pool = time_threaded_solves(fn, Ws, exts, N, T, threads)
-    t_one = time_threaded_solves(fn, Ws[:64], exts, N, T, 1)
     units = float(M) * NB * T
     value = units * sample / t_pool
     out = {'metric': 'SSN-steps/sec', 'value': value, 'unit': 'neuron*batch*Euler-steps/s', 'n_gpus': 1,
@@ -555,10 +591,12 @@ def run_c1_dropin(args):
            'config': {'workload': desc + ', via the drop-in symbols: %d host threads, one solve_dynamics_asym_tanh_euler '
                                          'call per (draw, stimulus), host buffers (PCIe, launch and sync inside the timed '
                                          'region)' % threads,
-                      'calls': sample * NB, 'us_per_call_pool': t_pool / (sample * NB) * 1e6,
-                      'us_per_call_single_thread': t_one / (min(sample, 64) * NB) * 1e6,
-                      'single_thread_value': units * min(sample, 64) / t_one},
+                      'calls': sample * NB, 'us_per_call_pool': t_pool / (sample * NB) * 1e6},
            'roofline': None}
+    if args.full:
+        t_one = time_threaded_solves(fn, Ws[:64], exts, N, T, 1)
+        out['config'].update(us_per_call_single_thread=t_one / (min(sample, 64) * NB) * 1e6,
+                             single_thread_value=units * min(sample, 64) / t_one)
     if not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(N, NB, T, sample)
         out['cpu_baseline']['gpu_over_cpu'] = value / out['cpu_baseline']['value']
@@ -593,6 +631,12 @@ def main():
     ap.add_argument('--variant', type=int, default=-1, help='-1 auto, 0 streaming, 1 register-stationary DPP, 2 tile (library picks the shape), '
                     '3 tile/split residency, 4 tile/all-register, 5 fp32 MFMA (NB >= 4), 6 fp16-split MFMA (NB >= 4), 7 the same in the alternating form, '
                     '8 fp16-split MFMA with two draws per workgroup')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: CPU baseline, `secondary` and `extras` (C2), comparison '
+                         'loops and kernel-alone / critic timings (C3), the dense entry point (C5), the single-thread pool (C1 '
+                         'drop-in).  A plain run times the steps and nothing else; the options below apply with --full')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the timed path's outputs of its last step as DIR/<name>.npy (rank 0)")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-sample', type=int, default=0, help='weight draws in the CPU baseline sample (0 = auto)')
     ap.add_argument('--secondary-steps', type=int, default=10,
@@ -609,6 +653,10 @@ def main():
                     help="c1 only: 'dropin' times the reference's call pattern (one solve_dynamics_* call per "
                          "(draw, stimulus) from a pool of one thread per usable core) through the zero-change drop-in symbols")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline, args.secondary_steps, args.extras = True, 0, False
+    if args.dump_outputs and args.workload == 'c1' and args.via == 'dropin':
+        ap.error('--dump-outputs: the drop-in path keeps no outputs (one host buffer per call)')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))            # before anything touches the GPU
@@ -650,9 +698,9 @@ def main():
         assert dist.get_world_size() == args.gpus, (dist.get_world_size(), args.gpus)
 
     if args.workload == 'c3paper':
-        out = run_c3(args, rank, world, local_rank, paper=True, z_mode=args.z_mode)
+        out = run_c3(args, rank, world, local_rank, paper=True, z_mode=args.z_mode, comparisons=args.full)
     elif args.workload == 'c3':
-        out = run_c3(args, rank, world, local_rank, z_mode=args.z_mode)
+        out = run_c3(args, rank, world, local_rank, z_mode=args.z_mode, comparisons=args.full)
     elif args.workload == 'c5':
         out = run_c5(args, rank, world, local_rank)
     elif args.workload == 'c1' and args.via == 'dropin':
@@ -661,7 +709,7 @@ def main():
         out = run_solver(args, rank, world, local_rank)
         if args.workload == 'c2' and args.secondary_steps > 0:
             # the second half of BASELINE.json.metric ("GAN iters/sec"): a short C3 run in the same job
-            sub = argparse.Namespace(**vars(args))
+            sub = argparse.Namespace(**dict(vars(args), dump_outputs=None))
             sub.steps, sub.warmup = args.secondary_steps, 3
             sec = run_c3(sub, rank, world, local_rank)
             out['secondary'] = {k: sec[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step',
@@ -681,7 +729,7 @@ def main():
                                                       ('c3paper', 'c3paper', 20, 5, {}),
                                                       ('c3_refstream', 'c3', max(args.secondary_steps, 3), 3, {})):
                 sub = argparse.Namespace(**dict(vars(args), workload=workload, steps=steps, warmup=warmup, variant=-1,
-                                                no_cpu_baseline=(name != 'c1_dropin'), **kw))
+                                                no_cpu_baseline=(name != 'c1_dropin'), dump_outputs=None, **kw))
                 t_extra = time.perf_counter()
                 if name == 'c3_refstream':
                     # the C3 loop WITHOUT --z-device-seed -- the reference's noise stream (RandomState seed 0), z continued on the
@@ -738,7 +786,8 @@ def run_single_rank_group(args, local_rank):
     os.environ['TCGAN_DIST_SINGLE_RANK'] = '1'
     dist.init_process_group('nccl', rank=0, world_size=1)
     try:
-        sub = argparse.Namespace(**dict(vars(args), workload='c3paper', steps=20, warmup=5, variant=-1, no_cpu_baseline=True))
+        sub = argparse.Namespace(**dict(vars(args), workload='c3paper', steps=20, warmup=5, variant=-1, no_cpu_baseline=True,
+                                        dump_outputs=None))
         res = run_c3(sub, 0, 1, local_rank, paper=True)
         return {'ms_per_step': res['ms_per_step'], 'value': res['value'], 'unit': res['unit'], 'steps': 20, 'warmup': 5,
                 'phases': res.get('phases'), 'dist_backend': dist.get_backend(), 'world_size': dist.get_world_size(),
@@ -818,6 +867,9 @@ def run_solver(args, rank, world, local_rank):
     # sanity: the work really ran (all pairs took exactly T steps with code 1, states finite)
     assert int((steps_out != T).sum()) == 0 and int((codes != 1).sum()) == 0
     assert bool(torch.isfinite(r).all())
+    if args.dump_outputs and rank == 0:
+        # what ssn_solve_batch_f32 hands its caller: end states (B, NB, 2N), exit codes and step counts (B, NB)
+        dump_outputs(args.dump_outputs, {'r': r, 'codes': codes, 'steps': steps_out})
 
     units_per_step = float(M) * B * NB * T                      # neuron x batch x Euler steps (per rank)
     value = units_per_step * args.steps * world / elapsed

@@ -221,12 +221,27 @@ def gen_index_helpers():
     np.savez_compressed(os.path.join(HERE, 'index_helpers.npz'), **out)
 
 
+def gen_reference_solves():
+    """The seeded solves of tests/test_oracle.py::test_oracle_matches_reference_build_live, on the reference build."""
+    out = {}
+    for seed, io_type in enumerate(['asym_power', 'asym_linear', 'asym_tanh'] * 2):
+        N = 12 + seed
+        z = np.random.RandomState(seed).rand(2 * N, 2 * N)
+        W = on.generate_weight(N, JDS['J'], JDS['D'], JDS['S'], z)
+        ext = on.stimulus_input([0.5], np.linspace(-.5, .5, N), P['smoothness'], [20.])[0]
+        b = on.fixed_point(W, ext, P['k'], P['n'], io_type=io_type, lib=ref)
+        out['error_%d' % seed] = np.int32(b.error)
+        out['x_%d' % seed] = b.x
+    np.savez_compressed(os.path.join(HERE, 'reference_solves.npz'), **out)
+
+
 if __name__ == '__main__':
     gen_io_tables()
     gen_weights_stimuli()
     gen_solver_cases()
     gen_matlab()
     gen_index_helpers()
+    gen_reference_solves()
     for f in sorted(os.listdir(HERE)):
         if f.endswith('.npz'):
             print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -1,10 +1,12 @@
 """The bench.py contract the driver depends on: one JSON line with the agreed keys, for the default workload (C2) and
-for the GAN loop (C3, shortened through the paper shape to keep the test fast)."""
+for the GAN loop (C3, shortened through the paper shape to keep the test fast); a plain run times its steps and nothing
+else, `--full` adds the runs of their own, `--dump-outputs` writes what the timed path computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +25,7 @@ def _bench(*args):
 
 
 def test_default_workload_line():
-    d = _bench('--steps', '2', '--warmup', '1', '--cpu-sample', '32')
+    d = _bench('--full', '--steps', '2', '--warmup', '1', '--cpu-sample', '32')
     assert KEYS | {'cpu_baseline'} <= set(d)
     assert d['metric'] == 'SSN-steps/sec' and d['n_gpus'] == 1 and d['steps'] == 2 and d['warmup'] == 1
     assert d['higher_is_better'] is True and d['scaling'] == 'weak' and d['data'] == 'synthetic' and d['dtype'] == 'f32'
@@ -64,8 +66,27 @@ def test_default_workload_line():
 
 
 def test_no_extras_flag():
-    d = _bench('--steps', '1', '--warmup', '0', '--no-extras', '--secondary-steps', '0', '--no-cpu-baseline')
+    d = _bench('--full', '--steps', '1', '--warmup', '0', '--no-extras', '--secondary-steps', '0', '--no-cpu-baseline')
     assert 'extras' not in d and 'secondary' not in d and 'cpu_baseline' not in d
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line holds the headline figure and nothing that takes a run of its own; --dump-outputs writes the
+    last timed step's end states, codes and step counts, and two runs with the same arguments write the same arrays."""
+    dumps = []
+    for k in range(2):
+        d = _bench('--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / str(k)))
+        assert KEYS <= set(d) and d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0
+        assert d['metric'] == 'SSN-steps/sec' and d['unit'] == 'neuron*batch*Euler-steps/s' and d['dtype'] == 'f32'
+        assert d['higher_is_better'] is True
+        assert abs(d['value'] - 200 * 4096 * 2000 / (d['ms_per_step'] * 1e-3)) / d['value'] < 1e-6
+        assert 'extras' not in d and 'secondary' not in d and 'cpu_baseline' not in d
+        dumps.append({n: np.load(str(tmp_path / str(k) / (n + '.npy'))) for n in ('r', 'codes', 'steps')})
+    a, b = dumps
+    assert a['r'].shape == (4096, 1, 200) and a['r'].dtype == np.float32 and np.isfinite(a['r']).all()
+    assert (a['codes'] == 1).all() and (a['steps'] == 2000).all() and a['codes'].shape == (4096, 1)
+    for n in a:
+        np.testing.assert_array_equal(a[n], b[n])
 
 
 def test_gan_loop_line():
@@ -82,7 +103,7 @@ def test_gpus_2_starts_its_own_ranks():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                          '--secondary-steps', '1'], check=True, env=env, capture_output=True, text=True,
+                          '--full', '--secondary-steps', '1'], check=True, env=env, capture_output=True, text=True,
                          timeout=900).stdout.strip().splitlines()
     lines = [l for l in out if l.startswith('{')]
     assert len(lines) == 1, out
@@ -128,7 +149,7 @@ def test_gpus_mismatch_is_refused():
 def test_c1_dropin_line():
     """BASELINE config 1 through the zero-change drop-in symbols, timed like the reference calls them (thread pool, one
     ctypes call per solve, host buffers) with the reference's own C beside it."""
-    d = _bench('--workload', 'c1', '--via', 'dropin', '--steps', '1', '--cpu-sample', '64')
+    d = _bench('--full', '--workload', 'c1', '--via', 'dropin', '--steps', '1', '--cpu-sample', '64')
     assert d['metric'] == 'SSN-steps/sec' and d['dtype'] == 'f64' and d['roofline'] is None
     assert 'drop-in' in d['config']['workload'] and d['config']['calls'] == 64
     assert d['value'] > 0 and d['config']['us_per_call_single_thread'] > 0
