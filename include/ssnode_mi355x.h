@@ -503,6 +503,54 @@ int ssn_moment_sums_f32(const float *x, int B, int D, double *sums, void *stream
 int ssn_moment_loss_grad_f32(const float *x, const double *sums, double global_batch, const double *data_moments,
                              const double *weights, int B, int D, float *gx, double *out, void *stream);
 
+/* ---- 6b. Ensembles of moment-matching runs (networks/moment_matching_ensemble.py) -------------------------------------
+ * K independent runs share the generator launches of a step: member k owns the contiguous draws [k B, (k + 1) B) of every
+ * batch (x[K B][D], W[K B][2N][2N], ...).  Per-member values come in small device arrays indexed by the member.  Each call is
+ * ONE launch whatever K is (ssn_ens_moments_f32: two), and every sum of a member runs over its own rows: a non-finite value in
+ * one member reaches no other member.  The record: one fp64 row of ssn_ens_record_doubles(D, P) doubles per member, row
+ * stride rstride >= that --
+ *   [0] L0, [1 .. D] m, [1 + D .. 2D] s, [1 + 2D] dynamics_penalty, [2 + 2D] rate_penalty (both rounded to fp32), [3 + 2D] loss,
+ *   [4 + 2D .. 4 + 2D + P) the new parameters, then the P gradients (P = nv + 12) --
+ * the one buffer the host reads back per step.
+ * ssn_ens_moments_f32: ssn_moment_sums_f32 + ssn_moment_loss_grad_f32 per member with the member's batch B (the same loops:
+ *   the same bits as the single run); sums: device [K][2][D] scratch; data_moments, weights: device [K][2][D]; m and s go to
+ *   the record, L0 is formed by ssn_ens_gen_grads_f32.
+ * ssn_ens_jds_grad_f32: ssn_jds_grad_f32 per member; p16: device [K][16] fp32 = J[4], D[4], 1 / (2 S^2)[4], 1 / S^3[4] (each S
+ *   term rounded as launch_jds_grad rounds it: 1.f / ((2.f * s) * s), 1.f / ((s * s) * s)); out: device [K B][4][3].
+ * ssn_ens_gen_grads_f32: grads[K][nv + 12] = ssn_gen_grads_f32's dL/dV, dL/dJ, dL/dD, dL/dS per member; the penalty means of the
+ *   forward's rows dyn_row / rate_row over the member's draws (scale_*: 1 / element count of ONE member); L0 and
+ *   loss = L0 + costs[k][0] dyn + costs[k][1] rate into the record.  One workgroup per member, fp64 sums in a fixed order.
+ * ssn_ens_apply_f32: ssn_optimizer_step's update of all K parameter vectors p[K][P] (states s1, s2 [K][P]) with
+ *   hyp[k][8] = (learning_rate, a_t, reg_l2_penalty, reg_l1_penalty, reg_l2_decay, reg_l1_decay, -, -) per member (a_t: Adam's
+ *   lr sqrt(1 - beta2^t) / (1 - beta1^t), formed by the caller) and per-element clip bounds [K][P]; a NaN value stays NaN.
+ * ssn_ens_stimulus_hetero_f32: ssn_stimulus_hetero_f32 (nv = 2) with v[k][2] = (V_E, V_I) of the draw's member. */
+typedef struct ssn_ens_grads {
+    int K, B, nv, NB, M, D;
+    const double *part;
+    const float *g_ext, *ext_base, *zin;
+    const float *dyn_row, *rate_row;
+    double scale_dyn, scale_rate;
+    const double *data_moments, *weights, *costs;
+    float *grads;
+    double *rec; int rstride;
+} ssn_ens_grads;
+typedef struct ssn_ens_apply {
+    int K, P, kind;
+    float beta1, beta2, eps, rho;
+    const float *hyp;
+    const float *clip_lo, *clip_hi;
+    float *p, *s1, *s2; const float *g;
+    double *rec; int rstride, rec_off;
+} ssn_ens_apply;
+long ssn_ens_record_doubles(int D, int P);
+int ssn_ens_moments_f32(const float *x, int K, int B, int D, double *sums, const double *data_moments, const double *weights,
+                        float *gx, double *rec, int rstride, void *stream);
+int ssn_ens_jds_grad_f32(const float *gW, const float *z, const float *p16, double *out, int K, int B, int N, void *stream);
+int ssn_ens_gen_grads_f32(const ssn_ens_grads *a, void *stream);
+int ssn_ens_apply_f32(const ssn_ens_apply *a, void *stream);
+int ssn_ens_stimulus_hetero_f32(const float *bw, const float *con, float smoothness, const float *zin, const float *v, float *ext,
+                                int K, int B, int NB, int N, void *stream);
+
 /* ---- 7. Fixed-point implicit gradient (tc_gan/gradient_expressions/SS_grad.py:17-99, make_w_batch.py:36-121) -----
  * dW[b][i][j][p][q] = d W[b][i][j] / d theta[p][q] for theta = J (which 0; independent of z, z may be NULL),
  * D (1) or S (2): the tensors make_WJ_with_x / make_WD_with_x / make_WS_with_x build (identity dJ'/dJ). */

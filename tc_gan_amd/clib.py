@@ -355,7 +355,42 @@ DECLARED_SYMBOLS = (
     'ssn_build_w_mt19937_tail_begin_f32', 'ssn_mt19937_plan_tail',
     'ssn_critic_num_params_act', 'ssn_critic_forward_act', 'ssn_critic_loss_grad_act', 'ssn_critic_input_grad_act',
     'ssn_critic_accuracy_act',
+    'ssn_ens_record_doubles', 'ssn_ens_moments_f32', 'ssn_ens_jds_grad_f32', 'ssn_ens_gen_grads_f32', 'ssn_ens_apply_f32',
+    'ssn_ens_stimulus_hetero_f32',
 )
+
+class EnsGrads(Structure):
+    """``ssn_ens_grads`` of include/ssnode_mi355x.h."""
+    _fields_ = [
+        ('K', c_int), ('B', c_int), ('nv', c_int), ('NB', c_int), ('M', c_int), ('D', c_int),
+        ('part', c_void_p), ('g_ext', c_void_p), ('ext_base', c_void_p), ('zin', c_void_p),
+        ('dyn_row', c_void_p), ('rate_row', c_void_p), ('scale_dyn', c_double), ('scale_rate', c_double),
+        ('data_moments', c_void_p), ('weights', c_void_p), ('costs', c_void_p), ('grads', c_void_p),
+        ('rec', c_void_p), ('rstride', c_int),
+    ]
+
+
+class EnsApply(Structure):
+    """``ssn_ens_apply`` of include/ssnode_mi355x.h."""
+    _fields_ = [
+        ('K', c_int), ('P', c_int), ('kind', c_int),
+        ('beta1', c_float), ('beta2', c_float), ('eps', c_float), ('rho', c_float),
+        ('hyp', c_void_p), ('clip_lo', c_void_p), ('clip_hi', c_void_p),
+        ('p', c_void_p), ('s1', c_void_p), ('s2', c_void_p), ('g', c_void_p),
+        ('rec', c_void_p), ('rstride', c_int), ('rec_off', c_int),
+    ]
+
+
+libssnode.ssn_ens_record_doubles.argtypes = [c_int, c_int]
+libssnode.ssn_ens_record_doubles.restype = c_long
+libssnode.ssn_ens_moments_f32.argtypes = [c_void_p, c_int, c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p]
+libssnode.ssn_ens_jds_grad_f32.argtypes = [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p]
+libssnode.ssn_ens_gen_grads_f32.argtypes = [POINTER(EnsGrads), c_void_p]
+libssnode.ssn_ens_apply_f32.argtypes = [POINTER(EnsApply), c_void_p]
+libssnode.ssn_ens_stimulus_hetero_f32.argtypes = [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                                  c_void_p]
+for _name in ('ssn_ens_moments_f32', 'ssn_ens_jds_grad_f32', 'ssn_ens_gen_grads_f32', 'ssn_ens_apply_f32', 'ssn_ens_stimulus_hetero_f32'):
+    getattr(libssnode, _name).restype = c_int
 
 libssnode.ssn_critic_num_params_act.argtypes = [c_void_p, c_void_p, c_int]
 libssnode.ssn_critic_num_params_act.restype = c_long

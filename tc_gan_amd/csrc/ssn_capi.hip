@@ -986,6 +986,64 @@ int ssn_lu_solve_f64(double* A, double* rhs, int* info, int nsys, int M, int nrh
     SSN_TRY(ssn::launch_lu_solve<double>(A, rhs, info, nsys, M, nrhs, (hipStream_t)stream));
     return 0;
 }
+long ssn_ens_record_doubles(int D, int P) { return (D < 0 || P < 0) ? -1 : 4L + 2L * D + 2L * P; }
+int ssn_ens_moments_f32(const float* x, int K, int B, int D, double* sums, const double* data_moments, const double* weights,
+                        float* gx, double* rec, int rstride, void* stream) {
+    if (K < 0 || B <= 0 || D < 0 || rstride < ssn_ens_record_doubles(D, 0) ||
+        (K > 0 && D > 0 && (!x || !sums || !data_moments || !weights || !gx || !rec))) {
+        g_last_error = "ssn_ens_moments: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_ens_moments(x, K, B, D, sums, data_moments, weights, gx, rec, rstride, (hipStream_t)stream));
+    return 0;
+}
+int ssn_ens_jds_grad_f32(const float* gW, const float* z, const float* p16, double* out, int K, int B, int N, void* stream) {
+    if (K < 0 || B < 0 || N < 1 || (K > 0 && B > 0 && (!gW || !z || !p16 || !out))) {
+        g_last_error = "ssn_ens_jds_grad: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_ens_jds_grad(gW, z, p16, out, K, B, N, (hipStream_t)stream));
+    return 0;
+}
+int ssn_ens_gen_grads_f32(const ssn_ens_grads* a, void* stream) {
+    if (!a || a->K < 0 || a->B <= 0 || a->nv < 0 || a->nv > 2 || a->NB <= 0 || a->M <= 0 || (a->M & 1) || a->D < 0 ||
+        a->rstride < ssn_ens_record_doubles(a->D, a->nv + 12) ||
+        (a->K > 0 && (!a->part || !a->dyn_row || !a->rate_row || !a->data_moments || !a->weights || !a->costs || !a->grads ||
+                      !a->rec || (a->nv > 0 && (!a->g_ext || !a->ext_base || !a->zin))))) {
+        g_last_error = "ssn_ens_gen_grads: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    ssn::EnsGradsArgs g{};
+    g.K = a->K; g.B = a->B; g.nv = a->nv; g.NB = a->NB; g.M = a->M; g.D = a->D;
+    g.part = a->part; g.g_ext = a->g_ext; g.ext_base = a->ext_base; g.zin = a->zin; g.dyn_row = a->dyn_row; g.rate_row = a->rate_row;
+    g.scale_dyn = a->scale_dyn; g.scale_rate = a->scale_rate;
+    g.data_moments = a->data_moments; g.weights = a->weights; g.costs = a->costs; g.grads = a->grads; g.rec = a->rec; g.rstride = a->rstride;
+    SSN_TRY(ssn::launch_ens_gen_grads(g, (hipStream_t)stream));
+    return 0;
+}
+int ssn_ens_apply_f32(const ssn_ens_apply* a, void* stream) {
+    if (!a || a->K < 0 || a->P <= 0 || a->kind < 0 || a->kind > 2 || a->rec_off < 0 || a->rstride < a->rec_off + 2 * a->P ||
+        (a->K > 0 && (!a->hyp || !a->clip_lo || !a->clip_hi || !a->p || !a->g || !a->rec || (a->kind > 0 && !a->s1) ||
+                      (a->kind == 1 && !a->s2)))) {
+        g_last_error = "ssn_ens_apply: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    ssn::EnsApplyArgs g{};
+    g.K = a->K; g.P = a->P; g.kind = a->kind; g.beta1 = a->beta1; g.beta2 = a->beta2; g.eps = a->eps; g.rho = a->rho;
+    g.hyp = a->hyp; g.clip_lo = a->clip_lo; g.clip_hi = a->clip_hi; g.p = a->p; g.s1 = a->s1; g.s2 = a->s2; g.g = a->g;
+    g.rec = a->rec; g.rstride = a->rstride; g.rec_off = a->rec_off;
+    SSN_TRY(ssn::launch_ens_apply(g, (hipStream_t)stream));
+    return 0;
+}
+int ssn_ens_stimulus_hetero_f32(const float* bw, const float* con, float smoothness, const float* zin, const float* v, float* ext,
+                                int K, int B, int NB, int N, void* stream) {
+    if (K < 0 || B < 0 || NB < 0 || N < 1 || !(smoothness > 0.f) || ((long)K * B * NB > 0 && (!bw || !con || !zin || !v || !ext))) {
+        g_last_error = "ssn_ens_stimulus_hetero: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_ens_stimulus_hetero(bw, con, smoothness, zin, v, ext, K, B, NB, N, (hipStream_t)stream));
+    return 0;
+}
 int ssn_moment_sums_f32(const float* x, int B, int D, double* sums, void* stream) {
     if (B < 0 || D < 0 || (D > 0 && (!x || !sums))) {
         g_last_error = "ssn_moment_sums: invalid argument";

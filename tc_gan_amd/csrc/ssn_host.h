@@ -105,6 +105,33 @@ struct GenGradsArgs {
 };
 hipError_t launch_gen_grads(const GenGradsArgs& a, hipStream_t st);
 
+// ssn_ensemble.hip (ensembles of moment-matching runs: member k owns draws [k B, (k + 1) B))
+struct EnsGradsArgs {
+    int K, B, nv, NB, M, D;
+    const double* part;                  // [K B][4][3] from ens_jds_grad_kernel
+    const float *g_ext, *ext_base, *zin; // nv > 0: [K B][NB][M], [K B][NB][M], [K B][M]
+    const float *dyn_row, *rate_row;     // [K B][NB][M] of the forward
+    double scale_dyn, scale_rate;        // 1 / (elements of ONE member's penalty means)
+    const double *data_moments, *weights, *costs;   // [K][2][D], [K][2][D], [K][2] = (dynamics_cost, rate_cost)
+    float* grads;                        // [K][nv + 12]
+    double* rec; int rstride;            // record rows
+};
+struct EnsApplyArgs {
+    int K, P, kind;
+    float beta1, beta2, eps, rho;
+    const float* hyp;                    // [K][8]: lr, a_t, l2_penalty, l1_penalty, l2_decay, l1_decay
+    const float *clip_lo, *clip_hi;      // [K][P]
+    float *p, *s1, *s2; const float* g;  // [K][P]
+    double* rec; int rstride, rec_off;
+};
+hipError_t launch_ens_moments(const float* x, int K, int B, int D, double* sums, const double* data_moments, const double* weights,
+                              float* gx, double* rec, int rstride, hipStream_t st);
+hipError_t launch_ens_jds_grad(const float* gW, const float* z, const float* p16, double* out, int K, int B, int N, hipStream_t st);
+hipError_t launch_ens_gen_grads(const EnsGradsArgs& a, hipStream_t st);
+hipError_t launch_ens_apply(const EnsApplyArgs& a, hipStream_t st);
+hipError_t launch_ens_stimulus_hetero(const float* bw, const float* con, float smooth, const float* zin, const float* v, float* ext,
+                                      int K, int B, int NB, int N, hipStream_t st);
+
 // ssn_solver.hip
 template <typename T> bool regw_supported(int M, int NB);
 template <typename T> hipError_t launch_regw(const SolveArgs<T>& a, hipStream_t st);
