@@ -734,6 +734,25 @@ int ssn_mt19937_plan(int pos, unsigned long long total, unsigned long long skip,
 int ssn_mt19937_plan_tail(int pos, unsigned long long total, unsigned long long skip, unsigned long long count, int tail_kind,
                           unsigned long long tail_total, unsigned long long tail_skip, unsigned long long tail_count, long *out);
 
+/* ---- Scoring the checkpoints of a run (analyzers/distdiff.py; csrc/ssn_score.hip) ---------------------------------
+ * S recorded parameter sets share one noise draw and run as one forward batch of S B draws (set s owns draws [s B, (s + 1) B));
+ * the tuning curves are reduced to two-sample Kolmogorov-Smirnov statistics against the truth on the device.
+ * ssn_build_w_table_f32: W[s][b] = make_W_with_x(z[b]; J_s, D_s, S_s) for s < S, b < B; jds_table: DEVICE float[S][12] (J, D, S
+ *   row-major, the layout of ssn_build_w_devparams_f32), z: device [B][2N][2N], W: device [S][B][2N][2N].  z is read once per
+ *   draw.  The arithmetic of ssn_build_w_f32: the same values give the same bits.
+ * ssn_tc_features_f32: tc: device [rows][NC NB Q], column (c NB + b) Q + q (the order of networks/utils.gridify_tc_samples with
+ *   Q = cell types x probes); feat: device [rows][4][NC Q]: of every curve (c, q) over its NB bandwidths, in this order,
+ *   maxrate = max_b tc, si = 1 - tc[NB - 1] / maxrate, prefbw = first index of the maximum, ipr = (sum tc)^2 / (NB sum tc^2).
+ * ssn_ks_columns_f32: x: device [S][B][C]; truth_sorted: device [C][T], every column ascending with its m[c] finite values
+ *   first (m: device int[C]).  n[s][c] = number of finite values among x[s][.][c] (the others are left out), num[s][c] =
+ *   max over the pooled points v of |#{x <= v} m - #{t <= v} n|, so that the KS statistic is num / (n m); n = 0 or m = 0
+ *   gives num = 0.  B <= SSN_KS_MAX_DRAWS (one workgroup sorts a column in LDS); more is refused. */
+#define SSN_KS_MAX_DRAWS 16384
+int ssn_build_w_table_f32(const float *z, const float *jds_table, float *W, int S, int B, int N, void *stream);
+int ssn_tc_features_f32(const float *tc, float *feat, long rows, int NC, int NB, int Q, void *stream);
+int ssn_ks_columns_f32(const float *x, const float *truth_sorted, const int *m, int S, int B, int C, int T, int *n,
+                       long long *num, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

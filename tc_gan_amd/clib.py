@@ -357,6 +357,7 @@ DECLARED_SYMBOLS = (
     'ssn_critic_accuracy_act',
     'ssn_ens_record_doubles', 'ssn_ens_moments_f32', 'ssn_ens_jds_grad_f32', 'ssn_ens_gen_grads_f32', 'ssn_ens_apply_f32',
     'ssn_ens_stimulus_hetero_f32',
+    'ssn_build_w_table_f32', 'ssn_tc_features_f32', 'ssn_ks_columns_f32',
 )
 
 class EnsGrads(Structure):
@@ -390,6 +391,14 @@ libssnode.ssn_ens_apply_f32.argtypes = [POINTER(EnsApply), c_void_p]
 libssnode.ssn_ens_stimulus_hetero_f32.argtypes = [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                                   c_void_p]
 for _name in ('ssn_ens_moments_f32', 'ssn_ens_jds_grad_f32', 'ssn_ens_gen_grads_f32', 'ssn_ens_apply_f32', 'ssn_ens_stimulus_hetero_f32'):
+    getattr(libssnode, _name).restype = c_int
+
+#: most values per column `ssn_ks_columns_f32` takes (SSN_KS_MAX_DRAWS of the header)
+KS_MAX_DRAWS = 16384
+libssnode.ssn_build_w_table_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
+libssnode.ssn_tc_features_f32.argtypes = [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p]
+libssnode.ssn_ks_columns_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+for _name in ('ssn_build_w_table_f32', 'ssn_tc_features_f32', 'ssn_ks_columns_f32'):
     getattr(libssnode, _name).restype = c_int
 
 libssnode.ssn_critic_num_params_act.argtypes = [c_void_p, c_void_p, c_int]

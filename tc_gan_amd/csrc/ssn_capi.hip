@@ -1044,6 +1044,35 @@ int ssn_ens_stimulus_hetero_f32(const float* bw, const float* con, float smoothn
     SSN_TRY(ssn::launch_ens_stimulus_hetero(bw, con, smoothness, zin, v, ext, K, B, NB, N, (hipStream_t)stream));
     return 0;
 }
+int ssn_build_w_table_f32(const float* z, const float* jds_table, float* W, int S, int B, int N, void* stream) {
+    if (S < 0 || B < 0 || N < 1 || ((long)S * B > 0 && (!z || !jds_table || !W))) {
+        g_last_error = "ssn_build_w_table_f32: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_build_w_table(z, jds_table, W, S, B, N, (hipStream_t)stream));
+    return 0;
+}
+int ssn_tc_features_f32(const float* tc, float* feat, long rows, int NC, int NB, int Q, void* stream) {
+    if (rows < 0 || NC < 0 || NB < 1 || Q < 0 || (rows * NC * Q > 0 && (!tc || !feat))) {
+        g_last_error = "ssn_tc_features_f32: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_tc_features(tc, feat, rows, NC, NB, Q, (hipStream_t)stream));
+    return 0;
+}
+int ssn_ks_columns_f32(const float* x, const float* truth_sorted, const int* m, int S, int B, int C, int T, int* n,
+                       long long* num, void* stream) {
+    if (B > SSN_KS_MAX_DRAWS) {
+        g_last_error = "ssn_ks_columns_f32: more than 16384 values per column (the sort runs in 64 KiB of LDS)";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if (S < 0 || B < 1 || C < 0 || T < 0 || ((long)S * C > 0 && (!x || !m || !n || !num || (T > 0 && !truth_sorted)))) {
+        g_last_error = "ssn_ks_columns_f32: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_ks_columns(x, truth_sorted, m, S, B, C, T, n, num, (hipStream_t)stream));
+    return 0;
+}
 int ssn_moment_sums_f32(const float* x, int B, int D, double* sums, void* stream) {
     if (B < 0 || D < 0 || (D > 0 && (!x || !sums))) {
         g_last_error = "ssn_moment_sums: invalid argument";

@@ -313,6 +313,12 @@ template <typename T> hipError_t launch_penalty_means(const T* dyn, const T* rat
                                                       int nsamp = 0, int NB = 0, int M = 0);
 template <typename T> hipError_t launch_dot(const T* x, const T* y, T* out, int dim, hipStream_t st);
 
+// ssn_score.hip (scoring the checkpoints of a run: S parameter sets on one shared noise draw, KS statistics on the device)
+hipError_t launch_build_w_table(const float* z, const float* table, float* W, int S, int B, int N, hipStream_t st);
+hipError_t launch_tc_features(const float* tc, float* feat, long R, int NC, int NB, int Q, hipStream_t st);
+hipError_t launch_ks_columns(const float* x, const float* t, const int* m, int S, int B, int C, int T, int* n_out,
+                             long long* num_out, hipStream_t st);
+
 // ssn_mt19937.hip: numpy's RandomState.random_sample on the device (key / pos: the host state, in/out)
 int mt19937_jump_poly(unsigned long long nblocks, unsigned long long* bits);
 hipError_t mt19937_draw(unsigned int* key, int* pos, unsigned long long total, unsigned long long skip, unsigned long long count,

@@ -1,0 +1,149 @@
+"""Time the batched checkpoint scorer (analyzers/distdiff.score_parameter_sets) against the loop a user can write without it:
+one sampler forward per checkpoint on the same z, the curves copied to the host, features and KS statistics in numpy there.
+Default shape: the paper's Fig. 4 run -- num_sites 101, 8 bandwidths, seqlen 240 / skip_steps 200, deg-heteroin, truth 2048
+rows.
+
+    python tools/time_distdiff.py [--draws 30,128,1024] [--checkpoints 256,256,32] [--repeats 3] [--out FILE]
+    python tools/time_distdiff.py --once 128          # one batched pass alone (for a kernel trace)
+
+Both paths run the same generator kernel (what 'auto' resolves to for the batched chunk), are warmed, alternate, and every
+window ends in a device synchronise and holds as many passes over the checkpoints as make it --window-seconds long.  One JSON
+line per size: checkpoints per second of each repeat, their median and their spread (max - min over the median)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tc_gan_amd.analyzers import distdiff  # noqa: E402
+from tc_gan_amd.networks.fixed_time_sampler import FixedTimeTuningCurveSampler, new_JDS  # noqa: E402
+
+SHAPE = dict(num_sites=101, bandwidths=[0, 0.0625, 0.125, 0.1875, 0.25, 0.5, 0.75, 1], contrasts=[20.0], seqlen=240, skip_steps=200,
+             ssn_type='deg-heteroin', norm_probes=[0, 0.125, 0.25, 0.5, 0.75], include_inhibitory_neurons=False, tau_E=2)
+TRUTH = dict(new_JDS, V=0.5)
+
+
+def thetas(count, seed=0):
+    """A made-up run: from J = D = S = 0.01-like values towards the truth, with jitter."""
+    rs = np.random.RandomState(seed)
+    out = []
+    for i in range(count):
+        a = (i + 1.0) / count
+        th = {k: TRUTH[k] * (0.5 + 0.5 * a) * (1 + 0.05 * (rs.rand(2, 2) - 0.5)) for k in 'JDS'}
+        th['V'] = 0.1 + 0.4 * a
+        out.append(th)
+    return out
+
+
+def host_scores(tc, truth, shape):
+    """Features and integer KS statistics of one checkpoint's curves in numpy (what the loop's user computes on the host)."""
+    nc, nb, q = shape
+    def feats(x):
+        g = x.reshape(len(x), nc, nb, q)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            mx = g.max(axis=2)
+            return np.concatenate([mx, 1 - g[:, :, nb - 1] / mx, g.argmax(axis=2).astype(x.dtype),
+                                   g.sum(axis=2) ** 2 / (nb * (g ** 2).sum(axis=2))], axis=1).reshape(len(x), -1)
+    x, t = np.concatenate([tc, feats(tc)], axis=1), np.concatenate([truth, feats(truth)], axis=1)
+    num = np.zeros(x.shape[1], dtype=np.int64)
+    for c in range(x.shape[1]):
+        xs, ts = np.sort(x[np.isfinite(x[:, c]), c]), np.sort(t[np.isfinite(t[:, c]), c])
+        pooled = np.concatenate([xs, ts])
+        if len(xs) and len(ts):
+            num[c] = np.abs(np.searchsorted(xs, pooled, side='right').astype(np.int64) * len(ts)
+                            - np.searchsorted(ts, pooled, side='right').astype(np.int64) * len(xs)).max()
+    return num
+
+
+def looped(cfg, sets, truth, draws, seed, kernel, score=True):
+    sampler = FixedTimeTuningCurveSampler.from_dict(dict(cfg, batchsize=draws, gen_kernel=kernel, **sets[0]))
+    z, zin = distdiff.shared_noise(cfg, draws, seed)
+    shape = (len(cfg['contrasts']), len(cfg['bandwidths']), len(cfg['norm_probes']))
+    nums = []
+    for th in sets:
+        sampler.gen.set_params(th)
+        out = sampler.gen.forward(stimulator_bandwidths=sampler.stimulator_bandwidths,
+                                  stimulator_contrasts=sampler.stimulator_contrasts, model_zs=z, model_zs_in=zin)
+        tc = out.prober_tuning_curve.cpu().numpy()
+        if score:
+            nums.append(host_scores(tc, truth, shape))
+    torch.cuda.synchronize()
+    return np.stack(nums) if score else None
+
+
+def batched(cfg, sets, truth, draws, seed, kernel, budget):
+    res = distdiff.score_parameter_sets(cfg, sets, truth, draws=draws, seed=seed, gen_kernel=kernel, max_draws_per_launch=budget)
+    torch.cuda.synchronize()
+    return res
+
+
+def window(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--draws', default='30,128,1024')
+    ap.add_argument('--checkpoints', default='256,256,32', help='checkpoints per size (one value: for all)')
+    ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--truth-size', type=int, default=2048)
+    ap.add_argument('--window-seconds', type=float, default=1.5)
+    ap.add_argument('--gen-kernel', default='auto')
+    ap.add_argument('--max-draws-per-launch', type=int, default=distdiff.DEFAULT_MAX_DRAWS_PER_LAUNCH)
+    ap.add_argument('--num-sites', type=int, default=SHAPE['num_sites'])
+    ap.add_argument('--once', type=int, default=None, help='one warmed batched pass at this many draws, nothing else')
+    ap.add_argument('--out')
+    ns = ap.parse_args()
+    cfg = dict(SHAPE, num_sites=ns.num_sites)
+    truth = np.concatenate([FixedTimeTuningCurveSampler.from_dict(dict(cfg, batchsize=256, seed=42 + i, **TRUTH)).sample()
+                            for i in range(-(-ns.truth_size // 256))])[:ns.truth_size]
+    sizes = [int(d) for d in ns.draws.split(',')]
+    counts = [int(c) for c in ns.checkpoints.split(',')]
+    counts = counts * len(sizes) if len(counts) == 1 else counts
+    if ns.once is not None:
+        sets = thetas(counts[0])
+        batched(cfg, sets[:2], truth, ns.once, 0, ns.gen_kernel, ns.max_draws_per_launch)
+        res = batched(cfg, sets, truth, ns.once, 0, ns.gen_kernel, ns.max_draws_per_launch)
+        print(json.dumps(dict(once=ns.once, checkpoints=len(sets), gen_kernel=res['gen_kernel'], chunks=res['chunks'])))
+        return
+    rows = []
+    for draws, S in zip(sizes, counts):
+        sets = thetas(S)
+        res = batched(cfg, sets, truth, draws, 0, ns.gen_kernel, ns.max_draws_per_launch)      # warm-up of every chunk shape
+        kernel = res['gen_kernel']
+        want = looped(cfg, sets[:3], truth, draws, 0, kernel)                                   # warm-up, and the same answers
+        C = want.shape[1] * 2 // 3                     # raw columns (8 bandwidths: 8 raw + 4 feature columns per curve); the host's
+        same = bool((want[:, :C] == res['num'][:3, :C]).all())      # fp32 features may round otherwise than the kernel's
+        paths = dict(batched=lambda: batched(cfg, sets, truth, draws, 0, kernel, ns.max_draws_per_launch),
+                     loop=lambda: looped(cfg, sets, truth, draws, 0, kernel),
+                     loop_forward_only=lambda: looped(cfg, sets, truth, draws, 0, kernel, score=False))
+        # passes per window: enough of them for a window of --window-seconds (a pass over S checkpoints may take milliseconds)
+        passes = {name: max(1, int(np.ceil(ns.window_seconds / window(fn)))) for name, fn in paths.items()}
+        secs = {name: [] for name in paths}
+        for _ in range(ns.repeats):
+            for name, fn in paths.items():                 # alternating
+                secs[name].append(window(lambda: [fn() for _ in range(passes[name])]))
+        cps = {name: [S * passes[name] / t for t in secs[name]] for name in paths}
+        row = dict(draws=draws, checkpoints=S, gen_kernel=kernel, chunk=res['chunk'], chunks=len(res['chunks']),
+                   loop_equals_batched_raw_columns_first3=same, passes_per_window=passes, window_seconds=secs)
+        for name in paths:
+            row[name + '_cps'] = cps[name]
+            row[name + '_cps_median'] = float(np.median(cps[name]))
+            row[name + '_cps_spread'] = (max(cps[name]) - min(cps[name])) / float(np.median(cps[name]))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    if ns.out:
+        with open(ns.out, 'w') as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == '__main__':
+    main()
