@@ -3,8 +3,11 @@
 Host-side mirror of ``ConditionalDiscriminator`` + ``ConditionalCriticTrainer``
 (networks/cwgan.py:123-214) and ``Updater`` (networks/wgan.py:111-165): parameters live
 in ONE flat fp32 device buffer in Lasagne's ``get_all_params`` order
-[W_1, b_1, ..., W_L, b_L, W_out]; every pass is a chain of MFMA GEMM launches in
-``csrc/ssn_critic.hip``.
+[W_1, b_1, ..., W_L, b_L, W_out] (a learnable scale, where a layer has one, between its W and b).  `Critic` describes the
+network to the library -- widths, per-layer flags, activation code -- and every pass is ONE call of the `ssn_critic_*_act`
+family; the library picks the kernels that compute that critic (fused row-block kernels, the layer-by-layer MFMA GEMM chain
+with its row-block form for wide layers, or the general LayerNorm / activation chain: the rule is stated once, in DESIGN.md
+section 3.8a and above `critic_path` in ``csrc/ssn_capi.hip``).
 """
 import ctypes
 
@@ -23,7 +26,7 @@ def _stream():
 
 # lasagne.nonlinearities names -> slope below zero (rectify, LeakyRectify(0.01), LeakyRectify(1/3), identity)
 LEAK = {'rectify': 0.0, 'leaky_rectify': 0.01, 'very_leaky_rectify': 1.0 / 3.0, 'linear': 1.0, 'identity': 1.0}
-# ... -> activation code of the general entry points (`ssn_critic_*_act`, include/ssnode_mi355x.h)
+# ... -> activation code of the critic's entry points (`ssn_critic_*_act`, include/ssnode_mi355x.h)
 ACT = {'rectify': 0, 'leaky_rectify': 1, 'very_leaky_rectify': 2, 'linear': 3, 'identity': 3, 'tanh': 4, 'sigmoid': 5,
        'softplus': 6, 'elu': 7}
 
@@ -71,8 +74,11 @@ class Critic(object):
             if n != 'layer' and 'use_scale' in o:
                 raise ValueError('use_scale is an option of layer-normalised layers')
             self.scaled.append(n == 'layer' and (nonlinearity != 'rectify' if use == 'auto' else bool(use)))
-        # the general entry points: a smooth nonlinearity anywhere, or a scale (the rectify / leaky fast paths have neither)
-        self.general = self.act >= 4 or any(self.scaled)
+        self.layer_norm = any(n == 'layer' for n in norms)
+        # the critic in its general form: a smooth nonlinearity anywhere, a scale, or a leak next to a layer normalisation (the
+        # rectify / leaky fast paths have none of these).  The library draws the same line when it picks the kernels; here it
+        # decides `has_step`, the parameter count and the workspace query.
+        self.general = self.act >= 4 or any(self.scaled) or bool(self.leak and self.layer_norm)
         clib.require_gpu()
         self.nx = int(nx)
         self.layers = [int(w) for w in layers]
@@ -82,12 +88,9 @@ class Critic(object):
         self.hide_cell_type = int(bool(hide_cell_type))
         self.precision = PRECISION[precision]
         self._dims_c = (ctypes.c_int * len(self.dims))(*self.dims)
-        self.layer_norm = any(n == 'layer' for n in norms)
         self._norm_c = (ctypes.c_int * max(len(norms), 1))(*[int(n == 'layer') for n in norms])
-        # (flags of the general entry points: 1 = layer normalisation, 3 = with the learnable scale after it)
+        # (per-layer flags of the passes: 1 = layer normalisation, 3 = with the learnable scale after it; `_norm_c`: `step`'s 0 / 1)
         self._flags_c = (ctypes.c_int * max(len(norms), 1))(*[int(n == 'layer') + 2 * int(sc) for n, sc in zip(norms, self.scaled)])
-        if self.leak and self.layer_norm and not self.general:
-            self.general = True              # (leaky + layer normalisation without its scale: no fast path for that either)
         self.num_params = int(libssnode.ssn_critic_num_params_act(self._dims_c, self._flags_c, self.nlayers) if self.general
                               else libssnode.ssn_critic_num_params(self._dims_c, self.nlayers))
         assert self.num_params == sum(int(np.prod(shape)) for _, shape in self.param_shapes())
@@ -242,24 +245,9 @@ class Critic(object):
         batch = x.shape[0]
         out = torch.empty(batch, device=self.device, dtype=torch.float32)
         ws = self._workspace(batch, 0)
-        if self.general:
-            clib.check(libssnode.ssn_critic_forward_act(
-                self.params.data_ptr(), self._dims_c, self._flags_c, self.nlayers, self.act, x.data_ptr(), cond.data_ptr(), batch,
-                self.hide_cell_type, out.data_ptr(), ws.data_ptr(), self.precision, _stream()), 'ssn_critic_forward_act')
-            return out
-        if self.layer_norm:
-            clib.check(libssnode.ssn_critic_forward_norm(
-                self.params.data_ptr(), self._dims_c, self._norm_c, self.nlayers, x.data_ptr(), cond.data_ptr(), batch,
-                self.hide_cell_type, out.data_ptr(), ws.data_ptr(), self.precision, _stream()), 'ssn_critic_forward_norm')
-            return out
-        if self.leak:
-            clib.check(libssnode.ssn_critic_forward_leaky(
-                self.params.data_ptr(), self._dims_c, self.nlayers, x.data_ptr(), cond.data_ptr(), batch, self.hide_cell_type,
-                self.leak, out.data_ptr(), ws.data_ptr(), self.precision, _stream()), 'ssn_critic_forward_leaky')
-            return out
-        clib.check(libssnode.ssn_critic_forward(self.params.data_ptr(), self._dims_c, self.nlayers, x.data_ptr(),
-                                                cond.data_ptr(), batch, self.hide_cell_type, out.data_ptr(),
-                                                ws.data_ptr(), self.precision, _stream()), 'ssn_critic_forward')
+        clib.check(libssnode.ssn_critic_forward_act(
+            self.params.data_ptr(), self._dims_c, self._flags_c, self.nlayers, self.act, x.data_ptr(), cond.data_ptr(), batch,
+            self.hide_cell_type, out.data_ptr(), ws.data_ptr(), self.precision, _stream()), 'ssn_critic_forward_act')
         return out
 
     def loss_grad(self, xg, cg, xd, cd, xp, cp, lmd):
@@ -268,32 +256,11 @@ class Critic(object):
         ng, nd, npn = xg.shape[0], xd.shape[0], xp.shape[0]
         ws = self._workspace(ng + nd, npn)
         self._dvals = torch.empty(ng + nd, device=self.device, dtype=torch.float32)
-        if self.general:
-            clib.check(libssnode.ssn_critic_loss_grad_act(
-                self.params.data_ptr(), self._dims_c, self._flags_c, self.nlayers, self.act, xg.data_ptr(), cg.data_ptr(),
-                xd.data_ptr(), cd.data_ptr(), xp.data_ptr(), cp.data_ptr(), ng, nd, npn, float(lmd), self.hide_cell_type,
-                self.grads.data_ptr(), self.stats.data_ptr(), self._dvals.data_ptr(), ws.data_ptr(), self.precision,
-                _stream()), 'ssn_critic_loss_grad_act')
-            return self.stats
-        if self.layer_norm:
-            clib.check(libssnode.ssn_critic_loss_grad_norm(
-                self.params.data_ptr(), self._dims_c, self._norm_c, self.nlayers, xg.data_ptr(), cg.data_ptr(),
-                xd.data_ptr(), cd.data_ptr(), xp.data_ptr(), cp.data_ptr(), ng, nd, npn, float(lmd), self.hide_cell_type,
-                self.grads.data_ptr(), self.stats.data_ptr(), self._dvals.data_ptr(), ws.data_ptr(), self.precision,
-                _stream()), 'ssn_critic_loss_grad_norm')
-            return self.stats
-        if self.leak:
-            clib.check(libssnode.ssn_critic_loss_grad_leaky(
-                self.params.data_ptr(), self._dims_c, self.nlayers, xg.data_ptr(), cg.data_ptr(), xd.data_ptr(),
-                cd.data_ptr(), xp.data_ptr(), cp.data_ptr(), ng, nd, npn, float(lmd), self.hide_cell_type, self.leak,
-                self.grads.data_ptr(), self.stats.data_ptr(), self._dvals.data_ptr(), ws.data_ptr(), self.precision,
-                _stream()), 'ssn_critic_loss_grad_leaky')
-            return self.stats
-        clib.check(libssnode.ssn_critic_loss_grad(
-            self.params.data_ptr(), self._dims_c, self.nlayers, xg.data_ptr(), cg.data_ptr(), xd.data_ptr(),
-            cd.data_ptr(), xp.data_ptr(), cp.data_ptr(), ng, nd, npn, float(lmd), self.hide_cell_type,
+        clib.check(libssnode.ssn_critic_loss_grad_act(
+            self.params.data_ptr(), self._dims_c, self._flags_c, self.nlayers, self.act, xg.data_ptr(), cg.data_ptr(),
+            xd.data_ptr(), cd.data_ptr(), xp.data_ptr(), cp.data_ptr(), ng, nd, npn, float(lmd), self.hide_cell_type,
             self.grads.data_ptr(), self.stats.data_ptr(), self._dvals.data_ptr(), ws.data_ptr(), self.precision,
-            _stream()), 'ssn_critic_loss_grad')
+            _stream()), 'ssn_critic_loss_grad_act')
         return self.stats
 
     def interpolate(self, eps, xd, xg):
@@ -311,33 +278,15 @@ class Critic(object):
         batch = x.shape[0]
         gx = torch.empty((batch, self.nx), device=self.device, dtype=torch.float32)
         ws = self._workspace(batch, batch)
-        if self.general:
-            clib.check(libssnode.ssn_critic_input_grad_act(
-                self.params.data_ptr(), self._dims_c, self._flags_c, self.nlayers, self.act, x.data_ptr(), cond.data_ptr(), batch,
-                self.hide_cell_type, float(scale), gx.data_ptr(), self.stats.data_ptr(), ws.data_ptr(), self.precision,
-                _stream()), 'ssn_critic_input_grad_act')
-            return gx, self.stats[0]
-        if self.layer_norm:
-            clib.check(libssnode.ssn_critic_input_grad_norm(
-                self.params.data_ptr(), self._dims_c, self._norm_c, self.nlayers, x.data_ptr(), cond.data_ptr(), batch,
-                self.hide_cell_type, float(scale), gx.data_ptr(), self.stats.data_ptr(), ws.data_ptr(), self.precision,
-                _stream()), 'ssn_critic_input_grad_norm')
-            return gx, self.stats[0]
-        if self.leak:
-            clib.check(libssnode.ssn_critic_input_grad_leaky(
-                self.params.data_ptr(), self._dims_c, self.nlayers, x.data_ptr(), cond.data_ptr(), batch,
-                self.hide_cell_type, self.leak, float(scale), gx.data_ptr(), self.stats.data_ptr(), ws.data_ptr(),
-                self.precision, _stream()), 'ssn_critic_input_grad_leaky')
-            return gx, self.stats[0]
-        clib.check(libssnode.ssn_critic_input_grad(
-            self.params.data_ptr(), self._dims_c, self.nlayers, x.data_ptr(), cond.data_ptr(), batch,
+        clib.check(libssnode.ssn_critic_input_grad_act(
+            self.params.data_ptr(), self._dims_c, self._flags_c, self.nlayers, self.act, x.data_ptr(), cond.data_ptr(), batch,
             self.hide_cell_type, float(scale), gx.data_ptr(), self.stats.data_ptr(), ws.data_ptr(), self.precision,
-            _stream()), 'ssn_critic_input_grad')
+            _stream()), 'ssn_critic_input_grad_act')
         return gx, self.stats[0]
 
     def accuracy_device(self, xg, cg, xd, cd, out=None):
         """mean D(xg) - mean D(xd) (cwgan.py:139-147) as a 1-element device tensor (`out`, when given), no host wait:
-        ONE library call (`ssn_critic_accuracy`: two forwards -- every output row depends on its own input row only, and
+        ONE library call (`ssn_critic_accuracy_act`: two forwards -- every output row depends on its own input row only, and
         stacking the rows would cost two more launches -- and one reduction in a fixed order)."""
         xg, cg, xd, cd = self._checked((xg, cg), (xd, cd))
         ng, nd = xg.shape[0], xd.shape[0]
@@ -347,16 +296,10 @@ class Critic(object):
         dv = self.__dict__.get('_acc_dvals')
         if dv is None or dv.numel() < ng + nd:
             dv = self._acc_dvals = torch.empty(ng + nd, device=self.device, dtype=torch.float32)
-        if self.general:
-            clib.check(libssnode.ssn_critic_accuracy_act(
-                self.params.data_ptr(), self._dims_c, self._flags_c, self.nlayers, self.act, xg.data_ptr(), cg.data_ptr(),
-                xd.data_ptr(), cd.data_ptr(), ng, nd, self.hide_cell_type, out.data_ptr(), dv.data_ptr(), ws.data_ptr(),
-                self.precision, _stream()), 'ssn_critic_accuracy_act')
-            return out
-        clib.check(libssnode.ssn_critic_accuracy(
-            self.params.data_ptr(), self._dims_c, self._norm_c if self.layer_norm else None, self.nlayers, float(self.leak),
-            xg.data_ptr(), cg.data_ptr(), xd.data_ptr(), cd.data_ptr(), ng, nd, self.hide_cell_type, out.data_ptr(),
-            dv.data_ptr(), ws.data_ptr(), self.precision, _stream()), 'ssn_critic_accuracy')
+        clib.check(libssnode.ssn_critic_accuracy_act(
+            self.params.data_ptr(), self._dims_c, self._flags_c, self.nlayers, self.act, xg.data_ptr(), cg.data_ptr(),
+            xd.data_ptr(), cd.data_ptr(), ng, nd, self.hide_cell_type, out.data_ptr(), dv.data_ptr(), ws.data_ptr(),
+            self.precision, _stream()), 'ssn_critic_accuracy_act')
         return out
 
     def accuracy(self, xg, cg, xd, cd):

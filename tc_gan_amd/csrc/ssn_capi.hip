@@ -539,6 +539,114 @@ int gen_backward_impl(const T* W, const T* traj, T* delta, const T* gta, T* g_ex
     return 0;
 }
 
+// ---- the WGAN-GP critic: one description, one choice of kernels ---------------------------------------------------------------
+// Every exported critic pass fills a CriticNet and goes through the four functions below; critic_path is the ONLY place that
+// decides which kernels compute a critic.
+struct CriticNet {
+    const float* params; const int* dims;
+    const int* flags;        // HOST int[nlayers] or NULL (all plain): bit 0 = layer normalisation, bit 1 = learnable scale after it
+    int nlayers;
+    int act;                 // the public activation code (0 rectify ... 7 elu): what the general chain computes
+    float leak;              // slope below zero of a piecewise-linear act (codes 0-3): what the plain chain computes
+    int hide_cell_type; bool bf16;
+};
+// slope of activation codes 0-3 (the table of act_from_code in ssn_critic_ln.hip); the smooth ones have none
+float act_leak(int act) {
+    static const float leak[4] = {0.f, 0.01f, 1.f / 3.f, 1.f};
+    return act >= 0 && act < 4 ? leak[act] : 0.f;
+}
+// Critics whose layers are all <= 128 wide fit the fused row-block kernels (ssn_critic_fused.hip: 3 launches per update, fp32
+// arithmetic whatever `precision` says).  Above ~2048 stacked rows the layer-by-layer chain (fixed ~250 us of launch latency,
+// MFMA arithmetic) is as fast as they are (plain FMAs, time proportional to the rows).  SSN_CRITIC_FUSED=0 in the environment
+// switches them off (A/B timing, tests of the other paths).
+bool fused_ok(const int* dims, int nlayers, long rows) {
+    static const bool enabled = [] { const char* v = std::getenv("SSN_CRITIC_FUSED"); return !(v && v[0] == '0'); }();
+    return enabled && rows <= 2048 && ssn::critic_fused_supported(dims, nlayers);
+}
+// Fused: the row-block kernels above (rectify, with or without layer normalisation; conditional critics only).
+// Plain: the layer-by-layer MFMA GEMM chain of ssn_critic.hip (plain layers, any slope; wide layers take its row-block form,
+//        ssn_critic_rows.hip, inside ssn::critic_loss_grad).
+// General: the chain of ssn_critic_ln.hip (layer normalisation, scales, smooth nonlinearities).
+enum class CriticPath { Fused, Plain, General };
+// rows: the stacked rows of the pass; conds: every condition pointer of the call is given
+CriticPath critic_path(const CriticNet& net, long rows, bool conds) {
+    bool norm = false, scaled = false;
+    for (int l = 0; net.flags && l < net.nlayers; ++l) { norm = norm || (net.flags[l] & 1); scaled = scaled || (net.flags[l] & 2); }
+    if (scaled || net.act >= 4 || (norm && net.leak != 0.f)) return CriticPath::General;
+    if (!norm && net.leak != 0.f) return CriticPath::Plain;        // (the fused kernels have no slope)
+    if (conds && fused_ok(net.dims, net.nlayers, rows)) return CriticPath::Fused;
+    return norm ? CriticPath::General : CriticPath::Plain;
+}
+int critic_net_forward(const CriticNet& n, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st) {
+    switch (critic_path(n, batch, cond != nullptr)) {
+    case CriticPath::Fused:
+        SSN_TRY(ssn::critic_fused_forward(n.params, n.dims, n.flags, n.nlayers, x, cond, batch, n.hide_cell_type, out, ws, st));
+        break;
+    case CriticPath::Plain:
+        SSN_TRY(ssn::critic_forward(n.params, n.dims, n.nlayers, x, cond, batch, n.hide_cell_type, out, ws, n.bf16, st, n.leak));
+        break;
+    case CriticPath::General:
+        SSN_TRY(ssn::critic_norm_forward(n.params, n.dims, n.flags, n.nlayers, x, cond, batch, n.hide_cell_type, out, ws, n.bf16, st, n.act));
+        break;
+    }
+    return 0;
+}
+// (eps, xp_out: the plain chain builds the penalty points and its three input blocks in ONE launch -- critic_step_impl)
+int critic_net_loss_grad(const CriticNet& n, const float* xg, const float* cg, const float* xd, const float* cd, const float* xp,
+                         const float* cp, int ng, int nd, int np, float lmd, float* grads, float* stats, float* dvals, float* ws,
+                         hipStream_t st, const float* eps = nullptr, float* xp_out = nullptr) {
+    switch (critic_path(n, (long)ng + nd + np, cg && cd && cp)) {
+    case CriticPath::Fused:
+        SSN_TRY(ssn::critic_fused_loss_grad(n.params, n.dims, n.flags, n.nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, n.hide_cell_type,
+                                            grads, stats, dvals, ws, st));
+        break;
+    case CriticPath::Plain:
+        SSN_TRY(ssn::critic_loss_grad(n.params, n.dims, n.nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, n.hide_cell_type, grads,
+                                      stats, dvals, ws, n.bf16, st, n.leak, eps, xp_out));
+        break;
+    case CriticPath::General:
+        SSN_TRY(ssn::critic_norm_loss_grad(n.params, n.dims, n.flags, n.nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd,
+                                           n.hide_cell_type, grads, stats, dvals, ws, n.bf16, st, n.act));
+        break;
+    }
+    return 0;
+}
+int critic_net_input_grad(const CriticNet& n, const float* x, const float* cond, int batch, float scale, float* gx, float* stats,
+                          float* ws, hipStream_t st) {
+    switch (critic_path(n, batch, cond != nullptr)) {
+    case CriticPath::Fused:
+        SSN_TRY(ssn::critic_fused_input_grad(n.params, n.dims, n.flags, n.nlayers, x, cond, batch, n.hide_cell_type, scale, gx, stats, ws, st));
+        break;
+    case CriticPath::Plain:
+        SSN_TRY(ssn::critic_input_grad(n.params, n.dims, n.nlayers, x, cond, batch, n.hide_cell_type, scale, gx, stats, ws, n.bf16, st,
+                                       n.leak));
+        break;
+    case CriticPath::General:
+        SSN_TRY(ssn::critic_norm_input_grad(n.params, n.dims, n.flags, n.nlayers, x, cond, batch, n.hide_cell_type, scale, gx, stats, ws,
+                                            n.bf16, st, n.act));
+        break;
+    }
+    return 0;
+}
+// dvals[0:ng] = D(xg), dvals[ng:ng+nd] = D(xd): what the accuracy mean D(xg) - mean D(xd) is reduced from.
+int critic_net_accuracy_forwards(const CriticNet& n, const float* xg, const float* cg, const float* xd, const float* cd, int ng,
+                                 int nd, float* dvals, float* ws, hipStream_t st, bool inputs_ready = false) {
+    const bool conds = cg && cd;
+    // a critic of fused size keeps one forward per input, on whichever path it takes (every leaky one included: those run
+    // the plain chain twice)
+    const bool fused_size = conds && (fused_ok(n.dims, n.nlayers, ng) || fused_ok(n.dims, n.nlayers, nd));
+    if (!fused_size && critic_path(n, ng, conds) == CriticPath::Plain) {
+        // ONE pass of the plain chain over the stacked rows [xg; xd] (the values of two separate forwards, bit for bit).
+        // inputs_ready: the workspace already starts with the input block of those rows (ssn_host.h)
+        SSN_TRY(ssn::critic_forward2(n.params, n.dims, n.nlayers, xg, cg, ng, xd, cd, nd, n.hide_cell_type, dvals, ws, n.bf16, st,
+                                     n.leak, inputs_ready));
+        return 0;
+    }
+    int rc = ng > 0 ? critic_net_forward(n, xg, cg, ng, dvals, ws, st) : 0;
+    if (!rc && nd > 0) rc = critic_net_forward(n, xd, cd, nd, dvals + ng, ws, st);
+    return rc;
+}
+
 }  // namespace
 
 template <typename T>
@@ -572,92 +680,115 @@ long ssn_critic_num_params(const int* dims, int nlayers) {
     for (int l = 0; l < nlayers; ++l) n += (long)dims[l] * dims[l + 1] + dims[l + 1];
     return n + dims[nlayers];
 }
-// Critics whose layers are all <= 128 wide run through the fused row-block kernels (ssn_critic_fused.hip: 3 launches per
-// update, fp32 arithmetic whatever `precision` says); wider ones through the layer-by-layer MFMA GEMM chain.  The
-// workspace is sized for whichever path the sizes select.
+// The workspace queries cover whichever path the sizes select (critic_path, above).  The _norm one covers every path: a caller
+// of the routed entry points who asks it is safe whatever critic he describes.
 static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
-// SSN_CRITIC_FUSED=0 in the environment keeps small critics on the layer-by-layer path too (A/B timing, tests of that path)
-// Above ~2048 stacked rows the layer-by-layer chain (fixed ~250 us of launch latency, MFMA arithmetic) is as fast as the
-// fused kernels (plain FMAs, time proportional to the rows).
-static bool fused_ok(const int* dims, int nlayers, long rows) {
-    static const bool enabled = [] { const char* v = std::getenv("SSN_CRITIC_FUSED"); return !(v && v[0] == '0'); }();
-    return enabled && rows <= 2048 && ssn::critic_fused_supported(dims, nlayers);
-}
 size_t ssn_critic_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p) {
     const size_t base = ssn::critic_workspace_floats(dims, nlayers, batch_gd, batch_p);
     return ssn::critic_fused_supported(dims, nlayers) ? max_sz(base, ssn::critic_fused_workspace_floats(dims, nlayers, batch_gd, batch_p)) : base;
 }
+size_t ssn_critic_norm_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p) {
+    return max_sz(ssn::critic_norm_workspace_floats(dims, nlayers, batch_gd, batch_p), ssn_critic_workspace_floats(dims, nlayers, batch_gd, batch_p));
+}
+// The critic's passes.  Four families of entry points have accumulated (include/ssnode_mi355x.h); each checks its own arguments,
+// describes its critic as a CriticNet and leaves the rest to critic_net_* above.
+// -- rectify, plain layers
 int ssn_critic_forward(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
                        int hide_cell_type, float* out, float* workspace, int precision, void* stream) {
     if (batch == 0) return 0;
-    if (cond && fused_ok(dims, nlayers, batch)) {
-        SSN_TRY(ssn::critic_fused_forward(params, dims, nullptr, nlayers, x, cond, batch, hide_cell_type, out, workspace, (hipStream_t)stream));
-        return 0;
-    }
-    SSN_TRY(ssn::critic_forward(params, dims, nlayers, x, cond, batch, hide_cell_type, out, workspace, precision == 0,
-                                (hipStream_t)stream));
-    return 0;
+    return critic_net_forward(CriticNet{params, dims, nullptr, nlayers, 0, 0.f, hide_cell_type, precision == 0}, x, cond, batch, out,
+                              workspace, (hipStream_t)stream);
 }
 int ssn_critic_loss_grad(const float* params, const int* dims, int nlayers, const float* xg, const float* cg,
                          const float* xd, const float* cd, const float* xp, const float* cp, int ng, int nd, int np,
                          float lmd, int hide_cell_type, float* grads, float* stats, float* dvals, float* workspace,
                          int precision, void* stream) {
-    if (cg && cd && cp && fused_ok(dims, nlayers, (long)ng + nd + np)) {
-        SSN_TRY(ssn::critic_fused_loss_grad(params, dims, nullptr, nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, hide_cell_type,
-                                            grads, stats, dvals, workspace, (hipStream_t)stream));
-        return 0;
-    }
-    SSN_TRY(ssn::critic_loss_grad(params, dims, nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, hide_cell_type, grads,
-                                  stats, dvals, workspace, precision == 0, (hipStream_t)stream));
-    return 0;
+    return critic_net_loss_grad(CriticNet{params, dims, nullptr, nlayers, 0, 0.f, hide_cell_type, precision == 0}, xg, cg, xd, cd, xp, cp,
+                                ng, nd, np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream);
 }
 int ssn_critic_input_grad(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
                           int hide_cell_type, float scale, float* gx, float* stats, float* workspace, int precision,
                           void* stream) {
     if (batch == 0) return 0;
-    if (cond && fused_ok(dims, nlayers, batch)) {
-        SSN_TRY(ssn::critic_fused_input_grad(params, dims, nullptr, nlayers, x, cond, batch, hide_cell_type, scale, gx, stats,
-                                             workspace, (hipStream_t)stream));
-        return 0;
-    }
-    SSN_TRY(ssn::critic_input_grad(params, dims, nlayers, x, cond, batch, hide_cell_type, scale, gx, stats, workspace,
-                                   precision == 0, (hipStream_t)stream));
-    return 0;
+    return critic_net_input_grad(CriticNet{params, dims, nullptr, nlayers, 0, 0.f, hide_cell_type, precision == 0}, x, cond, batch, scale,
+                                 gx, stats, workspace, (hipStream_t)stream);
 }
-size_t ssn_critic_norm_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p) {
-    const size_t base = ssn::critic_norm_workspace_floats(dims, nlayers, batch_gd, batch_p);
-    return ssn::critic_fused_supported(dims, nlayers) ? max_sz(base, ssn::critic_fused_workspace_floats(dims, nlayers, batch_gd, batch_p)) : base;
-}
-// The same three calls for a hidden nonlinearity x > 0 ? x : leak * x (lasagne's leaky_rectify = 0.01, very_leaky_rectify = 1/3,
-// linear = 1; plain layers only).  Always the layer-by-layer path.
+// -- a hidden nonlinearity x > 0 ? x : leak * x (lasagne's leaky_rectify = 0.01, very_leaky_rectify = 1/3, linear = 1), plain layers
 int ssn_critic_forward_leaky(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
                              int hide_cell_type, float leak, float* out, float* workspace, int precision, void* stream) {
     if (batch == 0) return 0;
-    SSN_TRY(ssn::critic_forward(params, dims, nlayers, x, cond, batch, hide_cell_type, out, workspace, precision == 0,
-                                (hipStream_t)stream, leak));
-    return 0;
+    return critic_net_forward(CriticNet{params, dims, nullptr, nlayers, 0, leak, hide_cell_type, precision == 0}, x, cond, batch, out,
+                              workspace, (hipStream_t)stream);
 }
 int ssn_critic_loss_grad_leaky(const float* params, const int* dims, int nlayers, const float* xg, const float* cg,
                                const float* xd, const float* cd, const float* xp, const float* cp, int ng, int nd, int np,
                                float lmd, int hide_cell_type, float leak, float* grads, float* stats, float* dvals,
                                float* workspace, int precision, void* stream) {
-    SSN_TRY(ssn::critic_loss_grad(params, dims, nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, hide_cell_type, grads,
-                                  stats, dvals, workspace, precision == 0, (hipStream_t)stream, leak));
-    return 0;
+    return critic_net_loss_grad(CriticNet{params, dims, nullptr, nlayers, 0, leak, hide_cell_type, precision == 0}, xg, cg, xd, cd, xp, cp,
+                                ng, nd, np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream);
 }
 int ssn_critic_input_grad_leaky(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
                                 int hide_cell_type, float leak, float scale, float* gx, float* stats, float* workspace,
                                 int precision, void* stream) {
     if (batch == 0) return 0;
-    SSN_TRY(ssn::critic_input_grad(params, dims, nlayers, x, cond, batch, hide_cell_type, scale, gx, stats, workspace,
-                                   precision == 0, (hipStream_t)stream, leak));
+    return critic_net_input_grad(CriticNet{params, dims, nullptr, nlayers, 0, leak, hide_cell_type, precision == 0}, x, cond, batch, scale,
+                                 gx, stats, workspace, (hipStream_t)stream);
+}
+// -- rectify, per-layer normalisation flags 0 / 1
+static bool norm_flags_plain(const int* layer_norm, int nlayers) {
+    for (int l = 0; layer_norm && l < nlayers; ++l) if (layer_norm[l] != 0 && layer_norm[l] != 1) return false;
+    return true;
+}
+static bool any_norm(const int* layer_norm, int nlayers) {
+    for (int l = 0; layer_norm && l < nlayers; ++l) if (layer_norm[l] != 0) return true;
+    return false;
+}
+int ssn_critic_forward_norm(const float* params, const int* dims, const int* layer_norm, int nlayers, const float* x,
+                            const float* cond, int batch, int hide_cell_type, float* out, float* workspace, int precision,
+                            void* stream) {
+    if (!norm_flags_plain(layer_norm, nlayers)) { g_last_error = "ssn_critic_forward_norm: layer_norm flags are 0 / 1 (scaled layers: ssn_critic_forward_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    if (batch == 0) return 0;
+    return critic_net_forward(CriticNet{params, dims, layer_norm, nlayers, 0, 0.f, hide_cell_type, precision == 0}, x, cond, batch, out,
+                              workspace, (hipStream_t)stream);
+}
+int ssn_critic_loss_grad_norm(const float* params, const int* dims, const int* layer_norm, int nlayers, const float* xg,
+                              const float* cg, const float* xd, const float* cd, const float* xp, const float* cp, int ng,
+                              int nd, int np, float lmd, int hide_cell_type, float* grads, float* stats, float* dvals,
+                              float* workspace, int precision, void* stream) {
+    if (!norm_flags_plain(layer_norm, nlayers)) { g_last_error = "ssn_critic_loss_grad_norm: layer_norm flags are 0 / 1 (scaled layers: ssn_critic_loss_grad_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    return critic_net_loss_grad(CriticNet{params, dims, layer_norm, nlayers, 0, 0.f, hide_cell_type, precision == 0}, xg, cg, xd, cd, xp,
+                                cp, ng, nd, np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream);
+}
+int ssn_critic_input_grad_norm(const float* params, const int* dims, const int* layer_norm, int nlayers, const float* x,
+                               const float* cond, int batch, int hide_cell_type, float scale, float* gx, float* stats,
+                               float* workspace, int precision, void* stream) {
+    if (!norm_flags_plain(layer_norm, nlayers)) { g_last_error = "ssn_critic_input_grad_norm: layer_norm flags are 0 / 1 (scaled layers: ssn_critic_input_grad_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    if (batch == 0) return 0;
+    return critic_net_input_grad(CriticNet{params, dims, layer_norm, nlayers, 0, 0.f, hide_cell_type, precision == 0}, x, cond, batch,
+                                 scale, gx, stats, workspace, (hipStream_t)stream);
+}
+// mean D(xg) - mean D(xd) in one call (the critic's values of both inputs into `dvals`, one reduction in a fixed order):
+// layer_norm NULL or all zero = plain layers, leak as in the _leaky entry points (plain layers only).
+int ssn_critic_accuracy(const float* params, const int* dims, const int* layer_norm, int nlayers, float leak, const float* xg,
+                        const float* cg, const float* xd, const float* cd, int ng, int nd, int hide_cell_type, float* acc,
+                        float* dvals, float* workspace, int precision, void* stream) {
+    if (!norm_flags_plain(layer_norm, nlayers)) { g_last_error = "ssn_critic_forward_norm: layer_norm flags are 0 / 1 (scaled layers: ssn_critic_forward_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    // (a slope next to a normalisation is a critic in its general form; this call used to drop the slope without a word)
+    if (leak != 0.f && any_norm(layer_norm, nlayers)) { g_last_error = "ssn_critic_accuracy: leak with layer-normalised layers (that critic: ssn_critic_accuracy_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    if (int rc = critic_net_accuracy_forwards(CriticNet{params, dims, layer_norm, nlayers, 0, leak, hide_cell_type, precision == 0}, xg, cg,
+                                              xd, cd, ng, nd, dvals, workspace, (hipStream_t)stream)) return rc;
+    SSN_TRY(ssn::launch_mean_diff(dvals, ng, nd, acc, (hipStream_t)stream));
     return 0;
 }
-// ---- the general layer-by-layer critic: any lasagne nonlinearity, learnable scale after a layer normalisation ----------------
+// -- any critic: activation code, per-layer flags 0 / 1 / 3
 static bool act_flags_ok(const int* flags, int nlayers, int act) {
     if (act < 0 || act > 7 || nlayers < 0 || nlayers > 8) return false;
     for (int l = 0; flags && l < nlayers; ++l) if (flags[l] != 0 && flags[l] != 1 && flags[l] != 3) return false;
     return true;
+}
+static CriticNet act_net(const float* params, const int* dims, const int* layer_flags, int nlayers, int act, int hide_cell_type,
+                         int precision) {
+    return CriticNet{params, dims, layer_flags, nlayers, act, act_leak(act), hide_cell_type, precision == 0};
 }
 long ssn_critic_num_params_act(const int* dims, const int* layer_flags, int nlayers) {
     if (!dims || !act_flags_ok(layer_flags, nlayers, 0)) return -1;
@@ -668,130 +799,33 @@ int ssn_critic_forward_act(const float* params, const int* dims, const int* laye
                            void* stream) {
     if (!act_flags_ok(layer_flags, nlayers, act)) { g_last_error = "ssn_critic_forward_act: invalid layer flags / activation"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
     if (batch == 0) return 0;
-    SSN_TRY(ssn::critic_norm_forward(params, dims, layer_flags, nlayers, x, cond, batch, hide_cell_type, out, workspace,
-                                     precision == 0, (hipStream_t)stream, act));
-    return 0;
+    return critic_net_forward(act_net(params, dims, layer_flags, nlayers, act, hide_cell_type, precision), x, cond, batch, out, workspace,
+                              (hipStream_t)stream);
 }
 int ssn_critic_loss_grad_act(const float* params, const int* dims, const int* layer_flags, int nlayers, int act, const float* xg,
                              const float* cg, const float* xd, const float* cd, const float* xp, const float* cp, int ng,
                              int nd, int np, float lmd, int hide_cell_type, float* grads, float* stats, float* dvals,
                              float* workspace, int precision, void* stream) {
     if (!act_flags_ok(layer_flags, nlayers, act)) { g_last_error = "ssn_critic_loss_grad_act: invalid layer flags / activation"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    SSN_TRY(ssn::critic_norm_loss_grad(params, dims, layer_flags, nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd,
-                                       hide_cell_type, grads, stats, dvals, workspace, precision == 0, (hipStream_t)stream, act));
-    return 0;
+    return critic_net_loss_grad(act_net(params, dims, layer_flags, nlayers, act, hide_cell_type, precision), xg, cg, xd, cd, xp, cp, ng, nd,
+                                np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream);
 }
 int ssn_critic_input_grad_act(const float* params, const int* dims, const int* layer_flags, int nlayers, int act, const float* x,
                               const float* cond, int batch, int hide_cell_type, float scale, float* gx, float* stats,
                               float* workspace, int precision, void* stream) {
     if (!act_flags_ok(layer_flags, nlayers, act)) { g_last_error = "ssn_critic_input_grad_act: invalid layer flags / activation"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
     if (batch == 0) return 0;
-    SSN_TRY(ssn::critic_norm_input_grad(params, dims, layer_flags, nlayers, x, cond, batch, hide_cell_type, scale, gx, stats,
-                                        workspace, precision == 0, (hipStream_t)stream, act));
-    return 0;
+    return critic_net_input_grad(act_net(params, dims, layer_flags, nlayers, act, hide_cell_type, precision), x, cond, batch, scale, gx,
+                                 stats, workspace, (hipStream_t)stream);
 }
 int ssn_critic_accuracy_act(const float* params, const int* dims, const int* layer_flags, int nlayers, int act, const float* xg,
                             const float* cg, const float* xd, const float* cd, int ng, int nd, int hide_cell_type, float* acc,
                             float* dvals, float* workspace, int precision, void* stream) {
-    if (int rc = ssn_critic_forward_act(params, dims, layer_flags, nlayers, act, xg, cg, ng, hide_cell_type, dvals, workspace, precision, stream)) return rc;
-    if (int rc = ssn_critic_forward_act(params, dims, layer_flags, nlayers, act, xd, cd, nd, hide_cell_type, dvals + ng, workspace, precision, stream)) return rc;
+    if (!act_flags_ok(layer_flags, nlayers, act)) { g_last_error = "ssn_critic_forward_act: invalid layer flags / activation"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    if (int rc = critic_net_accuracy_forwards(act_net(params, dims, layer_flags, nlayers, act, hide_cell_type, precision), xg, cg, xd, cd,
+                                              ng, nd, dvals, workspace, (hipStream_t)stream)) return rc;
     SSN_TRY(ssn::launch_mean_diff(dvals, ng, nd, acc, (hipStream_t)stream));
     return 0;
-}
-static bool norm_flags_plain(const int* layer_norm, int nlayers) {
-    for (int l = 0; layer_norm && l < nlayers; ++l) if (layer_norm[l] != 0 && layer_norm[l] != 1) return false;
-    return true;
-}
-int ssn_critic_forward_norm(const float* params, const int* dims, const int* layer_norm, int nlayers, const float* x,
-                            const float* cond, int batch, int hide_cell_type, float* out, float* workspace, int precision,
-                            void* stream) {
-    if (!norm_flags_plain(layer_norm, nlayers)) { g_last_error = "ssn_critic_forward_norm: layer_norm flags are 0 / 1 (scaled layers: ssn_critic_forward_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    if (batch == 0) return 0;
-    if (cond && fused_ok(dims, nlayers, batch)) {
-        SSN_TRY(ssn::critic_fused_forward(params, dims, layer_norm, nlayers, x, cond, batch, hide_cell_type, out, workspace, (hipStream_t)stream));
-        return 0;
-    }
-    SSN_TRY(ssn::critic_norm_forward(params, dims, layer_norm, nlayers, x, cond, batch, hide_cell_type, out, workspace,
-                                     precision == 0, (hipStream_t)stream));
-    return 0;
-}
-int ssn_critic_loss_grad_norm(const float* params, const int* dims, const int* layer_norm, int nlayers, const float* xg,
-                              const float* cg, const float* xd, const float* cd, const float* xp, const float* cp, int ng,
-                              int nd, int np, float lmd, int hide_cell_type, float* grads, float* stats, float* dvals,
-                              float* workspace, int precision, void* stream) {
-    if (!norm_flags_plain(layer_norm, nlayers)) { g_last_error = "ssn_critic_loss_grad_norm: layer_norm flags are 0 / 1 (scaled layers: ssn_critic_loss_grad_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    if (cg && cd && cp && fused_ok(dims, nlayers, (long)ng + nd + np)) {
-        SSN_TRY(ssn::critic_fused_loss_grad(params, dims, layer_norm, nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, hide_cell_type,
-                                            grads, stats, dvals, workspace, (hipStream_t)stream));
-        return 0;
-    }
-    SSN_TRY(ssn::critic_norm_loss_grad(params, dims, layer_norm, nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd,
-                                       hide_cell_type, grads, stats, dvals, workspace, precision == 0, (hipStream_t)stream));
-    return 0;
-}
-int ssn_critic_input_grad_norm(const float* params, const int* dims, const int* layer_norm, int nlayers, const float* x,
-                               const float* cond, int batch, int hide_cell_type, float scale, float* gx, float* stats,
-                               float* workspace, int precision, void* stream) {
-    if (!norm_flags_plain(layer_norm, nlayers)) { g_last_error = "ssn_critic_input_grad_norm: layer_norm flags are 0 / 1 (scaled layers: ssn_critic_input_grad_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    if (batch == 0) return 0;
-    if (cond && fused_ok(dims, nlayers, batch)) {
-        SSN_TRY(ssn::critic_fused_input_grad(params, dims, layer_norm, nlayers, x, cond, batch, hide_cell_type, scale, gx, stats,
-                                             workspace, (hipStream_t)stream));
-        return 0;
-    }
-    SSN_TRY(ssn::critic_norm_input_grad(params, dims, layer_norm, nlayers, x, cond, batch, hide_cell_type, scale, gx, stats,
-                                        workspace, precision == 0, (hipStream_t)stream));
-    return 0;
-}
-// mean D(xg) - mean D(xd) in one call (two critic forwards into `dvals`, one reduction in a fixed order): layer_norm NULL or all
-// zero = plain layers, leak as in the _leaky entry points.
-static int critic_accuracy_forwards(const float* params, const int* dims, const int* layer_norm, int nlayers, float leak, const float* xg,
-                                    const float* cg, const float* xd, const float* cd, int ng, int nd, int hide_cell_type,
-                                    float* dvals, float* workspace, int precision, void* stream, bool inputs_ready = false);
-int ssn_critic_accuracy(const float* params, const int* dims, const int* layer_norm, int nlayers, float leak, const float* xg,
-                        const float* cg, const float* xd, const float* cd, int ng, int nd, int hide_cell_type, float* acc,
-                        float* dvals, float* workspace, int precision, void* stream) {
-    if (int rc = critic_accuracy_forwards(params, dims, layer_norm, nlayers, leak, xg, cg, xd, cd, ng, nd, hide_cell_type, dvals,
-                                          workspace, precision, stream)) return rc;
-    SSN_TRY(ssn::launch_mean_diff(dvals, ng, nd, acc, (hipStream_t)stream));
-    return 0;
-}
-static int critic_accuracy_forwards(const float* params, const int* dims, const int* layer_norm, int nlayers, float leak, const float* xg,
-                                    const float* cg, const float* xd, const float* cd, int ng, int nd, int hide_cell_type,
-                                    float* dvals, float* workspace, int precision, void* stream, bool inputs_ready) {
-    bool norm = false;
-    for (int l = 0; layer_norm && l < nlayers; ++l) norm = norm || layer_norm[l] != 0;
-    if (!norm && !(cg && cd && (fused_ok(dims, nlayers, ng) || fused_ok(dims, nlayers, nd)))) {
-        // plain layers on the layer-by-layer path: ONE pass over the stacked rows [xg; xd] (the values of two separate
-        // forwards, bit for bit; narrow critics keep their single-launch forwards)
-        SSN_TRY(ssn::critic_forward2(params, dims, nlayers, xg, cg, ng, xd, cd, nd, hide_cell_type, dvals, workspace, precision == 0,
-                                     (hipStream_t)stream, leak, inputs_ready));
-        return 0;
-    }
-    const struct { const float* x; const float* c; int n; float* out; } part[2] = {{xg, cg, ng, dvals}, {xd, cd, nd, dvals + ng}};
-    for (int i = 0; i < 2; ++i) {
-        int rc;
-        if (norm) rc = ssn_critic_forward_norm(params, dims, layer_norm, nlayers, part[i].x, part[i].c, part[i].n, hide_cell_type,
-                                               part[i].out, workspace, precision, stream);
-        else if (leak != 0.f) rc = ssn_critic_forward_leaky(params, dims, nlayers, part[i].x, part[i].c, part[i].n, hide_cell_type,
-                                                            leak, part[i].out, workspace, precision, stream);
-        else rc = ssn_critic_forward(params, dims, nlayers, part[i].x, part[i].c, part[i].n, hide_cell_type, part[i].out,
-                                     workspace, precision, stream);
-        if (rc) return rc;
-    }
-    return 0;
-}
-static int optimizer_step_full(float* p, const float* g, float* s1, float* s2, long n, const ssn_opt_params* o, const double* gate,
-                               double gate_bound, const float* clip_lo_v, const float* clip_hi_v, float* record, const float* record_tail,
-                               void* stream);
-static int optimizer_step_gated(float* p, const float* g, float* s1, float* s2, long n, const ssn_opt_params* o, const double* gate,
-                                double gate_bound, void* stream);
-int ssn_optimizer_step(float* p, const float* g, float* s1, float* s2, long n, const ssn_opt_params* o, void* stream) {
-    return optimizer_step_gated(p, g, s1, s2, n, o, nullptr, 0.0, stream);
-}
-static int optimizer_step_gated(float* p, const float* g, float* s1, float* s2, long n, const ssn_opt_params* o, const double* gate,
-                                double gate_bound, void* stream) {
-    return optimizer_step_full(p, g, s1, s2, n, o, gate, gate_bound, nullptr, nullptr, nullptr, nullptr, stream);
 }
 static int optimizer_step_full(float* p, const float* g, float* s1, float* s2, long n, const ssn_opt_params* o, const double* gate,
                                double gate_bound, const float* clip_lo_v, const float* clip_hi_v, float* record, const float* record_tail,
@@ -814,6 +848,13 @@ static int optimizer_step_full(float* p, const float* g, float* s1, float* s2, l
     a.skip_nonfinite = (o->reserved & 1) && n <= 64 && record;        // ssn_opt_params.reserved bit 0 (ssn_gen_apply_f32)
     SSN_TRY(ssn::optimizer_step(a, (hipStream_t)stream));
     return 0;
+}
+static int optimizer_step_gated(float* p, const float* g, float* s1, float* s2, long n, const ssn_opt_params* o, const double* gate,
+                                double gate_bound, void* stream) {
+    return optimizer_step_full(p, g, s1, s2, n, o, gate, gate_bound, nullptr, nullptr, nullptr, nullptr, stream);
+}
+int ssn_optimizer_step(float* p, const float* g, float* s1, float* s2, long n, const ssn_opt_params* o, void* stream) {
+    return optimizer_step_gated(p, g, s1, s2, n, o, nullptr, 0.0, stream);
 }
 
 long ssn_gen_grads_ws_doubles(void) { return 2 * 128 + 1; }
@@ -838,7 +879,37 @@ int ssn_gen_apply_f32(float* params, const float* grads, float* s1, float* s2, i
     }
     return optimizer_step_full(params, grads, s1, s2, n, opt, nullptr, 0.0, clip_lo, clip_hi, record, record ? grads + n : nullptr, stream);
 }
-static int critic_step_impl(const ssn_critic_step* a, const double* gate, double gate_bound, void* stream);
+static int critic_step_impl(const ssn_critic_step* a, const double* gate, double gate_bound, void* stream) {
+    if (!a || !a->params || !a->dims || !a->xg || !a->xd || !a->eps || !a->xp || !a->grads || !a->stats || !a->dvals ||
+        !a->workspace || !a->opt || !a->acc_dvals || !a->tail || a->n <= 0 || a->nlayers < 0 || a->nseg < 0 ||
+        !norm_flags_plain(a->layer_norm, a->nlayers) || (a->leak != 0.f && any_norm(a->layer_norm, a->nlayers))) {
+        g_last_error = "ssn_critic_step_run: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    const CriticNet net{a->params, a->dims, a->layer_norm, a->nlayers, 0, a->leak, a->hide_cell_type, a->precision == 0};
+    const hipStream_t st = (hipStream_t)stream;
+    const int n = a->n, nx = a->dims[0] - (a->cond ? 3 : 0);        // cond NULL: the unconditional critic (dims[0] = nx)
+    int rc;
+    // the plain chain with the one condition array of the loop: the penalty points and the three input blocks come from ONE
+    // launch inside the loss pass (the bits of ssn_interpolate_f32 + the input kernels).  Not for a critic of fused size, a
+    // leaky one included.
+    const bool one_launch_inputs = critic_path(net, 3L * n, a->cond != nullptr) == CriticPath::Plain && a->cond &&
+                                   !fused_ok(a->dims, a->nlayers, 3L * n);
+    if (!one_launch_inputs && (rc = ssn_interpolate_f32(a->eps, a->xd, a->xg, a->xp, n, nx, stream))) return rc;
+    if ((rc = critic_net_loss_grad(net, a->xg, a->cond, a->xd, a->cond, a->xp, a->cond, n, n, n, a->lmd, a->grads, a->stats, a->dvals,
+                                   a->workspace, st, one_launch_inputs ? a->eps : nullptr, one_launch_inputs ? a->xp : nullptr))) return rc;
+    const long nparams = ssn_critic_num_params(a->dims, a->nlayers);
+    if ((rc = optimizer_step_gated(a->params, a->grads, a->opt_s1, a->opt_s2, nparams, a->opt, gate, gate_bound, stream))) return rc;
+    // (the loss pass of the one-launch-inputs form left the input block of [xg; xd] at the head of the workspace, where the
+    // stacked forward of the accuracy builds it: same rows, same conditions -- not built again)
+    if ((rc = critic_net_accuracy_forwards(net, a->xg, a->cond, a->xd, a->cond, n, n, a->acc_dvals, a->workspace, st, one_launch_inputs)))
+        return rc;
+    if (a->nseg > 0 && (!a->seg_bounds || !a->seg_ws)) { g_last_error = "ssn_critic_step_run: invalid argument"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    // accuracy, sums of squares and the head of the record: the chunk sums, then ONE finishing launch (same bits as
+    // ssn_critic_accuracy + ssn_segment_sqnorms2_f32 + the head kernel)
+    SSN_TRY(ssn::launch_step_finish(a->params, a->seg_bounds, a->nseg, a->seg_ws, a->acc_dvals, n, n, a->pens64, a->stats, a->tail, st));
+    return 0;
+}
 int ssn_critic_step_run(const ssn_critic_step* a, void* stream) { return critic_step_impl(a, nullptr, 0.0, stream); }
 int ssn_critic_step_gated_run(const ssn_critic_step* a, double rate_penalty_bound, void* stream) {
     if (!a || !a->pens64 || !(rate_penalty_bound > 0.0)) {
@@ -846,47 +917,6 @@ int ssn_critic_step_gated_run(const ssn_critic_step* a, double rate_penalty_boun
         return SSN_ERR_BASE + (int)hipErrorInvalidValue;
     }
     return critic_step_impl(a, a->pens64 + 1, rate_penalty_bound, stream);
-}
-static int critic_step_impl(const ssn_critic_step* a, const double* gate, double gate_bound, void* stream) {
-    if (!a || !a->params || !a->dims || !a->xg || !a->xd || !a->eps || !a->xp || !a->grads || !a->stats || !a->dvals ||
-        !a->workspace || !a->opt || !a->acc_dvals || !a->tail || a->n <= 0 || a->nlayers < 0 || a->nseg < 0) {
-        g_last_error = "ssn_critic_step_run: invalid argument";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    bool norm = false;
-    for (int l = 0; a->layer_norm && l < a->nlayers; ++l) norm = norm || a->layer_norm[l] != 0;
-    const int n = a->n, nx = a->dims[0] - (a->cond ? 3 : 0);        // cond NULL: the unconditional critic (dims[0] = nx)
-    int rc;
-    // plain layers on the layer-by-layer path with the one condition array of the loop: the penalty points and the three input
-    // blocks come from ONE launch inside the loss pass (the bits of ssn_interpolate_f32 + the input kernels)
-    const bool one_launch_inputs = !norm && a->cond && !fused_ok(a->dims, a->nlayers, 3L * n);
-    if (!one_launch_inputs && (rc = ssn_interpolate_f32(a->eps, a->xd, a->xg, a->xp, n, nx, stream))) return rc;
-    if (norm) rc = ssn_critic_loss_grad_norm(a->params, a->dims, a->layer_norm, a->nlayers, a->xg, a->cond, a->xd, a->cond, a->xp, a->cond,
-                                             n, n, n, a->lmd, a->hide_cell_type, a->grads, a->stats, a->dvals, a->workspace, a->precision, stream);
-    else if (one_launch_inputs) {
-        SSN_TRY(ssn::critic_loss_grad(a->params, a->dims, a->nlayers, a->xg, a->cond, a->xd, a->cond, a->xp, a->cond, n, n, n, a->lmd,
-                                      a->hide_cell_type, a->grads, a->stats, a->dvals, a->workspace, a->precision == 0,
-                                      (hipStream_t)stream, a->leak, a->eps, a->xp));
-        rc = 0;
-    }
-    else if (a->leak != 0.f) rc = ssn_critic_loss_grad_leaky(a->params, a->dims, a->nlayers, a->xg, a->cond, a->xd, a->cond, a->xp, a->cond,
-                                                             n, n, n, a->lmd, a->hide_cell_type, a->leak, a->grads, a->stats, a->dvals,
-                                                             a->workspace, a->precision, stream);
-    else rc = ssn_critic_loss_grad(a->params, a->dims, a->nlayers, a->xg, a->cond, a->xd, a->cond, a->xp, a->cond, n, n, n, a->lmd,
-                                   a->hide_cell_type, a->grads, a->stats, a->dvals, a->workspace, a->precision, stream);
-    if (rc) return rc;
-    const long nparams = ssn_critic_num_params(a->dims, a->nlayers);
-    if ((rc = optimizer_step_gated(a->params, a->grads, a->opt_s1, a->opt_s2, nparams, a->opt, gate, gate_bound, stream))) return rc;
-    // (the loss pass of the one-launch-inputs form left the input block of [xg; xd] at the head of the workspace, where the
-    // stacked forward of the accuracy builds it: same rows, same conditions -- not built again)
-    if ((rc = critic_accuracy_forwards(a->params, a->dims, a->layer_norm, a->nlayers, a->leak, a->xg, a->cond, a->xd, a->cond, n, n,
-                                       a->hide_cell_type, a->acc_dvals, a->workspace, a->precision, stream, one_launch_inputs))) return rc;
-    if (a->nseg > 0 && (!a->seg_bounds || !a->seg_ws)) { g_last_error = "ssn_critic_step_run: invalid argument"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    // accuracy, sums of squares and the head of the record: the chunk sums, then ONE finishing launch (same bits as
-    // ssn_critic_accuracy + ssn_segment_sqnorms2_f32 + the head kernel)
-    SSN_TRY(ssn::launch_step_finish(a->params, a->seg_bounds, a->nseg, a->seg_ws, a->acc_dvals, n, n, a->pens64, a->stats, a->tail,
-                                    (hipStream_t)stream));
-    return 0;
 }
 
 static ssn::FFArgs ff_args(const ssn_ff_params& p) {

@@ -223,6 +223,64 @@ def test_one_call_critic_step_equals_the_separate_calls(layers, norm, nonlin, pr
         assert all(torch.equal(x, y) for x, y in zip(ua._state, ub._state))
 
 
+def test_legacy_entry_points_equal_the_routed_ones():
+    """`Critic` makes every pass through the `ssn_critic_*_act` family, which picks the kernels for the critic it is given.  The
+    three older families (plain rectify; `_leaky`; `_norm`) and `ssn_critic_accuracy` describe a subset of those critics and go
+    through the same choice: called directly, they give the bits of the `Critic` methods -- D values, gradients, stats, input
+    gradient, accuracy."""
+    from tc_gan_amd import clib
+    from tc_gan_amd.critic import Critic
+    lib, st = clib.libssnode, clib.stream_ptr
+    rs = np.random.RandomState(11)
+    n, nx = 96, 8
+    for layers, norm, nonlin in [([64, 64], 'none', 'rectify'), ([64, 64], 'none', 'very_leaky_rectify'),
+                                 ([32, 32, 32], ['none', 'layer', 'layer'], 'rectify')]:
+        c = Critic(nx, layers, seed=5, precision='fp32', normalization=norm, nonlinearity=nonlin)
+        assert not c.general
+        xg, xd, xp = (torch.as_tensor(rs.rand(n, nx) * 5, device='cuda', dtype=torch.float32) for _ in range(3))
+        cond = torch.as_tensor(np.stack([np.full(n, 20.), rs.rand(n) * 2 - 1, rs.randint(0, 2, n)], axis=1), device='cuda',
+                               dtype=torch.float32)
+        d = c.forward(xg, cond).clone()
+        stats = c.loss_grad(xg, cond, xd, cond, xp, cond, 10.0).clone()
+        grads, dvals = c.grads.clone(), c._dvals.clone()
+        gx, mean_d = c.input_grad(xg, cond, -1.0 / n)
+        gx, mean_d = gx.clone(), mean_d.clone()
+        acc = c.accuracy_device(xg, cond, xd, cond).clone()
+
+        # the family's own arguments, between `nlayers` and the inputs / after `hide_cell_type` (include/ssnode_mi355x.h)
+        if c.layer_norm:
+            suffix, head, leak = '_norm', (c.params.data_ptr(), c._dims_c, c._norm_c, c.nlayers), ()
+        elif c.leak:
+            suffix, head, leak = '_leaky', (c.params.data_ptr(), c._dims_c, c.nlayers), (c.leak,)
+        else:
+            suffix, head, leak = '', (c.params.data_ptr(), c._dims_c, c.nlayers), ()
+        new = lambda *shape: torch.full(shape, float('nan'), device='cuda', dtype=torch.float32)
+        d2, grads2, stats2, dvals2, gx2, st_ig, acc2, accd = new(n), new(c.num_params), new(4), new(2 * n), new(n, nx), new(4), new(1), new(2 * n)
+        ws = c._workspace(n, 0)
+        clib.check(getattr(lib, 'ssn_critic_forward' + suffix)(
+            *head, xg.data_ptr(), cond.data_ptr(), n, c.hide_cell_type, *leak, d2.data_ptr(), ws.data_ptr(), c.precision, st()),
+            'forward' + suffix)
+        ws = c._workspace(2 * n, n)
+        clib.check(getattr(lib, 'ssn_critic_loss_grad' + suffix)(
+            *head, xg.data_ptr(), cond.data_ptr(), xd.data_ptr(), cond.data_ptr(), xp.data_ptr(), cond.data_ptr(), n, n, n, 10.0,
+            c.hide_cell_type, *leak, grads2.data_ptr(), stats2.data_ptr(), dvals2.data_ptr(), ws.data_ptr(), c.precision, st()),
+            'loss_grad' + suffix)
+        ws = c._workspace(n, n)
+        clib.check(getattr(lib, 'ssn_critic_input_grad' + suffix)(
+            *head, xg.data_ptr(), cond.data_ptr(), n, c.hide_cell_type, *leak, -1.0 / n, gx2.data_ptr(), st_ig.data_ptr(),
+            ws.data_ptr(), c.precision, st()), 'input_grad' + suffix)
+        ws = c._workspace(n, 0)
+        clib.check(lib.ssn_critic_accuracy(
+            c.params.data_ptr(), c._dims_c, c._norm_c if c.layer_norm else None, c.nlayers, float(c.leak), xg.data_ptr(),
+            cond.data_ptr(), xd.data_ptr(), cond.data_ptr(), n, n, c.hide_cell_type, acc2.data_ptr(), accd.data_ptr(), ws.data_ptr(),
+            c.precision, st()), 'ssn_critic_accuracy')
+        case = (layers, norm, nonlin)
+        assert torch.equal(d2, d), case
+        assert torch.equal(grads2, grads) and torch.equal(stats2, stats) and torch.equal(dvals2, dvals), case
+        assert torch.equal(gx2, gx) and torch.equal(st_ig[0], mean_d), case
+        assert torch.equal(acc2, acc), case
+
+
 def test_critic_bf16_path_close_to_fp64():
     from tc_gan_amd.critic import Critic
     c, params_o, xg, xd, xp, cond = _setup(512, 8, [256, 256], seed=3)
