@@ -756,6 +756,37 @@ int ssn_tc_features_f32(const float *tc, float *feat, long rows, int NC, int NB,
 int ssn_ks_columns_f32(const float *x, const float *truth_sorted, const int *m, int S, int B, int C, int T, int *n,
                        long long *num, void *stream);
 
+/* ---- Rejection sampling of fixed points on the device (ssnode.sample_tuning_curves_table; csrc/ssn_fpsample.hip) ----
+ * A parameter sets see the same stream of candidate draws; every (set, candidate) pair is solved for NB stimuli by
+ * ssn_solve_batch_* (the A R pairs as its batch, set-major), and the first NZ candidates of a set, in stream order, whose solves
+ * all succeed are kept: the rule of ssnode.find_fixed_points, with the states staying on the device.
+ * ssn_build_w_table_f64: ssn_build_w_table_f32 in fp64 (jds_table: DEVICE double[S][12]): the bits of ssn_build_w_f64 per set.
+ * ssn_fp_select_f64 / _f32: one round of R candidates for A sets, two launches on `stream`.
+ *   codes: device [A][R][NB] and x: device [A][R][NB][M], as the solver left them.  A (candidate, stimulus) pair fails with its
+ *   code, and with code 1 where the code is 0 but one of its M values is not finite.  verdict[a][b] (device int[A][R], a
+ *   workspace that is left filled) = 0 where no stimulus fails, else the failure code of the failing stimulus with the LARGEST
+ *   index (the first one in reversed stimulus order).
+ *   set_of: device int[A], the row of the arrays below that set a of this round owns (rows are distinct); cand0: the stream
+ *   index of the round's first candidate; probes: device int[nprobe], the neurons whose rates are kept.  Per row, updated in
+ *   place (the caller zeroes accepted / used / rejections, fills draw_index with -1 and out with NaN before the first round):
+ *     out [.][NZ][NB nprobe]   row accepted' = accepted + rank of every newly accepted candidate: x[a][b][s][probes[p]] in
+ *                              column s nprobe + p;
+ *     accepted [.]             rows filled so far (at most NZ; a row that has NZ is left alone by later rounds);
+ *     used [.]                 cand0 + R while the row is short, the stream index of its NZ-th success plus one once reached;
+ *     rejections [.][2]        candidates with verdict 1 and 2 in front of the NZ-th success (other codes are not counted:
+ *                              with the solver's codes, accepted + rejections[0] + rejections[1] == used);
+ *     draw_index [.][NZ]       stream index of every accepted row.
+ *   R <= ssn_fp_select_max_candidates() (one workgroup per set keeps the round's accepted indices in LDS); more, NZ < 1, odd M
+ *   or a null pointer is refused.  A == 0 or R == 0 is success. */
+int ssn_build_w_table_f64(const double *z, const double *jds_table, double *W, int S, int B, int N, void *stream);
+int ssn_fp_select_max_candidates(void);
+int ssn_fp_select_f64(const int *codes, const double *x, int A, int R, int NB, int M, const int *probes, int nprobe,
+                      const int *set_of, int cand0, int NZ, int *verdict, double *out, int *accepted, int *used, int *rejections,
+                      int *draw_index, void *stream);
+int ssn_fp_select_f32(const int *codes, const float *x, int A, int R, int NB, int M, const int *probes, int nprobe,
+                      const int *set_of, int cand0, int NZ, int *verdict, float *out, int *accepted, int *used, int *rejections,
+                      int *draw_index, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

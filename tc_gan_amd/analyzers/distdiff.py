@@ -21,8 +21,18 @@ generated and the truth column, ``KSD = num / (n m)`` -- exactly ``scipy.stats.k
 There is no p-value here: scipy's default for these sample sizes is its exact method, host arithmetic on (KSD, n, m), and the
 table carries all three for whoever wants it.  (Nothing here imports scipy.)
 
+``dynamics='fixed-point'`` (``--dynamics fixed-point``) scores with the reference's own definition instead, for runs whose truth
+is a sample of fixed points (``--dataset-provider ssnode``, the default): the curves of a checkpoint are those of the first
+`draws` candidate draws, in stream order, whose fixed points converge for every stimulus
+(`ssnode.sample_tuning_curves_table`: the draws, W, the solves, the rejection step and the gather of the probed rates all stay
+on the device), with the truth's solver options.  A checkpoint that rejects draws is short of rows -- its ``n`` is the accepted
+count -- and the counts of rejected draws per error code are part of the result (``rejections.csv``): the rejection rate is
+the diagnostic for a generator that has left the stable regime.
+
     ./run tc_gan.analyzers.distdiff -- RUNDIR [--steps ::10] [--draws 30] [--seed 0] [--gen-kernel K]
                                        [--max-draws-per-launch D] [--output DIR] [--save-tuning-curves]
+                                       [--dynamics {fixed-time,fixed-point}] [--max-candidates N]
+                                       [--solver-dtype {float64,float32}]
 """
 import ctypes
 import json
@@ -32,12 +42,21 @@ import numpy as np
 
 from .. import clib
 from ..clib import libssnode
+from ..networks.dataset import SSNODE_TRUTH_OPTIONS
 
 FEATURES = ('maxrate', 'si', 'prefbw', 'ipr')
 DEFAULT_DRAWS = 30                      # the reference's NZ per checkpoint
 DEFAULT_MAX_DRAWS_PER_LAUNCH = 4096
 #: forward variant (`ssn_gen_forward_variant`) -> the explicit kernel name that runs it
 _VARIANT_KERNELS = {1: 'tile', 2: 'mfma-fp32', 3: 'mfma-fp32-1g', 4: 'split-wide', 5: 'split-1g', 6: 'split-alt', 8: 'duo'}
+DYNAMICS = ('fixed-time', 'fixed-point')
+#: solver options of a fixed-point score: the very ones `networks.dataset.dataset_by_ssnode` makes the truth with
+FIXED_POINT_SOLVER_OPTIONS = SSNODE_TRUTH_OPTIONS
+#: what `fixed_point_options` hands to `ssnode.sample_tuning_curves_table` besides the stimuli and the probes
+FIXED_POINT_OPTION_KEYS = ('io_type', 'k', 'n', 'smoothness', 'dt', 'max_iter', 'atol', 'tau', 'rate_stop_at', 'rate_soft_bound',
+                           'rate_hard_bound', 'solver')
+#: the command-line arguments distdiff.json records in the fixed-time mode: the file keeps the keys it always had
+_FIXED_TIME_ARGUMENTS = ('rundir', 'steps', 'draws', 'seed', 'gen_kernel', 'max_draws_per_launch', 'output', 'save_tuning_curves')
 _SAMPLER_KEYS = ('num_sites', 'bandwidths', 'contrasts', 'smoothness', 'k', 'n', 'tau_E', 'tau_I', 'dt', 'io_type', 'seqlen',
                  'skip_steps')
 
@@ -176,7 +195,32 @@ def sampler_config_of_run(run_config):
     cfg['dist_in'] = rc.get('dist_in', 'bernoulli')
     cfg['gen_kernel'] = rc.get('gen_kernel', 'auto')
     cfg['dtype'] = rc.get('gen_dtype', 'float32')
+    cfg['true_ssn_options'] = dict(rc.get('true_ssn_options') or {})
     return cfg
+
+
+def fixed_point_options(cfg, solver_options=None):
+    """Keyword arguments of `ssnode.sample_tuning_curves_table` for a sampler config, as the truth of `dataset_by_ssnode` gets
+    them: `FIXED_POINT_SOLVER_OPTIONS`, overridden by the config's ``true_ssn_options`` and then by `solver_options`; what
+    neither names (k, n, smoothness among them) is ssnode's default, not the generator's.  Of the recorded options only the
+    `FIXED_POINT_OPTION_KEYS` are taken -- the truth's own J, D, S, V and whatever a fixed-time truth recorded (seqlen, ...)
+    are not the solver's; a key of `solver_options` outside them is refused by name."""
+    unknown = sorted(set(solver_options or {}) - set(FIXED_POINT_OPTION_KEYS))
+    if unknown:
+        raise ValueError('solver_options: unknown options {} (known: {})'.format(unknown, ', '.join(FIXED_POINT_OPTION_KEYS)))
+    recorded = {k: v for k, v in dict(cfg.get('true_ssn_options') or {}).items() if k in FIXED_POINT_OPTION_KEYS}
+    return dict(dict(FIXED_POINT_SOLVER_OPTIONS, **recorded), **(solver_options or {}))
+
+
+def _check_dynamics(dynamics, cfg, solver_dtype):
+    if dynamics not in DYNAMICS:
+        raise ValueError('dynamics must be one of {}, got {!r}'.format(DYNAMICS, dynamics))
+    if dynamics == 'fixed-point':
+        if cfg.get('ssn_type', 'default') != 'default':
+            raise NotImplementedError('fixed-point scoring does not support SSN with heterogeneous input (ssn_type {!r}): the '
+                                      'fixed-point sampler has none'.format(cfg.get('ssn_type')))
+        if solver_dtype not in ('float64', 'float32'):
+            raise ValueError("solver_dtype must be 'float64' or 'float32', got {!r}".format(solver_dtype))
 
 
 # ---- the core -----------------------------------------------------------------------------------------------------------
@@ -260,18 +304,76 @@ def _features(tc, nc, nb, q):
     return feat
 
 
+def _score_fixed_points(sampler_config, thetas, truth, draws, seed, max_draws_per_launch, return_samples, solver_options,
+                        max_candidates, solver_dtype):
+    """`score_parameter_sets` with dynamics='fixed-point'."""
+    _check_dynamics('fixed-point', sampler_config, solver_dtype)
+    cfg, shape, truth32 = _check_config(dict(sampler_config, dtype='float32'), draws, truth)
+    nc, nb, ct, npr, probes = shape
+    draws = int(draws)
+    N = int(cfg['num_sites'])
+    opts = fixed_point_options(cfg, solver_options)
+    from .. import ssnode
+    rounds = ssnode.plan_table_rounds(draws, None, max_candidates)
+    ssnode._theta_table(list(thetas))                                    # (refuses V and other keys before the device is touched)
+    chunk, sizes = plan_chunks(len(thetas), rounds[0][1], max_draws_per_launch)
+
+    import torch
+    clib.require_gpu()
+    tab = ssnode.sample_tuning_curves_table(
+        list(thetas), NZ=draws, seed=seed, N=N, bandwidths=list(cfg['bandwidths']), contrast=list(cfg['contrasts']),
+        sample_sites=probes[:npr], include_inhibitory_neurons=ct == 2, dtype=solver_dtype, max_candidates=max_candidates,
+        max_draws_per_launch=max_draws_per_launch, return_torch=True, **opts)
+    S, Q = len(thetas), ct * npr
+    C = nc * nb * Q
+    stat = stat_names(nc, nb, ct, npr)
+    Ct = len(stat)
+    tsorted, m_dev, m_host = _truth_on_device(truth32, shape)
+    tc = tab.tunings.to(torch.float32).reshape(S * draws, C)
+    feat = _features(tc, nc, nb, Q)
+    # (a row that was not accepted is NaN in every raw column; the feature kernel gives such a curve a finite prefbw)
+    feat = torch.where(torch.isnan(tc[:, :1]), torch.full_like(feat, float('nan')), feat)
+    x = torch.cat([tc, feat], dim=1).contiguous()
+    out_n = torch.empty((S, Ct), device='cuda', dtype=torch.int32)
+    out_num = torch.empty((S, Ct), device='cuda', dtype=torch.int64)
+    clib.check(libssnode.ssn_ks_columns_f32(x.data_ptr(), tsorted.data_ptr(), m_dev.data_ptr(), S, draws, Ct, truth32.shape[0],
+                                            out_n.data_ptr(), out_num.data_ptr(), clib.stream_ptr()), 'ssn_ks_columns_f32')
+    got = torch.stack([out_num, out_n.to(torch.int64)]).cpu().numpy() if S else np.zeros((2, 0, Ct), dtype='int64')
+    num, n = got[0], got[1]
+    result = dict(stat=stat, num=num, n=n, m=m_host, KSD=ksd_from_counts(num, n, m_host[None, :]), gen_kernel=None, chunk=chunk,
+                  chunks=sizes, note=None, draws=draws, seed=seed, bandwidths=[float(b) for b in cfg['bandwidths']],
+                  contrasts=[float(c) for c in cfg['contrasts']], probes=probes, gen_step=np.arange(S), dynamics='fixed-point',
+                  accepted=tab.accepted, used=tab.used, rejections=tab.rejections, candidates=tab.candidates,
+                  solver_variant=tab.variant, solver_options={k: (v if isinstance(v, (int, float, str)) else list(v))
+                                                              for k, v in opts.items()}, solver_dtype=solver_dtype)
+    if return_samples:
+        xh = x.cpu().numpy().reshape(S, draws, Ct)
+        result['tuning_curves'], result['features'] = xh[:, :, :C], xh[:, :, C:]
+    return result
+
+
 def score_parameter_sets(sampler_config, thetas, truth, draws=DEFAULT_DRAWS, seed=0, gen_kernel=None,
-                         max_draws_per_launch=DEFAULT_MAX_DRAWS_PER_LAUNCH, return_samples=False):
+                         max_draws_per_launch=DEFAULT_MAX_DRAWS_PER_LAUNCH, return_samples=False, dynamics='fixed-time',
+                         solver_options=None, max_candidates=None, solver_dtype='float64'):
     """KS statistics of `draws` tuning curves per parameter set against `truth`, all sets on the same noise.
 
     sampler_config: the fixed-time sampler -- num_sites, bandwidths, contrasts, smoothness, k, n, tau_E, tau_I, dt, io_type,
       seqlen, skip_steps (defaults: networks.wgan.DEFAULT_PARAMS), norm_probes + include_inhibitory_neurons (or probes),
       ssn_type, dist_in, gen_kernel.
+    dynamics: 'fixed-time' (the generator above) or 'fixed-point': the curves of a set are those of the first `draws` candidate
+      draws whose fixed points converge for every stimulus (`ssnode.sample_tuning_curves_table` in `solver_dtype`, at most
+      `max_candidates` candidates; solver options: `fixed_point_options`); sets with heterogeneous input are refused
+      (NotImplementedError).  The result then has accepted, used (S,), rejections (S, 2), candidates and solver_variant too, and
+      ``n`` is the accepted count.
     thetas: list of dicts J, D, S (2 x 2 or scalars) and V where the ssn_type has it.
     truth: (T, columns) array in the sampler's column order.
 
     Returns a dict: stat (names, `stat_names`), num / n (S, C') and m (C',) integers, KSD (S, C'), gen_kernel (the kernel that
     ran), chunk, chunks, note; with `return_samples` also tuning_curves (S, draws, C) and features (S, draws, 4 curves)."""
+    if dynamics != 'fixed-time':
+        _check_dynamics(dynamics, sampler_config, solver_dtype)
+        return _score_fixed_points(sampler_config, thetas, truth, draws, seed, max_draws_per_launch, return_samples,
+                                   solver_options, max_candidates, solver_dtype)
     kernel_name = gen_kernel or sampler_config.get('gen_kernel') or 'auto'
     cfg, shape, truth32 = _check_config(sampler_config, draws, truth)
     nc, nb, ct, npr, probes = shape
@@ -349,10 +451,12 @@ def _records(records_or_path):
 
 
 def calc_distdiff(records_or_path, steps=slice(None), draws=DEFAULT_DRAWS, seed=0, gen_kernel=None,
-                  max_draws_per_launch=DEFAULT_MAX_DRAWS_PER_LAUNCH, return_samples=False, extra_thetas=()):
+                  max_draws_per_launch=DEFAULT_MAX_DRAWS_PER_LAUNCH, return_samples=False, extra_thetas=(),
+                  dynamics='fixed-time', solver_options=None, max_candidates=None, solver_dtype='float64'):
     """`score_parameter_sets` for the rows `steps` (a slice or a list of row positions) of a run's ``generator`` table, with the
     run's own sampler and ``truth.npy``.  `extra_thetas`: parameter sets scored in front of the rows (gen_step -1, -2, ...),
-    e.g. the truth's own.  The result carries the rows' ``gen_step``."""
+    e.g. the truth's own.  The result carries the rows' ``gen_step``.  `dynamics`, `solver_options`, `max_candidates`,
+    `solver_dtype`: see `score_parameter_sets` (the run's recorded ``true_ssn_options`` come before `solver_options`)."""
     rec = _records(records_or_path)
     try:
         table = rec.generator
@@ -364,7 +468,8 @@ def calc_distdiff(records_or_path, steps=slice(None), draws=DEFAULT_DRAWS, seed=
     thetas = list(extra_thetas) + [rec.gen_params_at(i) for i in positions]
     gen_step = np.concatenate([-1 - np.arange(len(extra_thetas)), np.asarray(table['gen_step'], dtype='int64')[positions]]).astype('int64')
     result = score_parameter_sets(cfg, thetas, rec.truth, draws=draws, seed=seed, gen_kernel=gen_kernel,
-                                  max_draws_per_launch=max_draws_per_launch, return_samples=return_samples)
+                                  max_draws_per_launch=max_draws_per_launch, return_samples=return_samples, dynamics=dynamics,
+                                  solver_options=solver_options, max_candidates=max_candidates, solver_dtype=solver_dtype)
     result['gen_step'] = gen_step
     return result
 
@@ -382,21 +487,45 @@ def make_parser():
     parser.add_argument('--output', default=None, help='Output directory (default: the run directory).')
     parser.add_argument('--save-tuning-curves', action='store_true',
                         help='Also write tuning_curves/{:010d}.csv, bandwidths.csv and sample_epochs.csv.')
+    parser.add_argument('--dynamics', default='fixed-time', choices=DYNAMICS,
+                        help="'fixed-point': score the first --draws candidate draws whose fixed points converge (the truth of "
+                             "--dataset-provider ssnode) and write rejections.csv.")
+    parser.add_argument('--max-candidates', default=None, type=int,
+                        help='fixed-point: candidate draws per checkpoint at most (default: max(4 draws, draws + 64)).')
+    parser.add_argument('--solver-dtype', default='float64', choices=('float64', 'float32'), help='fixed-point: solver arithmetic.')
     return parser
+
+
+def write_rejections(path, result):
+    """rejections.csv of a fixed-point result: gen_step, accepted, used, code1, code2 per checkpoint."""
+    import pandas
+    pandas.DataFrame(dict(gen_step=np.asarray(result['gen_step']), accepted=result['accepted'], used=result['used'],
+                          code1=result['rejections'][:, 0], code2=result['rejections'][:, 1]),
+                     columns=['gen_step', 'accepted', 'used', 'code1', 'code2']).to_csv(path, index=False)
 
 
 def main(args=None):
     ns = make_parser().parse_args(args)
     output = ns.output or ns.rundir
     result = calc_distdiff(ns.rundir, steps=parse_steps(ns.steps), draws=ns.draws, seed=ns.seed, gen_kernel=ns.gen_kernel,
-                           max_draws_per_launch=ns.max_draws_per_launch, return_samples=ns.save_tuning_curves)
+                           max_draws_per_launch=ns.max_draws_per_launch, return_samples=ns.save_tuning_curves,
+                           dynamics=ns.dynamics, max_candidates=ns.max_candidates, solver_dtype=ns.solver_dtype)
     os.makedirs(output, exist_ok=True)
     write_long_table(os.path.join(output, 'distdiff.csv'), result)
+    fixed_point = ns.dynamics == 'fixed-point'
+    arguments = {k: v for k, v in vars(ns).items() if fixed_point or k in _FIXED_TIME_ARGUMENTS}
+    extra = {}
+    if fixed_point:
+        write_rejections(os.path.join(output, 'rejections.csv'), result)
+        extra = dict(dynamics='fixed-point', accepted=[int(v) for v in result['accepted']], used=[int(v) for v in result['used']],
+                     rejections=[[int(v) for v in row] for row in result['rejections']], candidates=int(result['candidates']),
+                     solver_variant=int(result['solver_variant']), solver_options=result['solver_options'],
+                     solver_dtype=result['solver_dtype'])
     with open(os.path.join(output, 'distdiff.json'), 'w') as f:
-        json.dump(dict(arguments=dict(vars(ns)), gen_kernel=result['gen_kernel'], note=result['note'], chunk=result['chunk'],
+        json.dump(dict(arguments=arguments, gen_kernel=result['gen_kernel'], note=result['note'], chunk=result['chunk'],
                        chunks=result['chunks'], draws=result['draws'], bandwidths=result['bandwidths'],
                        contrasts=result['contrasts'], probes=result['probes'], features=list(FEATURES),
-                       gen_steps=[int(s) for s in result['gen_step']]), f, indent=1)
+                       gen_steps=[int(s) for s in result['gen_step']], **extra), f, indent=1)
     if ns.save_tuning_curves:
         tcdir = os.path.join(output, 'tuning_curves')
         os.makedirs(tcdir, exist_ok=True)

@@ -358,6 +358,7 @@ DECLARED_SYMBOLS = (
     'ssn_ens_record_doubles', 'ssn_ens_moments_f32', 'ssn_ens_jds_grad_f32', 'ssn_ens_gen_grads_f32', 'ssn_ens_apply_f32',
     'ssn_ens_stimulus_hetero_f32',
     'ssn_build_w_table_f32', 'ssn_tc_features_f32', 'ssn_ks_columns_f32',
+    'ssn_build_w_table_f64', 'ssn_fp_select_max_candidates', 'ssn_fp_select_f64', 'ssn_fp_select_f32',
 )
 
 class EnsGrads(Structure):
@@ -400,6 +401,18 @@ libssnode.ssn_tc_features_f32.argtypes = [c_void_p, c_void_p, c_long, c_int, c_i
 libssnode.ssn_ks_columns_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
 for _name in ('ssn_build_w_table_f32', 'ssn_tc_features_f32', 'ssn_ks_columns_f32'):
     getattr(libssnode, _name).restype = c_int
+
+libssnode.ssn_build_w_table_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
+libssnode.ssn_build_w_table_f64.restype = c_int
+libssnode.ssn_fp_select_max_candidates.argtypes = []
+libssnode.ssn_fp_select_max_candidates.restype = c_int
+for _name in ('ssn_fp_select_f64', 'ssn_fp_select_f32'):
+    # codes, x, A, R, NB, M, probes, nprobe, set_of, cand0, NZ, verdict, out, accepted, used, rejections, draw_index, stream
+    getattr(libssnode, _name).argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int] + \
+        [c_void_p] * 7
+    getattr(libssnode, _name).restype = c_int
+#: most candidates of one `ssn_fp_select_*` round (host arithmetic of the library: no device needed)
+FP_SELECT_MAX_CANDIDATES = libssnode.ssn_fp_select_max_candidates()
 
 libssnode.ssn_critic_num_params_act.argtypes = [c_void_p, c_void_p, c_int]
 libssnode.ssn_critic_num_params_act.restype = c_long

@@ -27,6 +27,32 @@ int fail(hipError_t e, const char* where) {
         if (e__ != hipSuccess) return fail(e__, #expr);   \
     } while (0)
 
+// one round of the device rejection sampler (ssn_fp_select_f64 / _f32)
+template <typename T>
+int fp_select_impl(const char* name, const int* codes, const T* x, int A, int R, int NB, int M, const int* probes, int nprobe,
+                          const int* set_of, int cand0, int NZ, int* verdict, T* out, int* accepted, int* used, int* rejections,
+                          int* draw_index, void* stream) {
+    if (R > ssn::fp_select_max_candidates()) {
+        g_last_error = std::string(name) + ": more than " + std::to_string(ssn::fp_select_max_candidates()) +
+                       " candidates in one round (the accepted indices of a round are kept in LDS)";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if (A < 0 || R < 0 || NB < 1 || M <= 0 || (M & 1) || nprobe < 0 || NZ < 1 || cand0 < 0 || (long)NB * M >= (1L << 31) ||
+        (long)NZ * NB * nprobe >= (1L << 31) || (long)cand0 + R >= (1L << 31) ||
+        ((long)A * R > 0 && (!codes || !x || !set_of || !verdict || !out || !accepted || !used || !rejections || !draw_index ||
+                             (nprobe > 0 && !probes)))) {
+        g_last_error = std::string(name) + ": invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if ((long)A * R == 0) return 0;                           // empty batch
+    ssn::FpSelectArgs<T> a;
+    a.codes = codes; a.x = x; a.A = A; a.R = R; a.NB = NB; a.M = M; a.probes = probes; a.nprobe = nprobe; a.set_of = set_of;
+    a.cand0 = cand0; a.NZ = NZ; a.verdict = verdict; a.out = out; a.accepted = accepted; a.used = used; a.rejections = rejections;
+    a.draw_index = draw_index;
+    SSN_TRY(ssn::launch_fp_select<T>(a, (hipStream_t)stream));
+    return 0;
+}
+
 // Operand precision of the AUTOMATIC kernel choice (kernel = 0, variant < 0): process-wide state behind
 // ssn_set_operand_precision / ssn_get_operand_precision (include/ssnode_mi355x.h).  1 = the fp16-split matrix-core kernels
 // where they apply (W and state as two fp16 parts each), 0 = fp32 operands only.  The environment variable SSN_FWD_SPLIT=0
@@ -1102,6 +1128,27 @@ int ssn_ks_columns_f32(const float* x, const float* truth_sorted, const int* m, 
     }
     SSN_TRY(ssn::launch_ks_columns(x, truth_sorted, m, S, B, C, T, n, num, (hipStream_t)stream));
     return 0;
+}
+int ssn_build_w_table_f64(const double* z, const double* jds_table, double* W, int S, int B, int N, void* stream) {
+    if (S < 0 || B < 0 || N < 1 || ((long)S * B > 0 && (!z || !jds_table || !W))) {
+        g_last_error = "ssn_build_w_table_f64: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_build_w_table_f64(z, jds_table, W, S, B, N, (hipStream_t)stream));
+    return 0;
+}
+int ssn_fp_select_max_candidates(void) { return ssn::fp_select_max_candidates(); }
+int ssn_fp_select_f64(const int* codes, const double* x, int A, int R, int NB, int M, const int* probes, int nprobe, const int* set_of,
+                      int cand0, int NZ, int* verdict, double* out, int* accepted, int* used, int* rejections, int* draw_index,
+                      void* stream) {
+    return fp_select_impl<double>("ssn_fp_select_f64", codes, x, A, R, NB, M, probes, nprobe, set_of, cand0, NZ, verdict, out, accepted,
+                                  used, rejections, draw_index, stream);
+}
+int ssn_fp_select_f32(const int* codes, const float* x, int A, int R, int NB, int M, const int* probes, int nprobe, const int* set_of,
+                      int cand0, int NZ, int* verdict, float* out, int* accepted, int* used, int* rejections, int* draw_index,
+                      void* stream) {
+    return fp_select_impl<float>("ssn_fp_select_f32", codes, x, A, R, NB, M, probes, nprobe, set_of, cand0, NZ, verdict, out, accepted,
+                                 used, rejections, draw_index, stream);
 }
 int ssn_moment_sums_f32(const float* x, int B, int D, double* sums, void* stream) {
     if (B < 0 || D < 0 || (D > 0 && (!x || !sums))) {

@@ -319,6 +319,23 @@ hipError_t launch_tc_features(const float* tc, float* feat, long R, int NC, int 
 hipError_t launch_ks_columns(const float* x, const float* t, const int* m, int S, int B, int C, int T, int* n_out,
                              long long* num_out, hipStream_t st);
 
+// ssn_fpsample.hip (rejection sampling of fixed points on the device: W table in fp64, verdict per (set, candidate), selection)
+hipError_t launch_build_w_table_f64(const double* z, const double* table, double* W, int A, int B, int N, hipStream_t st);
+template <typename T>
+struct FpSelectArgs {
+    const int* codes;      // [A][R][NB] solver codes
+    const T* x;            // [A][R][NB][M] solver states
+    int A, R, NB, M;
+    const int* probes; int nprobe;   // device [nprobe]: neurons gathered per stimulus
+    const int* set_of;     // device [A]: row of the arrays below
+    int cand0, NZ;
+    int* verdict;          // [A][R] workspace, left filled
+    T* out;                // [.][NZ][NB nprobe]
+    int *accepted, *used, *rejections, *draw_index;   // [.], [.], [.][2], [.][NZ]
+};
+int fp_select_max_candidates();
+template <typename T> hipError_t launch_fp_select(const FpSelectArgs<T>& a, hipStream_t st);
+
 // ssn_mt19937.hip: numpy's RandomState.random_sample on the device (key / pos: the host state, in/out)
 int mt19937_jump_poly(unsigned long long nblocks, unsigned long long* bits);
 hipError_t mt19937_draw(unsigned int* key, int* pos, unsigned long long total, unsigned long long skip, unsigned long long count,

@@ -9,6 +9,9 @@ from .fixed_time_sampler import DEFAULT_PARAMS, FixedTimeTuningCurveSampler
 logger = getLogger(__name__)
 
 dataset_provider_choices = ('ssnode', 'fixedtime')
+#: solver options `dataset_by_ssnode` makes the truth with unless `true_ssn_options` says otherwise (dataset.py:28-71); the
+#: fixed-point scorer (analyzers/distdiff.py) starts from the same ones
+SSNODE_TRUTH_OPTIONS = dict(dt=5e-4, max_iter=100000, io_type='asym_power', rate_stop_at=200)
 
 
 def dataset_by_ssnode(num_sites, bandwidths, contrasts, truth_size, truth_seed, sample_sites,
@@ -18,7 +21,7 @@ def dataset_by_ssnode(num_sites, bandwidths, contrasts, truth_size, truth_seed, 
     data, (_, _, fpinfo) = ssnode.sample_tuning_curves(
         sample_sites=sample_sites, NZ=truth_size, seed=truth_seed, bandwidths=bandwidths, contrast=contrasts,
         N=num_sites, track_offset_identity=True, include_inhibitory_neurons=include_inhibitory_neurons,
-        **dict(dict(dt=5e-4, max_iter=100000, io_type='asym_power', rate_stop_at=200), **true_ssn_options))
+        **dict(SSNODE_TRUTH_OPTIONS, **true_ssn_options))
     data = np.array(data.T)
     logger.info('ssnode.sample_tuning_curves: rejections=%s codes=%r', fpinfo.rejections, fpinfo.counter)
     return data

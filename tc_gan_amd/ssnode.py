@@ -514,3 +514,196 @@ def sample_tuning_curves(sample_sites=[0], track_offset_identity=False,
     probed = subsample_neurons(np.array(sample[1]), sample_sites, include_inhibitory_neurons=include_inhibitory_neurons,
                                track_offset_identity=track_offset_identity)
     return probed.T, sample
+
+
+# --------------------------------------------------------------------------
+# rejection sampling for a table of parameter sets, on the device
+# --------------------------------------------------------------------------
+TuningCurveTable = collections.namedtuple('TuningCurveTable', [
+    'tunings', 'accepted', 'used', 'rejections', 'draw_index', 'candidates', 'variant',
+])
+_TABLE_DTYPES = ('float64', 'float32')
+
+
+def default_max_candidates(NZ):
+    """Candidates `sample_tuning_curves_table` draws at most when the caller sets no limit: four times the rows wanted, and
+    at least 64 more than them."""
+    return max(4 * int(NZ), int(NZ) + 64)
+
+
+def plan_table_rounds(NZ, round_draws=None, max_candidates=None):
+    """[(first candidate, count)] of the rounds that cover `max_candidates` candidates, `round_draws` (default `NZ`) per round
+    but possibly the last.  Refuses sizes out of range.
+
+    >>> plan_table_rounds(12, 5, 12)
+    [(0, 5), (5, 5), (10, 2)]
+    """
+    NZ = int(NZ)
+    if NZ < 1:
+        raise ValueError('NZ must be at least 1, got {}'.format(NZ))
+    round_draws = NZ if round_draws is None else int(round_draws)
+    if not 1 <= round_draws <= clib.FP_SELECT_MAX_CANDIDATES:
+        raise ValueError('round_draws = {} is out of range: a round has 1 to {} candidates'
+                         .format(round_draws, clib.FP_SELECT_MAX_CANDIDATES))
+    max_candidates = default_max_candidates(NZ) if max_candidates is None else int(max_candidates)
+    if max_candidates < 1:
+        raise ValueError('max_candidates must be at least 1, got {}'.format(max_candidates))
+    return [(c0, min(round_draws, max_candidates - c0)) for c0 in range(0, max_candidates, round_draws)]
+
+
+def plan_table_chunks(num_active, count, max_draws_per_launch):
+    """Sizes of the chunks of `num_active` sets such that one solve has at most `max_draws_per_launch` (set, candidate) pairs of a
+    round of `count` candidates (one set per launch where a round alone is more than that).
+
+    >>> plan_table_chunks(5, 12, 40)
+    [3, 2]
+    """
+    num_active, count, budget = int(num_active), int(count), int(max_draws_per_launch)
+    if count < 1 or budget < 1 or num_active < 0:
+        raise ValueError('need count >= 1, max_draws_per_launch >= 1 and num_active >= 0')
+    chunk = max(1, budget // count)
+    return [chunk] * (num_active // chunk) + ([num_active % chunk] if num_active % chunk else [])
+
+
+def _theta_table(thetas):
+    """float64 [S][12] of J, D, S; refuses other keys."""
+    table = np.empty((len(thetas), 12), dtype='float64')
+    for i, th in enumerate(thetas):
+        unknown = set(th) - {'J', 'D', 'S'}
+        if unknown:
+            raise ValueError('parameter set {}: unknown parameters {} (a fixed-point sample has J, D and S)'
+                             .format(i, sorted(unknown)))
+        for j, name in enumerate('JDS'):
+            if name not in th:
+                raise ValueError('parameter set {}: {} is missing'.format(i, name))
+            table[i, 4 * j:4 * j + 4] = np.broadcast_to(np.asarray(th[name], dtype='float64'), (2, 2)).reshape(4)
+    return table
+
+
+def _check_table_call(thetas, NZ, N, sample_sites, include_inhibitory_neurons, dtype, round_draws, max_candidates,
+                      max_draws_per_launch, offset):
+    """Everything `sample_tuning_curves_table` refuses without a device: (table, rounds, probes)."""
+    import os
+    if list(np.atleast_1d(offset)) != [0]:
+        raise ValueError('offset = {!r}: sample_tuning_curves_table takes stimuli at offset [0] only'.format(offset))
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise ValueError('sample_tuning_curves_table runs on one GPU: data-parallel ranks (WORLD_SIZE = {}) are not supported'
+                         .format(os.environ['WORLD_SIZE']))
+    if str(dtype) not in _TABLE_DTYPES:
+        raise ValueError('dtype must be one of {}, got {!r}'.format(_TABLE_DTYPES, dtype))
+    rounds = plan_table_rounds(NZ, round_draws, max_candidates)
+    if int(max_draws_per_launch) < 1:
+        raise ValueError('max_draws_per_launch must be at least 1, got {}'.format(max_draws_per_launch))
+    table = _theta_table(list(thetas))
+    sites = [int(s) for s in sample_sites]
+    if not sites or min(sites) < 0 or max(sites) >= int(N):
+        raise ValueError('sample_sites = {!r}: sites are neuron indices 0 .. N - 1 = {}'.format(list(sample_sites), int(N) - 1))
+    probes = sites + ([s + int(N) for s in sites] if include_inhibitory_neurons else [])
+    return table, rounds, probes
+
+
+def sample_tuning_curves_table(
+        thetas, NZ=30, seed=0,
+        N=DEFAULT_PARAMS['N'],
+        bandwidths=DEFAULT_PARAMS['bandwidths'],
+        smoothness=DEFAULT_PARAMS['smoothness'],
+        contrast=DEFAULT_PARAMS['contrast'],
+        sample_sites=[0], include_inhibitory_neurons=False,
+        io_type=DEFAULT_PARAMS['io_type'],
+        k=DEFAULT_PARAMS['k'],
+        n=DEFAULT_PARAMS['n'],
+        dtype='float64', round_draws=None, max_candidates=None, max_draws_per_launch=4096,
+        variant=None, return_torch=False, **solver_kwargs):
+    """
+    `sample_tuning_curves(track_offset_identity=True, ...)` for a table of parameter sets, without leaving the device
+    (additive API): for every set of `thetas` (dicts of J, D, S) the tuning curves of the first `NZ` candidate draws, in stream
+    order, whose fixed points converge for every stimulus.  Every set sees the SAME candidate stream -- candidate i is the
+    i-th ``rand(1, 2N, 2N)`` of ``numpy.random.RandomState(seed)``, what `sample_fixed_points` consumes for one set.
+
+    The candidates come in rounds of `round_draws` (default `NZ`): the round's z is drawn on the device (`device_rand`, in
+    `dtype`), W is formed for the sets that still need rows (`ssn_build_w_table_*`), all their (set, candidate) pairs are solved
+    against the shared stimuli in launches of at most `max_draws_per_launch` pairs, and `ssn_fp_select_*` classifies the solves,
+    counts the rejections and gathers the probed rates of the accepted candidates; one small array of accepted counts is read
+    back per round.  Sampling stops when every set has `NZ` rows or after `max_candidates` candidates (default
+    `default_max_candidates(NZ)`); a set that is short then has ``accepted < NZ`` and NaN rows.
+
+    `variant`: the solver variant every launch runs (`fixed_points_batch`); None = what the library picks for the first
+    launch's shape, kept for all launches, so that the result does not depend on the grouping.  Other keywords go to the solver
+    (dt, max_iter, atol, tau, rate_stop_at, rate_soft_bound, rate_hard_bound).
+
+    Returns `TuningCurveTable`: tunings (S, NZ, C) float64 with the columns of
+    ``sample_tuning_curves(track_offset_identity=True, ...)[0].T`` (stimulus, then E sites, then I sites); accepted (S,); used
+    (S,) -- candidates examined up to and including the NZ-th success, or all that were drawn; rejections (S, 2) -- codes 1 and
+    2 among those; draw_index (S, NZ) -- stream index of every row, -1 where there is none; candidates -- the number drawn;
+    variant.  ``accepted + rejections.sum(1) == used`` for every set.  `return_torch`: tunings stays a CUDA tensor of `dtype`.
+    """
+    solver_kwargs = dict(solver_kwargs)
+    offset = solver_kwargs.pop('offset', [0])
+    r0 = solver_kwargs.pop('r0', None)
+    table, rounds, probes = _check_table_call(thetas, NZ, N, sample_sites, include_inhibitory_neurons, np.dtype(dtype).name,
+                                              round_draws, max_candidates, max_draws_per_launch, offset)
+    if io_type not in clib.IO_CODES:
+        raise ValueError("Unknown I/O type: {}".format(io_type))
+    torch = _torch()
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise ValueError('sample_tuning_curves_table runs on one GPU: data-parallel ranks (world size {}) are not supported'
+                         .format(dist.get_world_size()))
+    clib.require_gpu()
+    from .networks.ssn import device_rand
+    f64 = np.dtype(dtype).name == 'float64'
+    tdtype = torch.float64 if f64 else torch.float32
+    build = libssnode.ssn_build_w_table_f64 if f64 else libssnode.ssn_build_w_table_f32
+    select = libssnode.ssn_fp_select_f64 if f64 else libssnode.ssn_fp_select_f32
+    NZ, N, S = int(NZ), int(N), len(table)
+    M = 2 * N
+    exts = _device_tensor(_stimulus_rows(N, bandwidths, smoothness, contrast), tdtype)        # contrast-major, then bandwidth
+    NB, npr = int(exts.shape[0]), len(probes)
+    C = NB * npr
+    solver_options = dict(solver_kwargs, k=k, n=n, io_type=io_type)
+    if r0 is not None:
+        r0 = _device_tensor(r0, tdtype).reshape(-1)
+        assert r0.shape == (M,)
+    if variant is None and S:
+        first = min(S, max(1, int(max_draws_per_launch) // rounds[0][1])) * rounds[0][1]
+        stop = solver_options.get('rate_stop_at', np.inf) if io_type in _UNBOUNDED_IO else \
+            solver_options.get('rate_hard_bound', DEFAULT_PARAMS['rate_hard_bound'])
+        p = _params(io_type, k, n, tau=solver_options.get('tau', DEFAULT_PARAMS['tau']), dt=solver_options.get('dt', .0008),
+                    max_iter=solver_options.get('max_iter', 10000), atol=solver_options.get('atol', 1e-5),
+                    rate_soft_bound=solver_options.get('rate_soft_bound', DEFAULT_PARAMS['rate_soft_bound']), rate_hard_bound=stop)
+        variant = int(libssnode.ssn_solve_batch_variant_for(first, NB, M, 8 if f64 else 4, ctypes.byref(p)))
+        if variant < 0:
+            raise ValueError('the solver has no kernel for {} draws of {} stimuli at 2N = {}'.format(first, NB, M))
+    dev = dict(device='cuda', dtype=torch.int32)
+    table_dev = _device_tensor(table, tdtype)
+    probes_dev = torch.as_tensor(np.asarray(probes, dtype='int32')).to('cuda')
+    out = torch.full((S, NZ, C), float('nan'), device='cuda', dtype=tdtype)
+    accepted, used = torch.zeros(S, **dev), torch.zeros(S, **dev)
+    rejections, draw_index = torch.zeros((S, 2), **dev), torch.full((S, NZ), -1, **dev)
+    rng = np.random.RandomState(seed)
+    active = np.arange(S)
+    candidates = 0
+    for cand0, count in rounds:
+        if not len(active):
+            break
+        z = device_rand(rng, (count, M, M), tdtype)
+        candidates += count
+        a0 = 0
+        for na in plan_table_chunks(len(active), count, max_draws_per_launch):
+            rows = torch.as_tensor(active[a0:a0 + na].astype('int32')).to('cuda')
+            W = torch.empty((na * count, M, M), device='cuda', dtype=tdtype)
+            chunk_table = table_dev[rows.long()].contiguous()
+            clib.check(build(z.data_ptr(), chunk_table.data_ptr(), W.data_ptr(), na, count, N, _stream_ptr()),
+                       'ssn_build_w_table')
+            start = None if r0 is None else r0.expand(na * count, NB, M)
+            res = fixed_points_batch(W, exts, r0=start, dtype=dtype, variant=variant, return_torch=True, **solver_options)
+            verdict = torch.empty((na, count), **dev)
+            clib.check(select(res.codes.data_ptr(), res.x.data_ptr(), na, count, NB, M, probes_dev.data_ptr(), npr, rows.data_ptr(),
+                              cand0, NZ, verdict.data_ptr(), out.data_ptr(), accepted.data_ptr(), used.data_ptr(),
+                              rejections.data_ptr(), draw_index.data_ptr(), _stream_ptr()), 'ssn_fp_select')
+            a0 += na
+        active = np.nonzero(accepted.cpu().numpy() < NZ)[0]              # the round's one copy to the host
+    torch.cuda.synchronize()
+    return TuningCurveTable(out if return_torch else out.cpu().numpy().astype('float64'), accepted.cpu().numpy().astype('int64'),
+                            used.cpu().numpy().astype('int64'), rejections.cpu().numpy().astype('int64'),
+                            draw_index.cpu().numpy().astype('int64'), candidates, variant)
