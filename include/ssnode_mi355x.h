@@ -190,22 +190,15 @@ typedef struct ssn_gen_params {
     int io_type;                 /* SSN_IO_* */
     int seqlen;                  /* T: Euler steps from r = 0 */
     int skip_steps;              /* first output index of the measurement window */
-    int kernel;                  /* 0 library default, 1 VALU tile kernels, 2 fp32 MFMA kernels (fp32, NB >= 4), 3 the
-                                  * same with one 4-stimulus group per workgroup (few draws: more workgroups), 4 / 5
-                                  * forward: fp16-split MFMA kernel (W carried as two fp16 parts = 22 significant bits,
-                                  * the state as three = exact, every product exact, fp32 accumulation; asym_tanh only)
-                                  * with two / one group per workgroup -- with two groups all 8 stimuli share one MFMA
-                                  * chain per step and the state enters it as two fp16 parts (22 bits, like W); 6 = two
-                                  * groups in the alternating form, which carries the state as three parts (exact);
-                                  * backward: the adjoint sweep in the alternating form
-                                  * (W^T as two fp16 parts, delta as three with a scale that follows max |delta| step
-                                  * by step; any I/O function); 8 = fp16-split forward with TWO DRAWS per workgroup
-                                  * (csrc/ssn_duo.hip: the chain of one draw behind the serial part of the other, W and
-                                  * state as two fp16 parts each by round to nearest = 23 bits; backward: the adjoint sweep in
-                                  * the same two-draw form, W^T and delta as two parts each, any I/O function).  0 picks
-                                  * 8 / 4 / 5 where they apply (8 when there are more than 256 (draw, 8 stimuli) units)
-                                  * unless ssn_set_operand_precision(0) -- or SSN_FWD_SPLIT=0 as the initial value --
-                                  * keeps the automatic choice on fp32 operands. */
+    int kernel;                  /* which kernels run the forward and the adjoint sweep -- the rule is DESIGN.md 3.5a:
+                                  * 0 the library chooses (under ssn_set_operand_precision), 1 VALU tile / streaming
+                                  * kernels; fp32 with NB >= 4 and 2N <= 208 also 2 / 3 fp32 MFMA kernels with two / one
+                                  * 4-stimulus group per workgroup, and the fp16-split MFMA kernels (forward: asym_tanh
+                                  * only, W as two fp16 parts; adjoint: any I/O function): 4 two groups, wide form (state
+                                  * as two parts), 5 one group (state as three parts, exact), 6 two groups, alternating
+                                  * form (exact state; the adjoint has one two-group form), 8 two draws per workgroup
+                                  * (csrc/ssn_duo.hip, W and state as two parts by round to nearest).  Any other code is
+                                  * refused. */
     double k, n;
     double tau_E, tau_I, dt;     /* eps = dt / tau per neuron */
     double rate_soft_bound, rate_hard_bound;
@@ -214,11 +207,10 @@ typedef struct ssn_gen_params {
 
 /* 1 if the register-stationary generator kernels cover this size (2N <= 208 fp32, <= 104 fp64). */
 int ssn_gen_supported(int M, int dtype_bytes);
-/* Which fp32 forward kernel ssn_gen_forward_f32 runs for this call shape and p->kernel (the numbering of p->kernel:
- * 1 VALU tile / streaming kernels, 2 / 3 fp32 MFMA, 4 / 5 / 6 / 8 fp16-split MFMA: 4 two groups in the wide form, 5 one
- * group, 6 two groups in the alternating form, 8 two draws per workgroup; 7: wide form with an exact state, SSN_FWD_WIDE=3);
- * save != 0: with trajectory stores;
- * -1: the call would be refused.  For benchmarks and tests that must name the kernel they measured. */
+/* Which fp32 forward kernel ssn_gen_forward_f32 runs for this call shape and p->kernel -- the launch's own decision, taken
+ * without launching (the numbering of p->kernel; 7: wide form with an exact state, SSN_FWD_WIDE=3); seqlen replaces
+ * p->seqlen; save != 0: with trajectory stores; -1: the call would be refused.  For benchmarks and tests that must name the
+ * kernel they measured. */
 int ssn_gen_forward_variant(int B, int NB, int M, int seqlen, int save, const ssn_gen_params *p);
 
 /*

@@ -47,8 +47,6 @@ from ..networks.dataset import SSNODE_TRUTH_OPTIONS
 FEATURES = ('maxrate', 'si', 'prefbw', 'ipr')
 DEFAULT_DRAWS = 30                      # the reference's NZ per checkpoint
 DEFAULT_MAX_DRAWS_PER_LAUNCH = 4096
-#: forward variant (`ssn_gen_forward_variant`) -> the explicit kernel name that runs it
-_VARIANT_KERNELS = {1: 'tile', 2: 'mfma-fp32', 3: 'mfma-fp32-1g', 4: 'split-wide', 5: 'split-1g', 6: 'split-alt', 8: 'duo'}
 DYNAMICS = ('fixed-time', 'fixed-point')
 #: solver options of a fixed-point score: the very ones `networks.dataset.dataset_by_ssnode` makes the truth with
 FIXED_POINT_SOLVER_OPTIONS = SSNODE_TRUTH_OPTIONS
@@ -231,18 +229,7 @@ def _resolve_kernel(name, rows, nb, M, cfg):
     note = None
     if name == 'duo-fused':
         name, note = 'duo', "gen_kernel 'duo-fused' differs from 'duo' only in the backward: the forward ran as 'duo'"
-    gp = _gen_params(cfg, clib.gen_kernel_code(name))
-    variant = genops.forward_variant(rows, nb, M, gp)
-    if variant < 0 or (name == 'auto' and variant not in _VARIANT_KERNELS):
-        raise ValueError('generator kernel {!r} has no form for {} draws of {} stimuli, num_sites = {}, io_type {!r}'
-                         .format(name, rows, nb, M // 2, cfg['io_type']))
-    return (_VARIANT_KERNELS[variant] if name == 'auto' else name), note
-
-
-def _gen_params(cfg, kernel):
-    from .. import genops
-    return genops.make_gen_params(io_type=cfg['io_type'], k=cfg['k'], n=cfg['n'], tau_E=cfg['tau_E'], tau_I=cfg['tau_I'],
-                                  dt=cfg['dt'], seqlen=cfg['seqlen'], skip_steps=cfg['skip_steps'], kernel=kernel)
+    return genops.resolve_kernel(rows, nb, M, genops.gen_params_of(cfg, clib.gen_kernel_code(name))), note
 
 
 def shared_noise(cfg, draws, seed):
@@ -385,10 +372,10 @@ def score_parameter_sets(sampler_config, thetas, truth, draws=DEFAULT_DRAWS, see
     M, NBT, Q = 2 * N, nc * nb, ct * npr
     C = NBT * Q
     kernel, note = _resolve_kernel(kernel_name, chunk * draws, NBT, M, cfg)
-    gp = _gen_params(cfg, clib.gen_kernel_code(kernel))
 
     import torch
     from .. import genops
+    gp = genops.gen_params_of(cfg, clib.gen_kernel_code(kernel))
     from ..networks._common import grid_stimulator_inputs
     from ..stimuli import stimulus_batch
     from ..utils import to_device

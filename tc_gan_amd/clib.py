@@ -480,6 +480,8 @@ GEN_KERNELS = collections.OrderedDict([
                           # one draw per workgroup); a host-side choice: ssn_gen_params.kernel carries 8
 ])
 GEN_KERNEL_FUSED = 9
+#: code -> name; for the codes 1 .. 8 also: forward variant (`ssn_gen_forward_variant`) -> the explicit name that runs it
+GEN_KERNEL_NAMES = {code: name for name, code in GEN_KERNELS.items()}
 OPERAND_PRECISIONS = {'fp32': 0, 'split': 1}
 
 

@@ -62,6 +62,10 @@ static std::atomic<int>& operand_precision_state() {
     return st;
 }
 static bool forward_split_default() { return operand_precision_state().load(std::memory_order_relaxed) != 0; }
+static long units8(int B, int NB) { return (long)B * ((NB + 7) / 8); }   // workgroups of two 4-stimulus groups each
+// fp16-split kernels with two groups per unit, automatic choice: two draws per workgroup (ssn_duo.hip, 3.4 ms at C3) when that
+// still gives every CU a workgroup, else one draw per workgroup (wide form, 5.3 ms at C3 but twice the workgroups)
+static bool duo_default(int B, int NB) { return units8(B, NB) > 256; }
 template <typename T>
 int solve_batch_impl(int variant, const T* W, const T* ext, int ext_per_draw, T* r, T* r_prev, int* codes,
                      int* steps, int B, int NB, int M, const ssn_solver_params* p, void* stream, bool dry_run = false) {
@@ -96,19 +100,18 @@ int solve_batch_impl(int variant, const T* W, const T* ext, int ext_per_draw, T*
     // enough (draw, 8 stimuli) workgroups to fill the chip -- 71 ms at the C2/NB=8 shape against 85-90 ms for the
     // split tile kernel (which runs one workgroup per (draw, stimulus) and so keeps small batches busier)
     if (variant < 0) {
-        const bool big = (long)B * ((NB + 7) / 8) >= 192 && M > 104;
-        // fp16-split forms: two draws per workgroup (8) once that still gives every CU a workgroup, else one (6)
-        const int split_variant = (long)B * ((NB + 7) / 8) > 256 ? 8 : 6;
+        const bool big = units8(B, NB) >= 192 && M > 104;
+        const int split_variant = duo_default(B, NB) ? 8 : 6;
         variant = (mfma_ok && big) ? ((split_ok && forward_split_default()) ? split_variant : 5) : (tile_ok ? 2 : (regw_ok ? 1 : 0));
     }
     if (dry_run) return variant;
+    a.split_form = variant == 7 ? 0 : ssn::gen_split_wide_parts();
     switch (variant) {
         case 2: SSN_TRY(ssn::launch_tile<T>(a, st, 0)); break;
         case 3: SSN_TRY(ssn::launch_tile<T>(a, st, 1)); break;
         case 4: SSN_TRY(ssn::launch_tile<T>(a, st, 2)); break;
         case 5: if constexpr (sizeof(T) == 4) { SSN_TRY(ssn::launch_solve_mfma(a, st)); } break;
-        case 6: if constexpr (sizeof(T) == 4) { SSN_TRY(ssn::launch_solve_split(a, st)); } break;
-        case 7: if constexpr (sizeof(T) == 4) { a.split_narrow = 1; SSN_TRY(ssn::launch_solve_split(a, st)); } break;
+        case 6: case 7: if constexpr (sizeof(T) == 4) { SSN_TRY(ssn::launch_solve_split(a, st)); } break;
         case 8: if constexpr (sizeof(T) == 4) { SSN_TRY(ssn::launch_solve_duo(a, st)); } break;
         case 1: SSN_TRY(ssn::launch_regw<T>(a, st)); break;
         default: SSN_TRY(ssn::launch_stream<T>(a, st)); break;
@@ -455,64 +458,93 @@ ssn::IoConsts<T> gen_io_consts(const ssn_gen_params& g) {
     return ssn::make_io_consts<T>(p);
 }
 
-// MFMA generator kernels: 0 = not used, else the number of 4-stimulus groups per workgroup.  kernel: 0 automatic
-// (two groups when that already gives >= 192 workgroups, one group when only that fills the chip -- 128 draws x 8
-// stimuli of the paper's runs -- else the tile kernels, which run one workgroup per (draw, stimulus)), 1 tile kernels,
-// 2 MFMA with two groups per workgroup, 3 MFMA with one group per workgroup.
-static int mfma_groups_for(int kernel, bool mfma_ok, int B, int NB) {
-    if (kernel == 2 || kernel == 4 || kernel == 6 || kernel == 8) return 2;
-    if (kernel == 3 || kernel == 5) return 1;
-    if (kernel != 0 || !mfma_ok) return 0;
-    if ((long)B * ((NB + 7) / 8) >= 192) return 2;
-    if ((long)B * ((NB + 3) / 4) >= 192) return 1;
-    return 0;
+// ---- the fixed-time generator: one choice of kernels ---------------------------------------------------------
+// gen_forward_path and gen_backward_path are the ONLY places that decide which kernels run a generator pass.  Both validate all
+// but the pointers, fill the arg struct and answer in the numbering of ssn_gen_forward_variant (1 tile / stream, 2 / 3 fp32 MFMA,
+// 4 - 7 fp16-split MFMA, 8 two draws per workgroup), or refuse: >= SSN_ERR_BASE with the error string set.
+int gen_refuse(const char* who, const char* why) { g_last_error = std::string(who) + ": " + why; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+const char* const kGenInvalid = "invalid argument, unsupported size or kernel not one of 0 (automatic), 1 (tile), 2 / 3 (fp32 MFMA), "
+                                "4 / 5 / 6 (fp16-split), 8 (two-draw)";
+const char* const kGenMfma = "the MFMA kernels need fp32, NB >= 4, 2N <= 208 and NB T 2N < 2^29";
+template <typename T>
+bool gen_call_ok(int M, const ssn_gen_params* g) {
+    return g && M > 0 && !(M & 1) && g->seqlen >= 1 && g->skip_steps >= 0 && g->skip_steps < g->seqlen && g->kernel >= 0 &&
+           g->kernel <= 8 && g->kernel != 7 && ssn::gen_supported<T>(M);
 }
-
-// automatic choice among the fp16-split forward kernels with two groups per unit: two draws per workgroup (ssn_duo.hip,
-// 3.4 ms at C3) when that still gives every CU a workgroup, else one draw per workgroup (wide form, 5.3 ms at C3 but
-// twice the workgroups)
-static bool duo_default(int groups, int B, int NB) { return groups == 2 && (long)B * ((NB + 7) / 8) > 256; }
+template <typename T, typename Args>   // what GenFwdArgs and GenBwdArgs take from the call's shape and parameters
+void gen_fill(Args& a, int B, int NB, int M, const ssn_gen_params& g) {
+    a.B = B; a.NB = NB; a.M = M; a.seqlen = g.seqlen; a.skip = g.skip_steps;
+    a.eps_E = (T)(g.dt / g.tau_E); a.eps_I = (T)(g.dt / g.tau_I); a.theta = (T)g.rate_penalty_threshold;
+}
+// 4-stimulus groups per workgroup of a matrix-core launch: what the code names, or for 0 what fills the chip -- two when that
+// already gives >= 192 workgroups, one when only that does (128 draws x 8 stimuli of the paper's runs), else 0: the tile
+// kernels, which run one workgroup per (draw, stimulus)
+int gen_groups(int kernel, int B, int NB) {
+    if (kernel) return kernel == 1 ? 0 : (kernel == 3 || kernel == 5 ? 1 : 2);
+    return units8(B, NB) >= 192 ? 2 : ((long)B * ((NB + 3) / 4) >= 192 ? 1 : 0);
+}
+// save: the call stores trajectory and f' (their stores address one draw's block with 32-bit byte offsets)
+template <typename T>
+int gen_forward_path(ssn::GenFwdArgs<T>& a, int B, int NB, int M, bool save, const ssn_gen_params* g) {
+    if (!gen_call_ok<T>(M, g) || g->io_type < 0 || g->io_type > 2) return gen_refuse("ssn_gen_forward", kGenInvalid);
+    gen_fill<T>(a, B, NB, M, *g);
+    a.io = gen_io_consts<T>(*g);
+    if constexpr (sizeof(T) == 4) {
+        const int k = g->kernel;
+        const bool mfma_ok = ssn::gen_mfma_supported(M, NB) && (!save || (long)NB * g->seqlen * M < (1L << 29));
+        const bool split_ok = mfma_ok && ssn::gen_split_rshift(a) >= 0;
+        if (k >= 2 && !mfma_ok) return gen_refuse("ssn_gen_forward", kGenMfma);
+        if (k >= 4 && !split_ok)
+            return gen_refuse("ssn_gen_forward", "the fp16-split MFMA kernels need asym_tanh, rate_hard_bound < 3e4 and dt <= tau");
+        const int groups = mfma_ok ? gen_groups(k, B, NB) : 0;
+        if (!groups) return 1;
+        a.mfma_groups = groups;
+        if (k == 2 || k == 3 || (k == 0 && !(split_ok && forward_split_default()))) return groups == 2 ? 2 : 3;
+        if (groups == 1) return 5;
+        if (k == 8 || (k == 0 && duo_default(B, NB))) return 8;
+        a.split_form = k == 6 ? 0 : ssn::gen_split_wide_parts();
+        return a.split_form == 0 ? 6 : (a.split_form == 3 ? 7 : 4);
+    }
+    return 1;
+}
+// NOT the forward's rule: the fp16-split sweep (one form: code 6 runs 4) and the two-draw sweep scale by the data, not by a rate
+// bound, so they take any I/O function -- with asym_power under the default operand precision the automatic adjoint is the
+// split or two-draw sweep behind an fp32 MFMA forward.
+template <typename T>
+int gen_backward_path(ssn::GenBwdArgs<T>& a, int B, int NB, int M, const ssn_gen_params* g) {
+    if (!gen_call_ok<T>(M, g)) return gen_refuse("ssn_gen_backward", kGenInvalid);
+    gen_fill<T>(a, B, NB, M, *g);
+    if constexpr (sizeof(T) == 4) {
+        const int k = g->kernel;
+        const bool mfma_ok = ssn::gen_mfma_supported(M, NB) && (long)NB * g->seqlen * M < (1L << 29);
+        if (k >= 2 && !mfma_ok) return gen_refuse("ssn_gen_backward", kGenMfma);
+        const int groups = mfma_ok ? gen_groups(k, B, NB) : 0;
+        if (!groups) return 1;
+        a.mfma_groups = groups;
+        if (k == 2 || k == 3 || (k == 0 && !forward_split_default())) return groups == 2 ? 2 : 3;
+        if (k == 8 || (k == 0 && duo_default(B, NB))) return 8;
+        return groups == 2 ? 4 : 5;
+    }
+    return 1;
+}
 
 template <typename T>
 int gen_forward_impl(const T* W, const T* ext, T* time_avg, T* dyn_row, T* rate_row, T* traj, T* df, int B, int NB,
                      int M, const ssn_gen_params* g, void* stream) {
     if (B == 0 || NB == 0) return 0;
-    if (!g || !W || !ext || !time_avg || !dyn_row || !rate_row || (traj == nullptr) != (df == nullptr) || M <= 0 ||
-        (M & 1) || g->seqlen < 1 || g->skip_steps < 0 || g->skip_steps >= g->seqlen || g->io_type < 0 || g->io_type > 2 ||
-        !ssn::gen_supported<T>(M)) {
-        g_last_error = "ssn_gen_forward: invalid argument or unsupported size";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
+    if (!W || !ext || !time_avg || !dyn_row || !rate_row || (traj == nullptr) != (df == nullptr))
+        return gen_refuse("ssn_gen_forward", kGenInvalid);
     ssn::GenFwdArgs<T> a;
     a.W = W; a.ext = ext; a.time_avg = time_avg; a.dyn_row = dyn_row; a.rate_row = rate_row; a.traj = traj; a.df = df;
-    a.B = B; a.NB = NB; a.M = M; a.seqlen = g->seqlen; a.skip = g->skip_steps;
-    a.eps_E = (T)(g->dt / g->tau_E); a.eps_I = (T)(g->dt / g->tau_I); a.theta = (T)g->rate_penalty_threshold;
-    a.io = gen_io_consts<T>(*g);
-    if constexpr (sizeof(T) == 4) {
-        // (trajectory stores address one draw's block with 32-bit byte offsets)
-        const bool mfma_ok = ssn::gen_mfma_supported(M, NB) && (!traj || (long)NB * g->seqlen * M < (1L << 29));
-        if (g->kernel >= 2 && g->kernel <= 8 && (!mfma_ok || g->kernel == 7)) {
-            g_last_error = "ssn_gen_forward: the MFMA kernels need fp32, NB >= 4 and 2N <= 208";
-            return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-        }
-        const bool split_ok = mfma_ok && ssn::gen_split_rshift(a) >= 0;
-        if (g->kernel >= 4 && g->kernel <= 8 && !split_ok) {
-            g_last_error = "ssn_gen_forward: the fp16-split MFMA kernel needs the saturating I/O function (asym_tanh), "
-                           "rate_hard_bound < 3e4 and dt <= tau";
-            return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-        }
-        if (const int groups = mfma_groups_for(g->kernel, mfma_ok, B, NB)) {
-            a.mfma_groups = groups;
-            a.split_narrow = g->kernel == 6;
-            const bool split = g->kernel >= 4 || (g->kernel == 0 && split_ok && forward_split_default());
-            if (g->kernel == 8 || (g->kernel == 0 && split && duo_default(groups, B, NB)))
-                SSN_TRY(ssn::launch_gen_forward_duo(a, (hipStream_t)stream));
-            else if (split) SSN_TRY(ssn::launch_gen_forward_split(a, (hipStream_t)stream));
-            else SSN_TRY(ssn::launch_gen_forward_mfma(a, (hipStream_t)stream));
-            return 0;
-        }
+    const int variant = gen_forward_path(a, B, NB, M, traj != nullptr, g);
+    if (variant >= SSN_ERR_BASE) return variant;
+    hipStream_t st = (hipStream_t)stream;
+    if constexpr (sizeof(T) == 4) switch (variant) {
+        case 2: case 3: SSN_TRY(ssn::launch_gen_forward_mfma(a, st)); return 0;
+        case 4: case 5: case 6: case 7: SSN_TRY(ssn::launch_gen_forward_split(a, st)); return 0;
+        case 8: SSN_TRY(ssn::launch_gen_forward_duo(a, st)); return 0;
     }
-    SSN_TRY(ssn::launch_gen_forward<T>(a, (hipStream_t)stream));
+    SSN_TRY(ssn::launch_gen_forward<T>(a, st));
     return 0;
 }
 
@@ -521,47 +553,25 @@ int gen_backward_impl(const T* W, const T* traj, T* delta, const T* gta, T* g_ex
                       int NB, int M, const ssn_gen_params* g, void* stream, float* dmax = nullptr, int* tracked = nullptr) {
     if (tracked) *tracked = 0;
     if (B == 0 || NB == 0) return 0;
-    if (!g || !W || !traj || !delta || !gta || M <= 0 || (M & 1) || g->seqlen < 1 || g->skip_steps < 0 ||
-        g->skip_steps >= g->seqlen || !ssn::gen_supported<T>(M)) {
-        g_last_error = "ssn_gen_backward: invalid argument or unsupported size";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
+    if (!W || !traj || !delta || !gta) return gen_refuse("ssn_gen_backward", kGenInvalid);
     ssn::GenBwdArgs<T> a;
-    a.W = W; a.traj = traj; a.delta = delta; a.g_time_avg = gta; a.g_ext = g_ext;
-    a.B = B; a.NB = NB; a.M = M; a.seqlen = g->seqlen; a.skip = g->skip_steps;
-    a.eps_E = (T)(g->dt / g->tau_E); a.eps_I = (T)(g->dt / g->tau_I); a.theta = (T)g->rate_penalty_threshold;
-    a.c_dyn = (T)c_dyn; a.c_rate = (T)c_rate;
+    a.W = W; a.traj = traj; a.delta = delta; a.g_time_avg = gta; a.g_ext = g_ext; a.c_dyn = (T)c_dyn; a.c_rate = (T)c_rate;
+    const int variant = gen_backward_path(a, B, NB, M, g);
+    if (variant >= SSN_ERR_BASE) return variant;
+    hipStream_t st = (hipStream_t)stream;
     if constexpr (sizeof(T) == 4) {
-        const bool mfma_ok = ssn::gen_mfma_supported(M, NB) && (long)NB * g->seqlen * M < (1L << 29);
-        if (g->kernel >= 2 && g->kernel <= 8 && !mfma_ok) {
-            g_last_error = "ssn_gen_backward: the MFMA kernel needs fp32, NB >= 4 and 2N <= 208";
-            return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+        if (variant >= 4 && dmax && tracked) {       // max |delta| per draw for ssn_weight_grad_scaled_f32 (atomic max of bit
+            SSN_TRY(hipMemsetAsync(dmax, 0, sizeof(float) * (size_t)B, st));   // patterns): the fp16-split sweeps keep it for
+            a.dmax = reinterpret_cast<unsigned*>(dmax);                         // their own scaling
+            *tracked = 1;
         }
-        if (const int groups = mfma_groups_for(g->kernel, mfma_ok, B, NB)) {
-            a.mfma_groups = groups;
-            const bool split_ok = ssn::gen_split_backward_supported(M, NB);
-            a.split_narrow = g->kernel == 6;
-            const bool split = split_ok && (g->kernel >= 4 || (g->kernel == 0 && forward_split_default()));
-            if (split_ok && (g->kernel == 8 || (g->kernel == 0 && forward_split_default() && duo_default(groups, B, NB)))) {
-                if (dmax && tracked) {                  // max |delta| per draw for ssn_weight_grad_scaled_f32 (atomic max of bit patterns)
-                    SSN_TRY(hipMemsetAsync(dmax, 0, sizeof(float) * (size_t)B, (hipStream_t)stream));
-                    a.dmax = reinterpret_cast<unsigned*>(dmax);
-                    *tracked = 1;
-                }
-                SSN_TRY(ssn::launch_gen_backward_duo(a, (hipStream_t)stream));
-            } else if (split) {
-                if (dmax && tracked) {                  // (the alternating split sweep keeps the same per-step maxima)
-                    SSN_TRY(hipMemsetAsync(dmax, 0, sizeof(float) * (size_t)B, (hipStream_t)stream));
-                    a.dmax = reinterpret_cast<unsigned*>(dmax);
-                    *tracked = 1;
-                }
-                SSN_TRY(ssn::launch_gen_backward_split(a, (hipStream_t)stream));
-            }
-            else SSN_TRY(ssn::launch_gen_backward_mfma(a, (hipStream_t)stream));
-            return 0;
+        switch (variant) {
+            case 2: case 3: SSN_TRY(ssn::launch_gen_backward_mfma(a, st)); return 0;
+            case 4: case 5: SSN_TRY(ssn::launch_gen_backward_split(a, st)); return 0;
+            case 8: SSN_TRY(ssn::launch_gen_backward_duo(a, st)); return 0;
         }
     }
-    SSN_TRY(ssn::launch_gen_backward<T>(a, (hipStream_t)stream));
+    SSN_TRY(ssn::launch_gen_backward<T>(a, st));
     return 0;
 }
 
@@ -1181,22 +1191,12 @@ int ssn_solve_batch_variant_for(int B, int NB, int M, int dtype_bytes, const ssn
 }
 
 int ssn_gen_forward_variant(int B, int NB, int M, int seqlen, int save, const ssn_gen_params* g) {
-    if (!g || B <= 0 || NB <= 0 || M <= 0 || (M & 1) || !ssn::gen_supported<float>(M)) return -1;
+    if (!g || B <= 0 || NB <= 0) return -1;
+    ssn_gen_params p = *g;
+    p.seqlen = seqlen;
     ssn::GenFwdArgs<float> a{};
-    a.B = B; a.NB = NB; a.M = M; a.seqlen = seqlen;
-    a.eps_E = (float)(g->dt / g->tau_E); a.eps_I = (float)(g->dt / g->tau_I);
-    a.io = gen_io_consts<float>(*g);
-    const bool mfma_ok = ssn::gen_mfma_supported(M, NB) && (!save || (long)NB * seqlen * M < (1L << 29));
-    const bool split_ok = mfma_ok && ssn::gen_split_rshift(a) >= 0;
-    if ((g->kernel >= 2 && g->kernel <= 8 && !mfma_ok) || (g->kernel >= 4 && !split_ok) || g->kernel == 7) return -1;
-    const int groups = mfma_groups_for(g->kernel, mfma_ok, B, NB);
-    if (!groups) return 1;
-    if (g->kernel == 8) return 8;
-    const bool split = g->kernel >= 4 || (g->kernel == 0 && split_ok && forward_split_default());
-    if (g->kernel == 0 && split && duo_default(groups, B, NB)) return 8;
-    if (split && groups == 2 && (g->kernel == 6 || ssn::gen_split_wide_parts() == 0)) return 6;
-    if (split && groups == 2 && ssn::gen_split_wide_parts() == 3) return 7;
-    return (split ? 4 : 2) + (groups == 1 ? 1 : 0);
+    const int v = gen_forward_path(a, B, NB, M, save != 0, &p);
+    return v >= SSN_ERR_BASE ? -1 : v;
 }
 
 int ssn_gen_supported(int M, int dtype_bytes) {
@@ -1235,8 +1235,8 @@ int ssn_gen_backward_max_f32(const float* W, const float* traj, float* df_delta,
 }
 int ssn_gen_backward_fused_supported(int B, int NB, int M, const ssn_gen_params* p, float xmax) {
     if (!p) return 0;
-    ssn::GenBwdArgs<float> a;
-    a.B = B; a.NB = NB; a.M = M; a.seqlen = p->seqlen; a.skip = p->skip_steps;
+    ssn::GenBwdArgs<float> a{};
+    gen_fill<float>(a, B, NB, M, *p);
     return p->skip_steps >= 0 && p->skip_steps < p->seqlen && (long)NB * p->seqlen * M < (1L << 29) &&
            ssn::gen_backward_fused_supported(a, xmax);
 }
@@ -1251,9 +1251,8 @@ int ssn_gen_backward_fused_f32(const float* W, const float* traj, const float* d
     }
     ssn::GenBwdArgs<float> a;
     a.W = W; a.traj = traj; a.delta = const_cast<float*>(df); a.g_time_avg = g_time_avg; a.g_ext = g_ext;
-    a.B = B; a.NB = NB; a.M = M; a.seqlen = p->seqlen; a.skip = p->skip_steps;
-    a.eps_E = (float)(p->dt / p->tau_E); a.eps_I = (float)(p->dt / p->tau_I); a.theta = (float)p->rate_penalty_threshold;
     a.c_dyn = (float)c_dyn; a.c_rate = (float)c_rate;
+    gen_fill<float>(a, B, NB, M, *p);
     if (dmax) {
         SSN_TRY(hipMemsetAsync(dmax, 0, sizeof(float) * (size_t)B, (hipStream_t)stream));
         a.dmax = reinterpret_cast<unsigned*>(dmax);

@@ -1173,7 +1173,7 @@ static hipError_t launch_duo_bwd_mk(const GenBwdArgs<float>& a, hipStream_t st) 
     else hipLaunchKernelGGL((gen_backward_duo_kernel<MK, false>), grid, dim3(512), 0, st, a);
     return hipGetLastError();
 }
-// applicability: gen_split_backward_supported (any I/O function: the scale follows the data)
+// applicability: gen_mfma_supported (any I/O function: the scale follows the data)
 hipError_t launch_gen_backward_duo(const GenBwdArgs<float>& a, hipStream_t st) {
     switch (duo_pick_mk(a.M)) {
         case 104: return launch_duo_bwd_mk<104>(a, st);

@@ -17,7 +17,7 @@ struct SolveArgs {
     int B, NB, M, N;
     IoConsts<T> io;
     StepConsts<T> st;
-    int split_narrow = 0;   // fp16-split solver: 1 = alternating two-group form (state as three parts) instead of the wide form
+    int split_form = 2;     // fp16-split solver: 2 = wide form, 0 = alternating two-group form (as GenFwdArgs::split_form)
 };
 
 // Fixed-time generator forward (ssn_gen.hip)
@@ -34,8 +34,8 @@ struct GenFwdArgs {
     T eps_E, eps_I, theta;
     IoConsts<T> io;
     int mfma_groups = 2;   // MFMA kernels: stimulus groups of 4 per workgroup (2, or 1 to spread few draws over the chip)
-    int split_narrow = 0;  // fp16-split forward with two groups: 1 = the alternating two-group form (state as three parts,
-                           // exact) instead of the wide form (all 8 stimuli in one chain, state as two parts)
+    int split_form = 2;    // fp16-split forward with two groups: 2 / 3 = the wide form (all 8 stimuli in one chain) with the state as
+                           // that many fp16 parts, 0 = the alternating two-group form (state as three parts, exact)
 };
 // BPTT adjoint sweep (ssn_gen.hip)
 template <typename T>
@@ -48,7 +48,6 @@ struct GenBwdArgs {
     int B, NB, M, seqlen, skip;
     T eps_E, eps_I, theta, c_dyn, c_rate;
     int mfma_groups = 2;
-    int split_narrow = 0;  // as GenFwdArgs::split_narrow
     unsigned* dmax = nullptr;   // [B] or nullptr: atomic max of the bit patterns of |delta| the sweep stores for draw b (zeroed by
                                 // the caller; the fp16-split sweeps of ssn_duo.hip / ssn_mfma16.hip only -- they track it for their own scaling)
 };
@@ -154,8 +153,7 @@ hipError_t launch_gen_forward_mfma(const GenFwdArgs<float>& a, hipStream_t st);
 // ssn_mfma16.hip: fp16-split matrix-core forward; gen_split_rshift < 0: not applicable (I/O function without a rate bound, sizes)
 int gen_split_rshift(const GenFwdArgs<float>& a);
 hipError_t launch_gen_forward_split(const GenFwdArgs<float>& a, hipStream_t st);
-int gen_split_wide_parts();   // two-group launches: 2 / 3 = wide form with that many state parts, 0 = alternating form
-bool gen_split_backward_supported(int M, int NB);
+int gen_split_wide_parts();   // SSN_FWD_WIDE: the split_form of a two-group launch that names none (read by ssn_capi.hip alone)
 bool solve_split_supported(const SolveArgs<float>& a);
 hipError_t launch_solve_split(const SolveArgs<float>& a, hipStream_t st);
 hipError_t launch_gen_backward_split(const GenBwdArgs<float>& a, hipStream_t st);

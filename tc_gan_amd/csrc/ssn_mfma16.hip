@@ -1430,8 +1430,8 @@ int gen_split_rshift(const GenFwdArgs<float>& a) {
     return sh;
 }
 
-// two-group launches: 2 = wide form with the state as two fp16 parts (default), 3 = wide form with three (exact state,
-// three MFMAs per tile: no faster than the alternating form), 0 = alternating two-group form; SSN_FWD_WIDE overrides
+// split_form of two-group launches: 2 = wide form with the state as two fp16 parts (default), 3 = wide form with three (exact
+// state, three MFMAs per tile: no faster than the alternating form), 0 = alternating two-group form; SSN_FWD_WIDE overrides
 int gen_split_wide_parts() {
     static const int rp = [] { const char* e = getenv("SSN_FWD_WIDE"); return (e && (e[0] == '0' || e[0] == '2' || e[0] == '3')) ? e[0] - '0' : 2; }();
     return rp;
@@ -1439,8 +1439,8 @@ int gen_split_wide_parts() {
 template <int MK>
 static hipError_t launch_split_mk(const GenFwdArgs<float>& a, int rshift, hipStream_t st) {
     const int ngroups = (a.NB + 4 * a.mfma_groups - 1) / (4 * a.mfma_groups);
-    if (a.mfma_groups == 2 && !a.split_narrow && gen_split_wide_parts()) {
-        const bool three = gen_split_wide_parts() == 3;
+    if (a.mfma_groups == 2 && a.split_form) {
+        const bool three = a.split_form == 3;
         if (a.traj) {
             if (three) hipLaunchKernelGGL((gen_forward_wide_kernel<MK, true, 3>), dim3(a.B * ngroups), dim3(512), 0, st, a, rshift);
             else hipLaunchKernelGGL((gen_forward_wide_kernel<MK, true, 2>), dim3(a.B * ngroups), dim3(512), 0, st, a, rshift);
@@ -1471,7 +1471,7 @@ bool solve_split_supported(const SolveArgs<float>& a) {
 }
 template <int MK>
 static hipError_t launch_solve_split_mk(const SolveArgs<float>& a, hipStream_t st) {
-    if (gen_split_wide_parts() && !a.split_narrow) hipLaunchKernelGGL((solve_wide_kernel<MK>), dim3(a.B * ((a.NB + 7) / 8)), dim3(512), 0, st, a);
+    if (a.split_form) hipLaunchKernelGGL((solve_wide_kernel<MK>), dim3(a.B * ((a.NB + 7) / 8)), dim3(512), 0, st, a);
     else hipLaunchKernelGGL((solve_split_kernel<MK>), dim3(a.B * ((a.NB + 7) / 8)), dim3(512), 0, st, a);
     return hipGetLastError();
 }
@@ -1484,8 +1484,6 @@ hipError_t launch_solve_split(const SolveArgs<float>& a, hipStream_t st) {
         default: return hipErrorInvalidValue;
     }
 }
-
-bool gen_split_backward_supported(int M, int NB) { return !(M & 1) && NB >= 4 && split_pick_mk(M) != 0; }
 
 template <int MK>
 static hipError_t launch_split_bwd_mk(const GenBwdArgs<float>& a, hipStream_t st) {

@@ -23,15 +23,18 @@ def make_gen_params(io_type='asym_tanh', k=0.01, n=2.2, tau_E=10., tau_I=1., dt=
                     skip_steps=1000, rate_soft_bound=200., rate_hard_bound=1000.,
                     rate_penalty_threshold=200., kernel=0):
     """Defaults: networks/wgan.py:39-63 (tau_E=10, tau_I=1, dt=0.1, seqlen=1200, skip_steps=1000).
-    kernel: 0 library default (MFMA kernels for fp32 with NB >= 4 and enough draws, VALU tile kernels otherwise),
-    1 tile, 2 fp32 MFMA (two 4-stimulus groups per workgroup), 3 fp32 MFMA (one group per workgroup), 4 / 5 forward on
-    the fp16-split MFMA kernel (asym_tanh only; the default where it applies unless SSN_FWD_SPLIT=0) and adjoint sweep
-    on its fp16-split form (any I/O function)."""
+    kernel: a code of `clib.GEN_KERNELS`; 0 leaves the choice to the library."""
     return clib.GenParams(io_type=clib.IO_CODES[io_type], seqlen=int(seqlen), skip_steps=int(skip_steps),
                           kernel=int(kernel), k=float(k), n=float(n), tau_E=float(tau_E), tau_I=float(tau_I),
                           dt=float(dt), rate_soft_bound=float(rate_soft_bound),
                           rate_hard_bound=float(rate_hard_bound),
                           rate_penalty_threshold=float(rate_penalty_threshold))
+
+
+def gen_params_of(cfg, kernel=0, **kw):
+    """`make_gen_params` from a config -- a mapping with io_type, k, n, tau_E, tau_I, dt, seqlen, skip_steps -- and a kernel code."""
+    keys = ('io_type', 'k', 'n', 'tau_E', 'tau_I', 'dt', 'seqlen', 'skip_steps')
+    return make_gen_params(kernel=kernel, **{key: cfg[key] for key in keys}, **kw)
 
 
 _PEN_SCRATCH = {}
@@ -50,9 +53,20 @@ def _penalty_scratch(device):
 
 
 def forward_variant(B, NB, M, gp, save=False):
-    """The fp32 forward kernel `gen_forward` runs for this shape (``ssn_gen_forward_variant``: 1 VALU, 2 / 3 fp32 MFMA,
-    4 / 5 fp16-split MFMA, -1 refused)."""
+    """The fp32 forward kernel `gen_forward` runs for this shape: the launch's own decision (``ssn_gen_forward_variant``:
+    1 VALU, 2 / 3 fp32 MFMA, 4 - 8 fp16-split MFMA, -1 refused)."""
     return int(libssnode.ssn_gen_forward_variant(int(B), int(NB), int(M), int(gp.seqlen), int(bool(save)), ctypes.byref(gp)))
+
+
+def resolve_kernel(B, NB, M, gp, save=False):
+    """The explicit name (`clib.GEN_KERNELS`) of the fp32 forward kernel the library runs for this shape: the one `gp.kernel`
+    names, or for 0 the one the library picks.  ValueError when it refuses the call or the pick has no name."""
+    variant = forward_variant(B, NB, M, gp, save=save)
+    name = clib.GEN_KERNEL_NAMES.get(gp.kernel or variant)
+    if variant < 0 or name is None:
+        raise ValueError('generator kernel {!r} has no form for {} draws of {} stimuli, num_sites = {}, io_type code {} (variant {})'
+                         .format(clib.GEN_KERNEL_NAMES.get(gp.kernel, gp.kernel), B, NB, M // 2, gp.io_type, variant))
+    return name
 
 
 def gen_forward(W, ext, gp, save=False, probe=None):

@@ -44,9 +44,6 @@ SHARED_KEYS = frozenset([
     'skip_steps', 'io_type', 'k', 'n', 'tau_E', 'tau_I', 'dt', 'ssn_type', 'dist_in', 'rate_penalty_threshold', 'update_name',
     'gen_kernel', 'iterations'])
 
-#: forward variant (`ssn_gen_forward_variant`) -> the explicit kernel name that runs it
-_VARIANT_KERNELS = {1: 'tile', 2: 'mfma-fp32', 3: 'mfma-fp32-1g', 4: 'split-wide', 5: 'split-1g', 6: 'split-alt', 8: 'duo'}
-
 
 class MemberOptionError(ValueError):
     pass
@@ -72,12 +69,6 @@ def validate_member_overrides(member_overrides):
     return [dict(over) for over in member_overrides]
 
 
-def _gen_params_of(config, kernel):
-    kw = dict(DEFAULT_PARAMS, **config)
-    return genops.make_gen_params(io_type=kw['io_type'], k=kw['k'], n=kw['n'], tau_E=kw['tau_E'], tau_I=kw['tau_I'], dt=kw['dt'],
-                                  seqlen=kw['seqlen'], skip_steps=kw['skip_steps'], kernel=kernel)
-
-
 def resolve_gen_kernel(config, num_members):
     """The explicit kernel name the ensemble runs: `gen_kernel` as given, or for 'auto' the family the library picks for the
     ensemble's batch of num_members x batchsize draws (host arithmetic only, `ssn_gen_forward_variant`)."""
@@ -89,13 +80,9 @@ def resolve_gen_kernel(config, num_members):
         return name
     if config.get('gen_dtype', 'float32') != 'float32':
         raise ValueError('ensembles run the float32 generator only')
-    num_sites = int(config['num_sites'])
     nb = len(config['bandwidths']) * len(config['contrasts'])
-    B = int(config['batchsize']) * int(num_members)
-    variant = genops.forward_variant(B, nb, 2 * num_sites, _gen_params_of(config, 0), save=True)
-    if variant not in _VARIANT_KERNELS:
-        raise ValueError('no generator kernel for {} draws of num_sites={} (variant {})'.format(B, num_sites, variant))
-    return _VARIANT_KERNELS[variant]
+    return genops.resolve_kernel(int(config['batchsize']) * int(num_members), nb, 2 * int(config['num_sites']),
+                                 genops.gen_params_of(dict(DEFAULT_PARAMS, **config)), save=True)
 
 
 def member_config(shared_config, override):

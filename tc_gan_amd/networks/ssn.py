@@ -388,7 +388,7 @@ class TuningCurveGenerator(object):
 
     @property
     def gen_kernel(self):
-        return next(name for name, code in clib.GEN_KERNELS.items() if code == self.kernel)
+        return clib.GEN_KERNEL_NAMES[self.kernel]
 
     def forward_variant(self, num_models=None, save=False):
         """The forward kernel a call with `num_models` draws runs (`ssn_gen_forward_variant`; fp32 only, else 1)."""
@@ -398,10 +398,8 @@ class TuningCurveGenerator(object):
                                       self.num_neurons, self.gen_params(), save=save)
 
     def gen_params(self, rate_penalty_threshold=200.0):
-        return genops.make_gen_params(io_type=self.io_type, k=self.k, n=self.n, tau_E=self.tau_E, tau_I=self.tau_I,
-                                      dt=self.dt, seqlen=self.seqlen, skip_steps=self.skip_steps,
-                                      rate_penalty_threshold=rate_penalty_threshold,
-                                      kernel=8 if self.fused_backward else self.kernel)
+        return genops.gen_params_of(vars(self), 8 if self.fused_backward else self.kernel,
+                                    rate_penalty_threshold=rate_penalty_threshold)
 
     # -- noise -----------------------------------------------------------------------------
     def gen_noise(self, rng, stimulator_bandwidths, rows=None, keep_z=None, **_):
@@ -634,9 +632,7 @@ class TuningCurveGenerator(object):
             full = (sv['shape'], sv['n_dyn'], sv['n_rate'])
             if subset is not None:
                 sv = dict(sv, **{k: sv[k][subset].contiguous() for k in ('W', 'z', 'zin', 'ext_base', 'ext') if sv[k] is not None})
-            gp = genops.make_gen_params(io_type=self.io_type, k=self.k, n=self.n, tau_E=self.tau_E, tau_I=self.tau_I, dt=self.dt,
-                                        seqlen=self.seqlen, skip_steps=self.skip_steps, rate_penalty_threshold=sv['theta'],
-                                        kernel=clib.GEN_KERNELS['mfma-fp32'])
+            gp = genops.gen_params_of(vars(self), clib.GEN_KERNELS['mfma-fp32'], rate_penalty_threshold=sv['theta'])
             # (trajectory and f' are all the sweep needs of it: no probe gather)
             sv = dict(sv, gp=gp, fwd=genops.gen_forward(sv['W'], sv['ext'], gp, save=True))
         fwd = sv['fwd']

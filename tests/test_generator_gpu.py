@@ -390,6 +390,62 @@ def test_two_draw_adjoint_hands_over_max_delta(io_type, bwd_kernel):
     assert res[1] is None
 
 
+# the explicit code whose sweep the automatic adjoint runs with asym_power under the default operand precision: the fp16-split and
+# two-draw sweeps take any I/O function, so it is NOT the forward's variant there (fp32 MFMA) -- DESIGN.md 3.5a
+_ADJOINT_OF_POWER = {3: 1, 100: 5, 200: 4, 300: 8}
+
+
+@pytest.mark.parametrize('precision', ['split', 'fp32'])
+@pytest.mark.parametrize('io_type', ['asym_tanh', 'asym_power'])
+@pytest.mark.parametrize('B', [3, 100, 200, 300])       # automatic choice: tile, one group, two groups, two draws per workgroup
+def test_automatic_choice_is_the_explicit_kernel_it_names(B, io_type, precision):
+    """kernel 0 runs, bit for bit, the kernel `forward_variant` names (forward) and the one the adjoint rule names (backward,
+    `dmax` tracked or not included)."""
+    from tc_gan_amd import clib, genops, stimuli, weight_gen
+    N, NB, T, skip = 10, 8, 20, 10
+    jds, z, bws, con = _problem(N, B, NB, 17, T, skip, 1.0)
+    W = weight_gen.generate_weight_batch(N, jds['J'], jds['D'], jds['S'], z, dtype='float32')
+    ext = stimuli.stimulus_batch(bws, con, P['smoothness'], N, dtype='float32')
+    gta = torch.as_tensor(np.random.RandomState(B).randn(B, NB, 2 * N), device='cuda', dtype=torch.float32)
+
+    def params(kernel):
+        return genops.make_gen_params(seqlen=T, skip_steps=skip, rate_penalty_threshold=1.0, kernel=kernel, **dict(GEN, io_type=io_type))
+    before = clib.set_operand_precision(precision)
+    try:
+        v = genops.forward_variant(B, NB, 2 * N, params(0), save=True)
+        assert v == ({3: 1, 100: 5, 200: 4, 300: 8} if (io_type, precision) == ('asym_tanh', 'split') else
+                     {3: 1, 100: 3, 200: 2, 300: 2})[B]
+        fwd = {k: genops.gen_forward(W, ext, params(k), save=True) for k in (0, v)}
+        for key in ('time_avg', 'penalties', 'traj', 'df'):
+            assert torch.equal(fwd[0][key], fwd[v][key]), key
+        bwd_code = _ADJOINT_OF_POWER[B] if (io_type, precision) == ('asym_power', 'split') else v
+        bwd = {k: genops.gen_backward(W, fwd[0]['traj'], fwd[0]['df'].clone(), gta, 1e-3, 1e-3, params(k), want_g_ext=True,
+                                      want_dmax=True) for k in (0, bwd_code)}
+    finally:
+        clib.set_operand_precision(before)
+    assert (bwd[0][2] is None) == (bwd[bwd_code][2] is None) == (bwd_code < 4)
+    for got, want in zip(bwd[0], bwd[bwd_code]):
+        assert got is want is None or torch.equal(got, want)
+
+
+def test_codes_that_name_no_kernel_and_empty_horizons_are_refused():
+    from tc_gan_amd import clib, genops, stimuli, weight_gen
+    N, B, NB, T, skip = 10, 3, 8, 20, 10
+    jds, z, bws, con = _problem(N, B, NB, 17, T, skip, 1.0)
+    W = weight_gen.generate_weight_batch(N, jds['J'], jds['D'], jds['S'], z, dtype='float32')
+    ext = stimuli.stimulus_batch(bws, con, P['smoothness'], N, dtype='float32')
+    gp = genops.make_gen_params(seqlen=T, skip_steps=skip, **GEN)
+    out = genops.gen_forward(W, ext, gp, save=True)
+    for code in (7, 9, -1):
+        gp.kernel = code
+        with pytest.raises(clib.SSNLibraryError):
+            genops.gen_forward(W, ext, gp)
+        with pytest.raises(clib.SSNLibraryError):
+            genops.gen_backward(W, out['traj'], out['df'], torch.zeros_like(out['time_avg']), 0.0, 0.0, gp)
+    with pytest.raises(clib.SSNLibraryError):
+        genops.gen_forward(W, ext, genops.make_gen_params(seqlen=0, skip_steps=0, **GEN))
+
+
 def test_split_kernel_refuses_unbounded_io_functions():
     """The fp16-split kernel scales the state by the rate bound of asym_tanh; asked for explicitly with another I/O
     function it must fail, not overflow."""
