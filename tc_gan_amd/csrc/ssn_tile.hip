@@ -36,6 +36,16 @@
 #ifndef SSN_TILE_MIXED
 #define SSN_TILE_MIXED 1
 #endif
+// diagnostic switches for the step loop of the fp32 NB = 1 kernels (A/B builds; 1 = product setting):
+// SSN_TILE_LOOP: the loop rotated by half a step so that one test of the verdict word ends it; the flag slots are rotating
+//                LDS addresses and the state buffer a toggled offset (no step % 3, no frozen / code / nsteps bookkeeping)
+// SSN_TILE_EXEC: no exec-mask regions around the state store, the flag stores and the flag clear
+#ifndef SSN_TILE_LOOP
+#define SSN_TILE_LOOP 1
+#endif
+#ifndef SSN_TILE_EXEC
+#define SSN_TILE_EXEC 1
+#endif
 
 namespace ssn {
 
@@ -60,13 +70,23 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     // ---- prologue: my RA x C tile of W -> registers (and LDS for the last RL rows) -----------------
     constexpr bool SPLIT = RL > 0 || PK;        // SplitTile: packed row pairs in VGPRs (+ RL rows in LDS)
     T w[!SPLIT ? RA : 1][!SPLIT ? C : 1];       // plain all-register shape
+    // the FMA block of the solver (SplitTile::matvec's MODE): SSN_TILE_FMA bit 0 asks for the one-statement form in the light
+    // wave of the mixed kernel (all rows packed, none in LDS), bit 2 in the waves with LDS-resident rows
+    constexpr int FMA_MODE = (SSN_TILE_FMA & 2) | ((SSN_TILE_FMA >> ((PK && RL == 0) ? 0 : 2)) & 1);
     SplitTile<T, RA, C, RL> sw;
     if constexpr (SPLIT) sw.template load<false>(a.W + (size_t)b * M * M, M, rowbase, colbase, wlds, threadIdx.x);
     else tile_load<T, RA, C, false>(a.W + (size_t)b * M * M, M, rowbase, colbase, w);
+    // fp32, NB = 1: the step loop below without the NB-generic bookkeeping (LOOP1) and without exec-mask regions (FLAT)
+    constexpr bool FAST1 = NB == 1 && sizeof(T) == 4 && !SSN_ABLATE;
+    constexpr bool LOOP1 = FAST1 && SSN_TILE_LOOP;
+    constexpr bool FLAT = FAST1 && SSN_TILE_EXEC && CP > C;      // (C = 4 has no pad float to absorb a dummy store)
     // the row this lane finishes each step (a = cg), its LDS slot, input and state
     const int myrow = rowbase + cg;
     const bool fin = (cg < RA) && (myrow < M);
-    const int myslot = (myrow / C) * CP + (myrow % C);
+    // FLAT: a lane that finishes no row stores its (meaningless) state every step all the same, to the last pad float of
+    // its column group's slab: column CP - 1 >= C, which no FMA consumes -- never to a column c < C of a ragged last
+    // group: those meet masked-zero W, and 0 * Inf = NaN
+    const int myslot = (FLAT && !fin) ? cg * CP + CP - 1 : (myrow / C) * CP + (myrow % C);
     T rc[NB], rp[NB], ex[NB];            // x_k, x_{k-1} of my row; input of my row
     bool live[NB];
 #pragma unroll
@@ -99,6 +119,111 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     // slot (i+1)%3 is cleared for iteration i+1.  The FMAs of the extra iteration are discarded.
     int cur = 0;
     int step = 0;
+    if constexpr (LOOP1 || FLAT) {
+        using LdsI = __attribute__((address_space(3))) int*;
+        using LdsS = __attribute__((address_space(3))) short*;
+        using LdsV = const __attribute__((address_space(3))) void*;
+        T* const rb0 = &rbuf[0][0][0];
+        constexpr unsigned BUF = 8 * CP;                          // elements per state buffer
+        const unsigned fbase = (unsigned)(size_t)(LdsV)&flags[0][0];
+        // FLAT: lanes with nothing to report store their 1 to a fourth word that nobody reads
+        const unsigned fsink = fbase + 12;
+        // partial sums of one step from the state buffer at element offset boff
+        auto partial_sums = [&](unsigned boff, T (&acc)[1][8]) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r) acc[0][r] = (T)0;
+            if constexpr (SPLIT) {
+                sw.template matvec<1, FMA_MODE>(wlds, threadIdx.x, rb0 + boff, cg, acc);
+            } else {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const V4 rv = *reinterpret_cast<const V4*>(&rb0[boff + cg * CP + 4 * q]);
+                    const T rr[4] = {rv.x, rv.y, rv.z, rv.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (4 * q + e < C) {
+#pragma unroll
+                            for (int r = 0; r < RA; ++r) acc[0][r] = fma(w[r][4 * q + e], rr[e], acc[0][r]);
+                        }
+                    }
+                }
+            }
+        };
+        // reduce, Euler update and stop tests of one step: the new state goes to the OTHER buffer, the tests to the flag
+        // word at byte address fcur, and the word at fnext is cleared for the next step
+        auto update = [&](T (&acc)[1][8], unsigned boff, unsigned fcur, unsigned fnext) {
+            const T u = reduce_rows_to_lane<RA>(acc[0], cg);
+            const T r1 = rc[0] + (-rc[0] + io_eval(u + ex[0], a.io)) * eps;
+            const bool moving = abs_t(r1 - rc[0]) >= a.st.atol;
+            const bool beyond = a.st.check_hard && r1 >= a.st.hard_stop;
+            if constexpr (FLAT) {
+                *(LdsS)(size_t)((fin && moving) ? fcur : fsink) = 1;
+                *(LdsS)(size_t)(((fin && beyond) ? fcur : fsink) + 2) = 1;
+                rc[0] = r1;
+                rb0[(boff ^ BUF) + myslot] = rc[0];
+                // Nothing reads slot (step + 1) % 3 between the barrier before this step and the barrier after it (it was
+                // read in step - 1, it is written in step + 1), so any lane may clear it now: all of them do, same address
+                *(LdsI)(size_t)fnext = 0;
+            } else {
+                if (fin) {
+                    if (moving) *(LdsS)(size_t)fcur = 1;
+                    if (beyond) *(LdsS)(size_t)(fcur + 2) = 1;
+                    rc[0] = r1;
+                    rb0[(boff ^ BUF) + myslot] = rc[0];
+                }
+                if (threadIdx.x < NB) *(LdsI)(size_t)fnext = 0;
+            }
+        };
+        // keeps the consumption of the flag word BELOW the FMA block (see the general loop)
+        auto verdict = [&](int fl, T (&acc)[1][8]) {
+            asm volatile("" : "+v"(fl));
+#pragma unroll
+            for (int r = 0; r < RA; ++r) asm volatile("" : "+v"(acc[0][r]));
+            return __builtin_amdgcn_readfirstlane(fl);
+        };
+        auto stops = [](int fu) { return !(fu & 0xffff) || (fu >> 16); };
+        int stopword = 1;
+        if constexpr (LOOP1) {
+            // The loop rotated by half a step: [update of step k, barrier, flag word of step k, FMA block of step k + 1,
+            // verdict], so that ONE test at the bottom ends it -- on the verdict of the step just taken or at max_iter,
+            // where the FMA block of a step that is never taken is discarded just as after a stop.  The flag slots are
+            // three byte addresses that rotate and the state buffer is an offset that toggles: no step % 3, no multiply.
+            if (a.st.max_iter > 0) {
+                unsigned fcur = fbase, fnext = fbase + 4, fafter = fbase + 8, boff = 0;
+                T acc[1][8];
+                partial_sums(boff, acc);
+                do {
+                    update(acc, boff, fcur, fnext);
+                    __syncthreads();
+                    ++step;
+                    boff ^= BUF;                                   // 0 <-> BUF
+                    const int fl = *(LdsI)(size_t)fcur;
+                    const unsigned t = fcur; fcur = fnext; fnext = fafter; fafter = t;
+                    partial_sums(boff, acc);
+                    stopword = verdict(fl, acc);
+                } while (!stops(stopword) && step < a.st.max_iter);
+                cur = boff != 0;
+            }
+        } else {
+            for (; step < a.st.max_iter; ++step) {
+                const unsigned fprev = fbase + 4 * ((step + 2) % 3), fcur = fbase + 4 * (step % 3), fnext = fbase + 4 * ((step + 1) % 3);
+                int fl = 1;
+                if (step > 0) fl = *(LdsI)(size_t)fprev;
+                T acc[1][8];
+                partial_sums(cur * BUF, acc);
+                if (step > 0) {
+                    stopword = verdict(fl, acc);
+                    if (stops(stopword)) break;
+                }
+                update(acc, cur * BUF, fcur, fnext);
+                __syncthreads();
+                cur ^= 1;
+            }
+            if (step == a.st.max_iter && step > 0) stopword = flags[(step + 2) % 3][0];      // the last step's own verdict
+        }
+        // code and step count once, from the word that ended the loop
+        if (stops(stopword)) { code[0] = (stopword & 0xffff) ? 2 : 0; nsteps[0] = step; }
+    } else
     for (; step < a.st.max_iter; ++step) {
         int fl[NB];
         if (!(SSN_ABLATE & 4) && step > 0) {
@@ -112,7 +237,7 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
 #pragma unroll
             for (int r = 0; r < 8; ++r) acc[s][r] = (T)0;
         if constexpr (SPLIT) {
-            sw.template matvec<NB>(wlds, threadIdx.x, &rbuf[cur][0][0], cg, acc);
+            sw.template matvec<NB, FMA_MODE>(wlds, threadIdx.x, &rbuf[cur][0][0], cg, acc);
         } else {
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
@@ -188,7 +313,7 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     // NB == 1: nothing runs after the stop, so the buffer that was read in the last update still holds x_{k-1}
     if constexpr (NB == 1) { if (step > 0 && fin) rp[0] = rbuf[cur ^ 1][0][myslot]; }
     // verdict of the last executed iteration (no extra step was taken, so no roll-back)
-    if (!(SSN_ABLATE & 4) && step == a.st.max_iter && step > 0) {
+    if (!(SSN_ABLATE & 4) && !(LOOP1 || FLAT) && step == a.st.max_iter && step > 0) {
 #pragma unroll
         for (int s = 0; s < NB; ++s) {
             if (!frozen[s]) {
@@ -223,7 +348,7 @@ __global__ void __launch_bounds__(MAXTHREADS, MINWAVES) solve_tile_kernel(SolveA
     __shared__ __align__(16) T rbuf[2][NB][8 * CP];
     // per slot and stimulus one 32-bit word: low half = "some row has not converged", high half = "some row hit
     // the rate bound"; written with 16-bit stores (no race between the two kinds), read and cleared as one word
-    __shared__ int flags[3][NB];
+    __shared__ int flags[(NB == 1 && sizeof(T) == 4) ? 4 : 3][NB];      // (fourth word: sink of the NB = 1 loop)
     if constexpr (RL > 0) set_rank_priority((blockIdx.x >> 8) % 3);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     tile_wave_body<T, RA, C, RL, NB, false>(a, wlds, rbuf, flags, (8 * wave + (lane >> 3)) * RA);
@@ -239,7 +364,7 @@ __global__ void __launch_bounds__(64 * NW, MINWAVES) solve_tile_mixed_kernel(Sol
     using Split = TileSplit<7, C, RL>;
     __shared__ __align__(16) T wlds[Split::lds_elems(64 * (NW - 1))];      // heavy waves only
     __shared__ __align__(16) T rbuf[2][NB][8 * CP];
-    __shared__ int flags[3][NB];
+    __shared__ int flags[(NB == 1 && sizeof(T) == 4) ? 4 : 3][NB];
     set_rank_priority((blockIdx.x >> 8) % 3);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave < NW - 1) tile_wave_body<T, 7, C, RL, NB, false>(a, wlds, rbuf, flags, (8 * wave + (lane >> 3)) * 7);

@@ -20,6 +20,12 @@
 #ifndef SSN_REDUCE4
 #define SSN_REDUCE4 1            // diagnostic: 0 = 8-row transpose-reduce also for tiles of <= 4 rows
 #endif
+// diagnostic switch, fp32 solver only (bit mask; the generator kernels always run SplitTile::matvec<NB, 0>):
+// 1 = light wave of the mixed kernel: the packed FMAs of a quad of columns as ONE asm statement, 2 = the first column as a
+// multiply (no accumulator zeroed first), 4 = the one-statement form also in the waves with LDS-resident rows
+#ifndef SSN_TILE_FMA
+#define SSN_TILE_FMA 3
+#endif
 
 namespace ssn {
 
@@ -323,14 +329,65 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
         }
     }
 
+    // The packed FMAs of the two register row pairs for NC columns of one quad, as ONE asm statement.  The compiler
+    // counts an asm statement as zero wait states and assumes that it may write its result through dst_sel, so between
+    // two single-instruction statements of one accumulator chain it puts an s_nop unless an instruction of its own
+    // happens to stand there: one per pair of FMAs in a wave that runs two chains only.  v_pk_fma_f32 writes whole
+    // registers (op_sel picks SOURCE halves), dependent VALU instructions interlock, and statements a whole stage apart
+    // have the LDS reads between them.  MUL: column 0 is a multiply (the accumulators are outputs only).
+    // TIE: `tie` rides along as an in-out operand that no instruction touches.  It is the accumulator of the LDS-resident
+    // rows, whose FMAs wait for their W units and therefore have to stay BEHIND the block that covers that wait.
+#define SSN_PK_LO(a, w, r) "v_pk_fma_f32 %[" a "], %[" w "], %[" r "], %[" a "] op_sel_hi:[1,0,1]\n"
+#define SSN_PK_HI(a, w, r) "v_pk_fma_f32 %[" a "], %[" w "], %[" r "], %[" a "] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n"
+#define SSN_PK_MUL(a, w, r) "v_pk_mul_f32 %[" a "], %[" w "], %[" r "] op_sel_hi:[1,0]\n"
+#define SSN_PK_COL0 SSN_PK_LO("a0", "u0", "rl") SSN_PK_LO("a1", "v0", "rl")
+#define SSN_PK_COL0M SSN_PK_MUL("a0", "u0", "rl") SSN_PK_MUL("a1", "v0", "rl")
+#define SSN_PK_COL1 SSN_PK_HI("a0", "u1", "rl") SSN_PK_HI("a1", "v1", "rl")
+#define SSN_PK_COL2 SSN_PK_LO("a0", "u2", "rh") SSN_PK_LO("a1", "v2", "rh")
+#define SSN_PK_COL3 SSN_PK_HI("a0", "u3", "rh") SSN_PK_HI("a1", "v3", "rh")
+#define SSN_PK_IN [rl] "v"(rlo), [rh] "v"(rhi), [u0] "v"(w0[0]), [u1] "v"(w0[NC > 1 ? 1 : 0]), [u2] "v"(w0[NC > 2 ? 2 : 0]), \
+                  [u3] "v"(w0[NC > 3 ? 3 : 0]), [v0] "v"(w1[0]), [v1] "v"(w1[NC > 1 ? 1 : 0]), [v2] "v"(w1[NC > 2 ? 2 : 0]), \
+                  [v3] "v"(w1[NC > 3 ? 3 : 0])
+#define SSN_PK_STMT(text, how)                                                                      \
+    do {                                                                                            \
+        if constexpr (TIE) asm(text : [a0] how(a0), [a1] how(a1), [t] "+v"(tie) : SSN_PK_IN);       \
+        else asm(text : [a0] how(a0), [a1] how(a1) : SSN_PK_IN);                                    \
+    } while (0)
+    template <int NC, bool MUL, bool TIE>
+    static __device__ __forceinline__ void pk_block(V2& a0, V2& a1, V2& tie, const V2* w0, const V2* w1, const V2& rlo, const V2& rhi) {
+        static_assert(NC >= 1 && NC <= 4, "columns of one 16-byte read");
+        if constexpr (MUL) {
+            if constexpr (NC == 1) SSN_PK_STMT(SSN_PK_COL0M, "=&v");
+            else if constexpr (NC == 2) SSN_PK_STMT(SSN_PK_COL0M SSN_PK_COL1, "=&v");
+            else if constexpr (NC == 3) SSN_PK_STMT(SSN_PK_COL0M SSN_PK_COL1 SSN_PK_COL2, "=&v");
+            else SSN_PK_STMT(SSN_PK_COL0M SSN_PK_COL1 SSN_PK_COL2 SSN_PK_COL3, "=&v");
+        } else {
+            if constexpr (NC == 1) SSN_PK_STMT(SSN_PK_COL0, "+v");
+            else if constexpr (NC == 2) SSN_PK_STMT(SSN_PK_COL0 SSN_PK_COL1, "+v");
+            else if constexpr (NC == 3) SSN_PK_STMT(SSN_PK_COL0 SSN_PK_COL1 SSN_PK_COL2, "+v");
+            else SSN_PK_STMT(SSN_PK_COL0 SSN_PK_COL1 SSN_PK_COL2 SSN_PK_COL3, "+v");
+        }
+    }
+#undef SSN_PK_STMT
+#undef SSN_PK_IN
+
     // acc[s][a] = sum_c W[a][c] * x_s[col(cg, c)], rows a < RR from VGPRs, rows a >= RR from the LDS image.
     // Software pipeline per quad q of columns: issue the x reads of quad q+1 and the W units of quad q, run the
     // register FMAs of quad q (which cover the LDS latency), then the LDS-row FMAs.
-    template <int NB>
+    // MODE (fp32 with SSN_PK_ASM only; 0 = the generator kernels' block): bit 0 = pk_block for a tile with two register row
+    // pairs; bit 1 = the first product of every chain is a multiply, so no accumulator is zeroed first.  fma(w, r, +0) and
+    // w * r are the same bits unless the product is an exact zero of negative sign (+0 from the FMA, -0 from the
+    // multiply); a chain can then end in -0 instead of +0 only if every one of its products is a zero, the
+    // transpose-reduce adds it to the other partial sums (x + -0 = x, and -0 + +0 = +0), and a row whose partial sums are
+    // all -0 meets `+ ext` before the I/O function, which maps +0 and -0 to the same rate: the state never sees the sign.
+    template <int NB, int MODE = 0>
     __device__ __forceinline__ void matvec(const T* wl, int tid, const T* xs /* [NB][8*CP] */, int cg,
                                            T (&acc)[NB][8]) const {
         constexpr int CP = SlabPad<C>::value;
         constexpr int NQ = (C + 3) / 4;
+        constexpr bool F32ASM = sizeof(T) == 4 && SSN_PK_ASM;
+        constexpr bool BLK = F32ASM && (MODE & 1) && NP == 2;
+        constexpr bool MUL0 = F32ASM && (MODE & 2);
         // Stage boundaries are enforced with data dependencies (an empty asm that "redefines" the LDS
         // addresses and the accumulators): the reads of stage q+1 cannot be hoisted above it, the FMAs of
         // stage q cannot sink below it.  __builtin_amdgcn_sched_barrier alone is not enough -- instruction
@@ -343,12 +400,14 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
         unsigned wa = (unsigned)(size_t)(LdsT)(wl + tid * 4);
         V2 a2[NB][NP > 0 ? NP : 1], al2[NB];
         T ao[NB], al1[NB];
+        if constexpr (!MUL0) {
 #pragma unroll
-        for (int s = 0; s < NB; ++s) {
+            for (int s = 0; s < NB; ++s) {
 #pragma unroll
-            for (int k = 0; k < NP; ++k) a2[s][k] = (V2){(T)0, (T)0};
-            al2[s] = (V2){(T)0, (T)0};
-            ao[s] = al1[s] = (T)0;
+                for (int k = 0; k < NP; ++k) a2[s][k] = (V2){(T)0, (T)0};
+                al2[s] = (V2){(T)0, (T)0};
+                ao[s] = al1[s] = (T)0;
+            }
         }
         V4 rv[NQ][NB];
         V4 wu[S::NF4 > 0 ? S::NF4 : 1];
@@ -380,7 +439,11 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
                 // the compiler, short of registers, copies every fourth r into a fresh pair first (one v_mov per quad and
                 // accumulator group: ~15 of ~190 instructions per step).
                 const V2 rlo = {rv[q][s].x, rv[q][s].y}, rhi = {rv[q][s].z, rv[q][s].w};
-                auto pk_bcast = [&](V2& acc, const V2& w2, int e) {
+                // first (MUL0): acc = w2 * (r, r), the chain's first product (column 0 is the low half of the low pair)
+                auto pk_bcast = [&](V2& acc, const V2& w2, int e, bool first = false) {
+                    if constexpr (MUL0) {
+                        if (first) { asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(acc) : "v"(w2), "v"(rlo)); return; }
+                    }
                     if constexpr (sizeof(T) == 4 && SSN_PK_ASM) {
                         if (e == 0) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(w2), "v"(rlo));
                         else if (e == 1) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(w2), "v"(rlo));
@@ -390,13 +453,33 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
                         acc = __builtin_elementwise_fma(w2, (V2){rr[e], rr[e]}, acc);
                     }
                 };
+                if constexpr (BLK) {
+                    // (q is a constant once the loop is unrolled; the other branches fold away.  In the first quad
+                    // under MUL0 the accumulator of the LDS-resident rows does not exist yet: no tie there.)
+                    const int nc = C - 4 * q < 4 ? C - 4 * q : 4;
+                    const V2 *w0 = &p[0][4 * q], *w1 = &p[1][4 * q];
+                    V2 &x0 = a2[s][0], &x1 = a2[s][1], &t = al2[s];
+                    if (MUL0 && q == 0) {
+                        if (nc == 1) pk_block<1, true, false>(x0, x1, t, w0, w1, rlo, rhi);
+                        else if (nc == 2) pk_block<2, true, false>(x0, x1, t, w0, w1, rlo, rhi);
+                        else if (nc == 3) pk_block<3, true, false>(x0, x1, t, w0, w1, rlo, rhi);
+                        else pk_block<4, true, false>(x0, x1, t, w0, w1, rlo, rhi);
+                    } else {
+                        if (nc == 1) pk_block<1, false, RL == 2>(x0, x1, t, w0, w1, rlo, rhi);
+                        else if (nc == 2) pk_block<2, false, RL == 2>(x0, x1, t, w0, w1, rlo, rhi);
+                        else if (nc == 3) pk_block<3, false, RL == 2>(x0, x1, t, w0, w1, rlo, rhi);
+                        else pk_block<4, false, RL == 2>(x0, x1, t, w0, w1, rlo, rhi);
+                    }
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int c = 4 * q + e;
                     if (c < C) {
+                        if constexpr (!BLK) {
 #pragma unroll
-                        for (int k = 0; k < NP; ++k) pk_bcast(a2[s][k], p[k][c], e);
-                        if (ODD) ao[s] = fma(o[c], rr[e], ao[s]);
+                            for (int k = 0; k < NP; ++k) pk_bcast(a2[s][k], p[k][c], e, c == 0);
+                        }
+                        if (ODD) ao[s] = (MUL0 && c == 0) ? o[c] * rr[e] : fma(o[c], rr[e], ao[s]);
                     }
                 }
 #pragma unroll
@@ -406,9 +489,9 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
                         if constexpr (RL == 2) {
                             const int j = c * 2;
                             const V2 wp = {wu[j / 4][j % 4], wu[j / 4][j % 4 + 1]};
-                            pk_bcast(al2[s], wp, e);
+                            pk_bcast(al2[s], wp, e, c == 0);
                         } else if constexpr (RL == 1) {
-                            al1[s] = fma(wu[c / 4][c % 4], rr[e], al1[s]);
+                            al1[s] = (MUL0 && c == 0) ? wu[c / 4][c % 4] * rr[e] : fma(wu[c / 4][c % 4], rr[e], al1[s]);
                         }
                     }
                 }
