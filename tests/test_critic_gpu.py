@@ -1,5 +1,6 @@
 """GPU parity of the critic (forward, WGAN-GP loss and gradient, input gradient) and of the optimizer
-kernels against oracle/gan_torch.py.  fp32-MFMA path: tight; bf16-MFMA path: bf16 tolerance."""
+kernels against oracle/gan_torch.py.  fp32-MFMA path: tight; bf16-MFMA path: bf16 tolerance here, on generic inputs -- and
+bit for bit against an fp64 oracle on inputs with nothing to round in tests/test_critic_lattice_gpu.py."""
 import os
 import subprocess
 import sys
