@@ -14,6 +14,9 @@ Parity status:
     (tests/test_oracle_gan.py::test_time_avg_matches_reference_c_fixed_point).
   * probe indexing -- PINNED by the quenched values of
     networks/tests/test_conditional_prober.py:18-86.
+  * `euler_ssn_adjoint` (delta_t = dL/du_t, dL/dW, dL/d ext of the recurrence, any dtype) -- autograd of `euler_ssn` itself;
+    pinned by the layout identities of the kernels' header and by finite differences in single elements
+    (tests/test_adjoint_oracle.py).
   * dynamics/rate penalties, critic, WGAN-GP, BPTT gradients, Adam/RMSprop steps --
     PARITY UNPINNED against the reference (it holds no value tests for them); pinned
     only against this restatement and finite differences.  Third-party semantics
@@ -76,22 +79,29 @@ def io_fun(v, io_type, k=0.01, n=2.2, r0=200.0, r1=1000.0):
 
 
 def euler_ssn(W, ext, io_type, k, n, tau_E, tau_I, dt, seqlen, skip_steps, rate_penalty_threshold,
-              return_trajectory=False):
+              return_trajectory=False, dtype=DT, perturbations=None, inputs_out=None):
     """networks/ssn.py:555-576 (step) + 598-633 (reductions).
 
     W: (B, M, M) (NOT transposed; the reference keeps Wt and computes batched_dot(r, Wt)),
     ext: (B, NB, M).  r_0 = 0; trajectory[t] = state after t+1 steps;
     rs = trajectory[skip_steps:].  Returns time_avg (B, NB, M), dynamics_penalty, rate_penalty.
+
+    `dtype`: the arithmetic of the whole recurrence (W and ext are expected in it).  `perturbations`: a list of `seqlen`
+    tensors (B, NB, M) added to u_t = W r_t + ext (`euler_ssn_adjoint`); `inputs_out`: a list that receives every u_t.
     """
     B, NB, M = ext.shape
     N = M // 2
-    tau = torch.cat([torch.full((N,), float(tau_E), dtype=DT), torch.full((N,), float(tau_I), dtype=DT)])
+    tau = torch.cat([torch.full((N,), float(tau_E), dtype=dtype), torch.full((N,), float(tau_I), dtype=dtype)])
     eps = (dt / tau).reshape(1, 1, -1)
-    r = torch.zeros((B, NB, M), dtype=DT)
+    r = torch.zeros((B, NB, M), dtype=dtype)
     traj = []
     Wt = W.transpose(1, 2)
-    for _ in range(seqlen):
+    for t in range(seqlen):
         u = torch.bmm(r, Wt) + ext
+        if perturbations is not None:
+            u = u + perturbations[t]
+        if inputs_out is not None:
+            inputs_out.append(u)
         r = (1 - eps) * r + eps * io_fun(u, io_type, k, n)
         traj.append(r)
     rates = torch.stack(traj, dim=1)            # (B, T, NB, M)
@@ -102,6 +112,39 @@ def euler_ssn(W, ext, io_type, k, n, tau_E, tau_I, dt, seqlen, skip_steps, rate_
     if return_trajectory:
         return time_avg, dynamics_penalty, rate_penalty, rates
     return time_avg, dynamics_penalty, rate_penalty
+
+
+def euler_ssn_adjoint(W, ext, G, dynamics_cost, rate_cost, io_type, k, n, tau_E, tau_I, dt, seqlen, skip_steps,
+                      rate_penalty_threshold, dtype=DT):
+    """The adjoint of `euler_ssn` itself, by autograd: L = sum(G * time_avg) + dynamics_cost * dynamics_penalty
+    + rate_cost * rate_penalty (the generator loss of wgan.py:236-241 with the critic's gradient G in place of the critic),
+    with a zero perturbation p_t added to u_t = W r_t + ext at every step, so that delta_t = dL/dp_t = dL/du_t is a result
+    and not an intermediate.  W (B, M, M), ext and G (B, NB, M), any dtype: they are cast to `dtype`, which the whole
+    recurrence and its backward run in.  A cost of exactly 0 leaves its penalty out of L (the mean over an empty window,
+    skip_steps = seqlen - 1, is NaN).
+
+    Returns a dict of detached tensors: delta, traj, u, df = f'(u) all (B, T, NB, M) -- traj[:, t] the state after t + 1
+    steps, u[:, t] and delta[:, t] the input that produced it and dL/d of it -- gW = dL/dW (B, M, M), g_ext = dL/d ext
+    (B, NB, M), time_avg, dynamics_penalty, rate_penalty, loss.  The identities the kernels' layout rests on
+    (tests/test_adjoint_oracle.py): gW[b] = sum_t delta[b, t + 1]^T traj[b, t] and g_ext = sum_t delta[:, t], t = 0 included.
+    """
+    W = W.detach().to(dtype).clone().requires_grad_(True)
+    ext = ext.detach().to(dtype).clone().requires_grad_(True)
+    G = G.detach().to(dtype)
+    ps = [torch.zeros(ext.shape, dtype=dtype, requires_grad=True) for _ in range(seqlen)]
+    us = []
+    ta, dyn, rate, traj = euler_ssn(W, ext, io_type, k, n, tau_E, tau_I, dt, seqlen, skip_steps, rate_penalty_threshold,
+                                    return_trajectory=True, dtype=dtype, perturbations=ps, inputs_out=us)
+    loss = (G * ta).sum()
+    if dynamics_cost != 0:
+        loss = loss + dynamics_cost * dyn
+    if rate_cost != 0:
+        loss = loss + rate_cost * rate
+    grads = torch.autograd.grad(loss, [W, ext] + ps)
+    u = torch.stack(us, dim=1).detach().clone().requires_grad_(True)
+    df, = torch.autograd.grad(io_fun(u, io_type, k, n).sum(), u)
+    return dict(delta=torch.stack(grads[2:], dim=1), gW=grads[0], g_ext=grads[1], traj=traj.detach(), u=u.detach(), df=df,
+                time_avg=ta.detach(), dynamics_penalty=dyn.detach(), rate_penalty=rate.detach(), loss=loss.detach())
 
 
 def probes_from_norm(norm_probes, cell_types, num_sites):
