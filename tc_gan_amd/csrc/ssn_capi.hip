@@ -576,21 +576,10 @@ int gen_backward_impl(const T* W, const T* traj, T* delta, const T* gta, T* g_ex
 }
 
 // ---- the WGAN-GP critic: one description, one choice of kernels ---------------------------------------------------------------
-// Every exported critic pass fills a CriticNet and goes through the four functions below; critic_path is the ONLY place that
-// decides which kernels compute a critic.
-struct CriticNet {
-    const float* params; const int* dims;
-    const int* flags;        // HOST int[nlayers] or NULL (all plain): bit 0 = layer normalisation, bit 1 = learnable scale after it
-    int nlayers;
-    int act;                 // the public activation code (0 rectify ... 7 elu): what the general chain computes
-    float leak;              // slope below zero of a piecewise-linear act (codes 0-3): what the plain chain computes
-    int hide_cell_type; bool bf16;
-};
-// slope of activation codes 0-3 (the table of act_from_code in ssn_critic_ln.hip); the smooth ones have none
-float act_leak(int act) {
-    static const float leak[4] = {0.f, 0.01f, 1.f / 3.f, 1.f};
-    return act >= 0 && act < 4 ? leak[act] : 0.f;
-}
+// Every exported critic pass describes its critic as an ssn::CriticSpec (ssn_host.h, built by one helper per family of entry
+// points further down) and goes through the four functions below; critic_path is the ONLY place that decides which kernels
+// compute a critic.  The back ends read the flat parameter vector through ssn::critic_layout (ssn_host.h), the ONLY walk of it.
+using ssn::CriticSpec;
 // Critics whose layers are all <= 128 wide fit the fused row-block kernels (ssn_critic_fused.hip: 3 launches per update, fp32
 // arithmetic whatever `precision` says).  Above ~2048 stacked rows the layer-by-layer chain (fixed ~250 us of launch latency,
 // MFMA arithmetic) is as fast as they are (plain FMAs, time proportional to the rows).  SSN_CRITIC_FUSED=0 in the environment
@@ -605,7 +594,7 @@ bool fused_ok(const int* dims, int nlayers, long rows) {
 // General: the chain of ssn_critic_ln.hip (layer normalisation, scales, smooth nonlinearities).
 enum class CriticPath { Fused, Plain, General };
 // rows: the stacked rows of the pass; conds: every condition pointer of the call is given
-CriticPath critic_path(const CriticNet& net, long rows, bool conds) {
+CriticPath critic_path(const CriticSpec& net, long rows, bool conds) {
     bool norm = false, scaled = false;
     for (int l = 0; net.flags && l < net.nlayers; ++l) { norm = norm || (net.flags[l] & 1); scaled = scaled || (net.flags[l] & 2); }
     if (scaled || net.act >= 4 || (norm && net.leak != 0.f)) return CriticPath::General;
@@ -613,60 +602,44 @@ CriticPath critic_path(const CriticNet& net, long rows, bool conds) {
     if (conds && fused_ok(net.dims, net.nlayers, rows)) return CriticPath::Fused;
     return norm ? CriticPath::General : CriticPath::Plain;
 }
-int critic_net_forward(const CriticNet& n, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st) {
+int critic_net_forward(const CriticSpec& n, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st) {
     switch (critic_path(n, batch, cond != nullptr)) {
-    case CriticPath::Fused:
-        SSN_TRY(ssn::critic_fused_forward(n.params, n.dims, n.flags, n.nlayers, x, cond, batch, n.hide_cell_type, out, ws, st));
-        break;
-    case CriticPath::Plain:
-        SSN_TRY(ssn::critic_forward(n.params, n.dims, n.nlayers, x, cond, batch, n.hide_cell_type, out, ws, n.bf16, st, n.leak));
-        break;
-    case CriticPath::General:
-        SSN_TRY(ssn::critic_norm_forward(n.params, n.dims, n.flags, n.nlayers, x, cond, batch, n.hide_cell_type, out, ws, n.bf16, st, n.act));
-        break;
+    case CriticPath::Fused: SSN_TRY(ssn::critic_fused_forward(n, x, cond, batch, out, ws, st)); break;
+    case CriticPath::Plain: SSN_TRY(ssn::critic_forward(n, x, cond, batch, out, ws, st)); break;
+    case CriticPath::General: SSN_TRY(ssn::critic_norm_forward(n, x, cond, batch, out, ws, st)); break;
     }
     return 0;
 }
-// (eps, xp_out: the plain chain builds the penalty points and its three input blocks in ONE launch -- critic_step_impl)
-int critic_net_loss_grad(const CriticNet& n, const float* xg, const float* cg, const float* xd, const float* cd, const float* xp,
+// (eps, xp_out: the plain chain builds the penalty points and its three input blocks in ONE launch -- critic_step_impl; nullptr
+// on every other path)
+int critic_net_loss_grad(const CriticSpec& n, const float* xg, const float* cg, const float* xd, const float* cd, const float* xp,
                          const float* cp, int ng, int nd, int np, float lmd, float* grads, float* stats, float* dvals, float* ws,
-                         hipStream_t st, const float* eps = nullptr, float* xp_out = nullptr) {
+                         hipStream_t st, const float* eps, float* xp_out) {
     switch (critic_path(n, (long)ng + nd + np, cg && cd && cp)) {
     case CriticPath::Fused:
-        SSN_TRY(ssn::critic_fused_loss_grad(n.params, n.dims, n.flags, n.nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, n.hide_cell_type,
-                                            grads, stats, dvals, ws, st));
+        SSN_TRY(ssn::critic_fused_loss_grad(n, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, grads, stats, dvals, ws, st));
         break;
     case CriticPath::Plain:
-        SSN_TRY(ssn::critic_loss_grad(n.params, n.dims, n.nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, n.hide_cell_type, grads,
-                                      stats, dvals, ws, n.bf16, st, n.leak, eps, xp_out));
+        SSN_TRY(ssn::critic_loss_grad(n, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, grads, stats, dvals, ws, st, eps, xp_out));
         break;
     case CriticPath::General:
-        SSN_TRY(ssn::critic_norm_loss_grad(n.params, n.dims, n.flags, n.nlayers, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd,
-                                           n.hide_cell_type, grads, stats, dvals, ws, n.bf16, st, n.act));
+        SSN_TRY(ssn::critic_norm_loss_grad(n, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, grads, stats, dvals, ws, st));
         break;
     }
     return 0;
 }
-int critic_net_input_grad(const CriticNet& n, const float* x, const float* cond, int batch, float scale, float* gx, float* stats,
+int critic_net_input_grad(const CriticSpec& n, const float* x, const float* cond, int batch, float scale, float* gx, float* stats,
                           float* ws, hipStream_t st) {
     switch (critic_path(n, batch, cond != nullptr)) {
-    case CriticPath::Fused:
-        SSN_TRY(ssn::critic_fused_input_grad(n.params, n.dims, n.flags, n.nlayers, x, cond, batch, n.hide_cell_type, scale, gx, stats, ws, st));
-        break;
-    case CriticPath::Plain:
-        SSN_TRY(ssn::critic_input_grad(n.params, n.dims, n.nlayers, x, cond, batch, n.hide_cell_type, scale, gx, stats, ws, n.bf16, st,
-                                       n.leak));
-        break;
-    case CriticPath::General:
-        SSN_TRY(ssn::critic_norm_input_grad(n.params, n.dims, n.flags, n.nlayers, x, cond, batch, n.hide_cell_type, scale, gx, stats, ws,
-                                            n.bf16, st, n.act));
-        break;
+    case CriticPath::Fused: SSN_TRY(ssn::critic_fused_input_grad(n, x, cond, batch, scale, gx, stats, ws, st)); break;
+    case CriticPath::Plain: SSN_TRY(ssn::critic_input_grad(n, x, cond, batch, scale, gx, stats, ws, st)); break;
+    case CriticPath::General: SSN_TRY(ssn::critic_norm_input_grad(n, x, cond, batch, scale, gx, stats, ws, st)); break;
     }
     return 0;
 }
 // dvals[0:ng] = D(xg), dvals[ng:ng+nd] = D(xd): what the accuracy mean D(xg) - mean D(xd) is reduced from.
-int critic_net_accuracy_forwards(const CriticNet& n, const float* xg, const float* cg, const float* xd, const float* cd, int ng,
-                                 int nd, float* dvals, float* ws, hipStream_t st, bool inputs_ready = false) {
+int critic_net_accuracy_forwards(const CriticSpec& n, const float* xg, const float* cg, const float* xd, const float* cd, int ng,
+                                 int nd, float* dvals, float* ws, hipStream_t st, bool inputs_ready) {
     const bool conds = cg && cd;
     // a critic of fused size keeps one forward per input, on whichever path it takes (every leaky one included: those run
     // the plain chain twice)
@@ -674,13 +647,59 @@ int critic_net_accuracy_forwards(const CriticNet& n, const float* xg, const floa
     if (!fused_size && critic_path(n, ng, conds) == CriticPath::Plain) {
         // ONE pass of the plain chain over the stacked rows [xg; xd] (the values of two separate forwards, bit for bit).
         // inputs_ready: the workspace already starts with the input block of those rows (ssn_host.h)
-        SSN_TRY(ssn::critic_forward2(n.params, n.dims, n.nlayers, xg, cg, ng, xd, cd, nd, n.hide_cell_type, dvals, ws, n.bf16, st,
-                                     n.leak, inputs_ready));
+        SSN_TRY(ssn::critic_forward2(n, xg, cg, ng, xd, cd, nd, dvals, ws, st, inputs_ready));
         return 0;
     }
     int rc = ng > 0 ? critic_net_forward(n, xg, cg, ng, dvals, ws, st) : 0;
     if (!rc && nd > 0) rc = critic_net_forward(n, xd, cd, nd, dvals + ng, ws, st);
     return rc;
+}
+
+// One helper per family of entry points (include/ssnode_mi355x.h): the family's arguments as a CriticSpec, or a refusal under
+// the name `fn` of the entry point that was called.  What every family refuses is what ssn::critic_layout refuses.
+int critic_refuse(const char* fn, const char* why) {
+    g_last_error = std::string(fn) + ": " + why;
+    return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+}
+int checked_spec(const char* fn, const CriticSpec& s) {
+    ssn::CriticLayout lay;
+    return ssn::critic_layout(s, lay) ? 0 : critic_refuse(fn, "invalid layer flags / activation / slope, or more than 8 layers");
+}
+// -- norm: rectify, per-layer normalisation flags 0 / 1 -- and, for the accuracy and the one-call step, a slope next to plain
+//    layers (a slope next to a normalisation is a critic in its general form: the _act entry points)
+int norm_spec(const char* fn, const float* params, const int* dims, const int* layer_norm, int nlayers, float leak, int hide_cell_type,
+              int precision, CriticSpec& s) {
+    bool norm = false;
+    for (int l = 0; layer_norm && l < nlayers; ++l) {
+        if (layer_norm[l] != 0 && layer_norm[l] != 1)
+            return critic_refuse(fn, "layer_norm flags are 0 / 1 (scaled layers: the _act entry points)");
+        norm = norm || layer_norm[l] != 0;
+    }
+    if (leak != 0.f && norm) return critic_refuse(fn, "leak with layer-normalised layers (that critic: the _act entry points)");
+    s = CriticSpec{params, dims, layer_norm, nlayers, 0, leak, hide_cell_type, precision == 0};
+    return checked_spec(fn, s);
+}
+// -- leaky: plain layers, a hidden nonlinearity x > 0 ? x : leak * x (lasagne's leaky_rectify = 0.01, very_leaky_rectify = 1/3,
+//    linear = 1)
+int leaky_spec(const char* fn, const float* params, const int* dims, int nlayers, float leak, int hide_cell_type, int precision,
+               CriticSpec& s) {
+    return norm_spec(fn, params, dims, nullptr, nlayers, leak, hide_cell_type, precision, s);
+}
+// -- plain: rectify, plain layers
+int plain_spec(const char* fn, const float* params, const int* dims, int nlayers, int hide_cell_type, int precision, CriticSpec& s) {
+    return leaky_spec(fn, params, dims, nlayers, 0.f, hide_cell_type, precision, s);
+}
+// -- act: any critic -- activation code, per-layer flags 0 / 1 / 3
+int act_spec(const char* fn, const float* params, const int* dims, const int* layer_flags, int nlayers, int act, int hide_cell_type,
+             int precision, CriticSpec& s) {
+    ssn::ActSpec a{};
+    if (!ssn::act_from_code(act, a)) return critic_refuse(fn, "invalid layer flags / activation");
+    s = CriticSpec{params, dims, layer_flags, nlayers, act, a.leak, hide_cell_type, precision == 0};
+    return checked_spec(fn, s);
+}
+long critic_num_params(const int* dims, const int* layer_flags, int nlayers) {
+    ssn::CriticLayout lay;
+    return dims && ssn::critic_layout(CriticSpec{nullptr, dims, layer_flags, nlayers, 0, 0.f, 0, false}, lay) ? lay.nparams : -1;
 }
 
 }  // namespace
@@ -711,10 +730,9 @@ static int ss_system_impl(const T* R, const T* W, const T* dW, int dw_per_draw, 
 }
 extern "C" {
 
-long ssn_critic_num_params(const int* dims, int nlayers) {
-    long n = 0;
-    for (int l = 0; l < nlayers; ++l) n += (long)dims[l] * dims[l + 1] + dims[l + 1];
-    return n + dims[nlayers];
+long ssn_critic_num_params(const int* dims, int nlayers) { return critic_num_params(dims, nullptr, nlayers); }
+long ssn_critic_num_params_act(const int* dims, const int* layer_flags, int nlayers) {
+    return critic_num_params(dims, layer_flags, nlayers);
 }
 // The workspace queries cover whichever path the sizes select (critic_path, above).  The _norm one covers every path: a caller
 // of the routed entry points who asks it is safe whatever critic he describes.
@@ -726,142 +744,131 @@ size_t ssn_critic_workspace_floats(const int* dims, int nlayers, int batch_gd, i
 size_t ssn_critic_norm_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p) {
     return max_sz(ssn::critic_norm_workspace_floats(dims, nlayers, batch_gd, batch_p), ssn_critic_workspace_floats(dims, nlayers, batch_gd, batch_p));
 }
-// The critic's passes.  Four families of entry points have accumulated (include/ssnode_mi355x.h); each checks its own arguments,
-// describes its critic as a CriticNet and leaves the rest to critic_net_* above.
-// -- rectify, plain layers
+// The critic's passes.  Four families of entry points have accumulated (include/ssnode_mi355x.h); each describes its critic with
+// its family's helper (plain_spec, leaky_spec, norm_spec, act_spec above) and leaves the rest to critic_net_* above.
+// -- plain
 int ssn_critic_forward(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
                        int hide_cell_type, float* out, float* workspace, int precision, void* stream) {
     if (batch == 0) return 0;
-    return critic_net_forward(CriticNet{params, dims, nullptr, nlayers, 0, 0.f, hide_cell_type, precision == 0}, x, cond, batch, out,
-                              workspace, (hipStream_t)stream);
+    CriticSpec s;
+    if (int rc = plain_spec("ssn_critic_forward", params, dims, nlayers, hide_cell_type, precision, s)) return rc;
+    return critic_net_forward(s, x, cond, batch, out, workspace, (hipStream_t)stream);
 }
 int ssn_critic_loss_grad(const float* params, const int* dims, int nlayers, const float* xg, const float* cg,
                          const float* xd, const float* cd, const float* xp, const float* cp, int ng, int nd, int np,
                          float lmd, int hide_cell_type, float* grads, float* stats, float* dvals, float* workspace,
                          int precision, void* stream) {
-    return critic_net_loss_grad(CriticNet{params, dims, nullptr, nlayers, 0, 0.f, hide_cell_type, precision == 0}, xg, cg, xd, cd, xp, cp,
-                                ng, nd, np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream);
+    CriticSpec s;
+    if (int rc = plain_spec("ssn_critic_loss_grad", params, dims, nlayers, hide_cell_type, precision, s)) return rc;
+    return critic_net_loss_grad(s, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream,
+                                nullptr, nullptr);
 }
 int ssn_critic_input_grad(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
                           int hide_cell_type, float scale, float* gx, float* stats, float* workspace, int precision,
                           void* stream) {
     if (batch == 0) return 0;
-    return critic_net_input_grad(CriticNet{params, dims, nullptr, nlayers, 0, 0.f, hide_cell_type, precision == 0}, x, cond, batch, scale,
-                                 gx, stats, workspace, (hipStream_t)stream);
+    CriticSpec s;
+    if (int rc = plain_spec("ssn_critic_input_grad", params, dims, nlayers, hide_cell_type, precision, s)) return rc;
+    return critic_net_input_grad(s, x, cond, batch, scale, gx, stats, workspace, (hipStream_t)stream);
 }
-// -- a hidden nonlinearity x > 0 ? x : leak * x (lasagne's leaky_rectify = 0.01, very_leaky_rectify = 1/3, linear = 1), plain layers
+// -- leaky
 int ssn_critic_forward_leaky(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
                              int hide_cell_type, float leak, float* out, float* workspace, int precision, void* stream) {
     if (batch == 0) return 0;
-    return critic_net_forward(CriticNet{params, dims, nullptr, nlayers, 0, leak, hide_cell_type, precision == 0}, x, cond, batch, out,
-                              workspace, (hipStream_t)stream);
+    CriticSpec s;
+    if (int rc = leaky_spec("ssn_critic_forward_leaky", params, dims, nlayers, leak, hide_cell_type, precision, s)) return rc;
+    return critic_net_forward(s, x, cond, batch, out, workspace, (hipStream_t)stream);
 }
 int ssn_critic_loss_grad_leaky(const float* params, const int* dims, int nlayers, const float* xg, const float* cg,
                                const float* xd, const float* cd, const float* xp, const float* cp, int ng, int nd, int np,
                                float lmd, int hide_cell_type, float leak, float* grads, float* stats, float* dvals,
                                float* workspace, int precision, void* stream) {
-    return critic_net_loss_grad(CriticNet{params, dims, nullptr, nlayers, 0, leak, hide_cell_type, precision == 0}, xg, cg, xd, cd, xp, cp,
-                                ng, nd, np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream);
+    CriticSpec s;
+    if (int rc = leaky_spec("ssn_critic_loss_grad_leaky", params, dims, nlayers, leak, hide_cell_type, precision, s)) return rc;
+    return critic_net_loss_grad(s, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream,
+                                nullptr, nullptr);
 }
 int ssn_critic_input_grad_leaky(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
                                 int hide_cell_type, float leak, float scale, float* gx, float* stats, float* workspace,
                                 int precision, void* stream) {
     if (batch == 0) return 0;
-    return critic_net_input_grad(CriticNet{params, dims, nullptr, nlayers, 0, leak, hide_cell_type, precision == 0}, x, cond, batch, scale,
-                                 gx, stats, workspace, (hipStream_t)stream);
+    CriticSpec s;
+    if (int rc = leaky_spec("ssn_critic_input_grad_leaky", params, dims, nlayers, leak, hide_cell_type, precision, s)) return rc;
+    return critic_net_input_grad(s, x, cond, batch, scale, gx, stats, workspace, (hipStream_t)stream);
 }
-// -- rectify, per-layer normalisation flags 0 / 1
-static bool norm_flags_plain(const int* layer_norm, int nlayers) {
-    for (int l = 0; layer_norm && l < nlayers; ++l) if (layer_norm[l] != 0 && layer_norm[l] != 1) return false;
-    return true;
-}
-static bool any_norm(const int* layer_norm, int nlayers) {
-    for (int l = 0; layer_norm && l < nlayers; ++l) if (layer_norm[l] != 0) return true;
-    return false;
-}
+// -- norm
 int ssn_critic_forward_norm(const float* params, const int* dims, const int* layer_norm, int nlayers, const float* x,
                             const float* cond, int batch, int hide_cell_type, float* out, float* workspace, int precision,
                             void* stream) {
-    if (!norm_flags_plain(layer_norm, nlayers)) { g_last_error = "ssn_critic_forward_norm: layer_norm flags are 0 / 1 (scaled layers: ssn_critic_forward_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    CriticSpec s;
+    if (int rc = norm_spec("ssn_critic_forward_norm", params, dims, layer_norm, nlayers, 0.f, hide_cell_type, precision, s)) return rc;
     if (batch == 0) return 0;
-    return critic_net_forward(CriticNet{params, dims, layer_norm, nlayers, 0, 0.f, hide_cell_type, precision == 0}, x, cond, batch, out,
-                              workspace, (hipStream_t)stream);
+    return critic_net_forward(s, x, cond, batch, out, workspace, (hipStream_t)stream);
 }
 int ssn_critic_loss_grad_norm(const float* params, const int* dims, const int* layer_norm, int nlayers, const float* xg,
                               const float* cg, const float* xd, const float* cd, const float* xp, const float* cp, int ng,
                               int nd, int np, float lmd, int hide_cell_type, float* grads, float* stats, float* dvals,
                               float* workspace, int precision, void* stream) {
-    if (!norm_flags_plain(layer_norm, nlayers)) { g_last_error = "ssn_critic_loss_grad_norm: layer_norm flags are 0 / 1 (scaled layers: ssn_critic_loss_grad_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    return critic_net_loss_grad(CriticNet{params, dims, layer_norm, nlayers, 0, 0.f, hide_cell_type, precision == 0}, xg, cg, xd, cd, xp,
-                                cp, ng, nd, np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream);
+    CriticSpec s;
+    if (int rc = norm_spec("ssn_critic_loss_grad_norm", params, dims, layer_norm, nlayers, 0.f, hide_cell_type, precision, s)) return rc;
+    return critic_net_loss_grad(s, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream,
+                                nullptr, nullptr);
 }
 int ssn_critic_input_grad_norm(const float* params, const int* dims, const int* layer_norm, int nlayers, const float* x,
                                const float* cond, int batch, int hide_cell_type, float scale, float* gx, float* stats,
                                float* workspace, int precision, void* stream) {
-    if (!norm_flags_plain(layer_norm, nlayers)) { g_last_error = "ssn_critic_input_grad_norm: layer_norm flags are 0 / 1 (scaled layers: ssn_critic_input_grad_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    CriticSpec s;
+    if (int rc = norm_spec("ssn_critic_input_grad_norm", params, dims, layer_norm, nlayers, 0.f, hide_cell_type, precision, s)) return rc;
     if (batch == 0) return 0;
-    return critic_net_input_grad(CriticNet{params, dims, layer_norm, nlayers, 0, 0.f, hide_cell_type, precision == 0}, x, cond, batch,
-                                 scale, gx, stats, workspace, (hipStream_t)stream);
+    return critic_net_input_grad(s, x, cond, batch, scale, gx, stats, workspace, (hipStream_t)stream);
 }
-// mean D(xg) - mean D(xd) in one call (the critic's values of both inputs into `dvals`, one reduction in a fixed order):
+// mean D(xg) - mean D(xd) in one call (the critic's values of both inputs into `dvals`, one reduction in a fixed order)
+static int critic_accuracy(const CriticSpec& s, const float* xg, const float* cg, const float* xd, const float* cd, int ng, int nd,
+                           float* acc, float* dvals, float* workspace, void* stream) {
+    if (int rc = critic_net_accuracy_forwards(s, xg, cg, xd, cd, ng, nd, dvals, workspace, (hipStream_t)stream, false)) return rc;
+    SSN_TRY(ssn::launch_mean_diff(dvals, ng, nd, acc, (hipStream_t)stream));
+    return 0;
+}
 // layer_norm NULL or all zero = plain layers, leak as in the _leaky entry points (plain layers only).
 int ssn_critic_accuracy(const float* params, const int* dims, const int* layer_norm, int nlayers, float leak, const float* xg,
                         const float* cg, const float* xd, const float* cd, int ng, int nd, int hide_cell_type, float* acc,
                         float* dvals, float* workspace, int precision, void* stream) {
-    if (!norm_flags_plain(layer_norm, nlayers)) { g_last_error = "ssn_critic_forward_norm: layer_norm flags are 0 / 1 (scaled layers: ssn_critic_forward_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    // (a slope next to a normalisation is a critic in its general form; this call used to drop the slope without a word)
-    if (leak != 0.f && any_norm(layer_norm, nlayers)) { g_last_error = "ssn_critic_accuracy: leak with layer-normalised layers (that critic: ssn_critic_accuracy_act)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    if (int rc = critic_net_accuracy_forwards(CriticNet{params, dims, layer_norm, nlayers, 0, leak, hide_cell_type, precision == 0}, xg, cg,
-                                              xd, cd, ng, nd, dvals, workspace, (hipStream_t)stream)) return rc;
-    SSN_TRY(ssn::launch_mean_diff(dvals, ng, nd, acc, (hipStream_t)stream));
-    return 0;
+    CriticSpec s;
+    if (int rc = norm_spec("ssn_critic_accuracy", params, dims, layer_norm, nlayers, leak, hide_cell_type, precision, s)) return rc;
+    return critic_accuracy(s, xg, cg, xd, cd, ng, nd, acc, dvals, workspace, stream);
 }
-// -- any critic: activation code, per-layer flags 0 / 1 / 3
-static bool act_flags_ok(const int* flags, int nlayers, int act) {
-    if (act < 0 || act > 7 || nlayers < 0 || nlayers > 8) return false;
-    for (int l = 0; flags && l < nlayers; ++l) if (flags[l] != 0 && flags[l] != 1 && flags[l] != 3) return false;
-    return true;
-}
-static CriticNet act_net(const float* params, const int* dims, const int* layer_flags, int nlayers, int act, int hide_cell_type,
-                         int precision) {
-    return CriticNet{params, dims, layer_flags, nlayers, act, act_leak(act), hide_cell_type, precision == 0};
-}
-long ssn_critic_num_params_act(const int* dims, const int* layer_flags, int nlayers) {
-    if (!dims || !act_flags_ok(layer_flags, nlayers, 0)) return -1;
-    return ssn::critic_act_num_params(dims, layer_flags, nlayers);
-}
+// -- act
 int ssn_critic_forward_act(const float* params, const int* dims, const int* layer_flags, int nlayers, int act, const float* x,
                            const float* cond, int batch, int hide_cell_type, float* out, float* workspace, int precision,
                            void* stream) {
-    if (!act_flags_ok(layer_flags, nlayers, act)) { g_last_error = "ssn_critic_forward_act: invalid layer flags / activation"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    CriticSpec s;
+    if (int rc = act_spec("ssn_critic_forward_act", params, dims, layer_flags, nlayers, act, hide_cell_type, precision, s)) return rc;
     if (batch == 0) return 0;
-    return critic_net_forward(act_net(params, dims, layer_flags, nlayers, act, hide_cell_type, precision), x, cond, batch, out, workspace,
-                              (hipStream_t)stream);
+    return critic_net_forward(s, x, cond, batch, out, workspace, (hipStream_t)stream);
 }
 int ssn_critic_loss_grad_act(const float* params, const int* dims, const int* layer_flags, int nlayers, int act, const float* xg,
                              const float* cg, const float* xd, const float* cd, const float* xp, const float* cp, int ng,
                              int nd, int np, float lmd, int hide_cell_type, float* grads, float* stats, float* dvals,
                              float* workspace, int precision, void* stream) {
-    if (!act_flags_ok(layer_flags, nlayers, act)) { g_last_error = "ssn_critic_loss_grad_act: invalid layer flags / activation"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    return critic_net_loss_grad(act_net(params, dims, layer_flags, nlayers, act, hide_cell_type, precision), xg, cg, xd, cd, xp, cp, ng, nd,
-                                np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream);
+    CriticSpec s;
+    if (int rc = act_spec("ssn_critic_loss_grad_act", params, dims, layer_flags, nlayers, act, hide_cell_type, precision, s)) return rc;
+    return critic_net_loss_grad(s, xg, cg, xd, cd, xp, cp, ng, nd, np, lmd, grads, stats, dvals, workspace, (hipStream_t)stream,
+                                nullptr, nullptr);
 }
 int ssn_critic_input_grad_act(const float* params, const int* dims, const int* layer_flags, int nlayers, int act, const float* x,
                               const float* cond, int batch, int hide_cell_type, float scale, float* gx, float* stats,
                               float* workspace, int precision, void* stream) {
-    if (!act_flags_ok(layer_flags, nlayers, act)) { g_last_error = "ssn_critic_input_grad_act: invalid layer flags / activation"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    CriticSpec s;
+    if (int rc = act_spec("ssn_critic_input_grad_act", params, dims, layer_flags, nlayers, act, hide_cell_type, precision, s)) return rc;
     if (batch == 0) return 0;
-    return critic_net_input_grad(act_net(params, dims, layer_flags, nlayers, act, hide_cell_type, precision), x, cond, batch, scale, gx,
-                                 stats, workspace, (hipStream_t)stream);
+    return critic_net_input_grad(s, x, cond, batch, scale, gx, stats, workspace, (hipStream_t)stream);
 }
 int ssn_critic_accuracy_act(const float* params, const int* dims, const int* layer_flags, int nlayers, int act, const float* xg,
                             const float* cg, const float* xd, const float* cd, int ng, int nd, int hide_cell_type, float* acc,
                             float* dvals, float* workspace, int precision, void* stream) {
-    if (!act_flags_ok(layer_flags, nlayers, act)) { g_last_error = "ssn_critic_forward_act: invalid layer flags / activation"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    if (int rc = critic_net_accuracy_forwards(act_net(params, dims, layer_flags, nlayers, act, hide_cell_type, precision), xg, cg, xd, cd,
-                                              ng, nd, dvals, workspace, (hipStream_t)stream)) return rc;
-    SSN_TRY(ssn::launch_mean_diff(dvals, ng, nd, acc, (hipStream_t)stream));
-    return 0;
+    CriticSpec s;
+    if (int rc = act_spec("ssn_critic_accuracy_act", params, dims, layer_flags, nlayers, act, hide_cell_type, precision, s)) return rc;
+    return critic_accuracy(s, xg, cg, xd, cd, ng, nd, acc, dvals, workspace, stream);
 }
 static int optimizer_step_full(float* p, const float* g, float* s1, float* s2, long n, const ssn_opt_params* o, const double* gate,
                                double gate_bound, const float* clip_lo_v, const float* clip_hi_v, float* record, const float* record_tail,
@@ -917,12 +924,11 @@ int ssn_gen_apply_f32(float* params, const float* grads, float* s1, float* s2, i
 }
 static int critic_step_impl(const ssn_critic_step* a, const double* gate, double gate_bound, void* stream) {
     if (!a || !a->params || !a->dims || !a->xg || !a->xd || !a->eps || !a->xp || !a->grads || !a->stats || !a->dvals ||
-        !a->workspace || !a->opt || !a->acc_dvals || !a->tail || a->n <= 0 || a->nlayers < 0 || a->nseg < 0 ||
-        !norm_flags_plain(a->layer_norm, a->nlayers) || (a->leak != 0.f && any_norm(a->layer_norm, a->nlayers))) {
-        g_last_error = "ssn_critic_step_run: invalid argument";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    const CriticNet net{a->params, a->dims, a->layer_norm, a->nlayers, 0, a->leak, a->hide_cell_type, a->precision == 0};
+        !a->workspace || !a->opt || !a->acc_dvals || !a->tail || a->n <= 0 || a->nseg < 0)
+        return critic_refuse("ssn_critic_step_run", "invalid argument");
+    CriticSpec net;
+    if (int rc = norm_spec("ssn_critic_step_run", a->params, a->dims, a->layer_norm, a->nlayers, a->leak, a->hide_cell_type,
+                           a->precision, net)) return rc;
     const hipStream_t st = (hipStream_t)stream;
     const int n = a->n, nx = a->dims[0] - (a->cond ? 3 : 0);        // cond NULL: the unconditional critic (dims[0] = nx)
     int rc;
@@ -940,7 +946,7 @@ static int critic_step_impl(const ssn_critic_step* a, const double* gate, double
     // stacked forward of the accuracy builds it: same rows, same conditions -- not built again)
     if ((rc = critic_net_accuracy_forwards(net, a->xg, a->cond, a->xd, a->cond, n, n, a->acc_dvals, a->workspace, st, one_launch_inputs)))
         return rc;
-    if (a->nseg > 0 && (!a->seg_bounds || !a->seg_ws)) { g_last_error = "ssn_critic_step_run: invalid argument"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    if (a->nseg > 0 && (!a->seg_bounds || !a->seg_ws)) return critic_refuse("ssn_critic_step_run", "invalid argument");
     // accuracy, sums of squares and the head of the record: the chunk sums, then ONE finishing launch (same bits as
     // ssn_critic_accuracy + ssn_segment_sqnorms2_f32 + the head kernel)
     SSN_TRY(ssn::launch_step_finish(a->params, a->seg_bounds, a->nseg, a->seg_ws, a->acc_dvals, n, n, a->pens64, a->stats, a->tail, st));

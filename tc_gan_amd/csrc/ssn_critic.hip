@@ -657,47 +657,20 @@ __global__ void __launch_bounds__(256) axpy_kernel(float* __restrict__ y, const 
 // ---------------------------------------------------------------------------------
 // critic passes
 // ---------------------------------------------------------------------------------
-struct CriticNet {
-    int nlayers;           // hidden layers L
-    int dims[10];          // n_0 .. n_L
-    const float* W[9];
-    const float* b[9];
-    const float* wout;     // [n_L]
-    long nparams;
-    float leak;            // hidden nonlinearity: x > 0 ? x : leak * x (0 = rectify; the sign of h_l is the sign of its pre-activation)
-};
-
-static bool parse_net(const float* params, const int* dims, int nlayers, CriticNet& net, float leak = 0.f) {
-    if (nlayers < 0 || nlayers > 8 || !(leak >= 0.f) || leak > 1.f) return false;
-    net.nlayers = nlayers;
-    net.leak = leak;
-    long off = 0;
-    for (int l = 0; l <= nlayers; ++l) net.dims[l] = dims[l];
-    for (int l = 0; l < nlayers; ++l) {
-        net.W[l] = params + off; off += (long)dims[l] * dims[l + 1];
-        net.b[l] = params + off; off += dims[l + 1];
-    }
-    net.wout = params + off; off += dims[nlayers];
-    net.nparams = off;
-    return true;
-}
-
-static int blocks_for(long n) { long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
-
 // activations h[l] (l = 0..L) for `batch` rows live at act + offsets; returns D in dout[batch]
-static hipError_t critic_forward_pass(const CriticNet& net, float* const* h, float* dout, int batch, bool bf16, hipStream_t st) {
+static hipError_t critic_forward_pass(const CriticLayout& net, float* const* h, float* dout, int batch, bool bf16, hipStream_t st) {
     hipError_t e;
-    for (int l = 0; l < net.nlayers; ++l) {
+    for (int l = 0; l < net.L; ++l) {
         GemmArgs g{};
         g.A = h[l]; g.sam = net.dims[l]; g.sak = 1;
         g.B = net.W[l]; g.sbk = net.dims[l + 1]; g.sbn = 1;
         g.C = h[l + 1]; g.ldc = net.dims[l + 1];
         g.M = batch; g.N = net.dims[l + 1]; g.K = net.dims[l];
-        g.bias = net.b[l]; g.epilogue = EPI_BIAS_RELU; g.leak = net.leak;
+        g.bias = net.b[l]; g.epilogue = EPI_BIAS_RELU; g.leak = net.act.leak;
         if ((e = gemm(g, bf16, st)) != hipSuccess) return e;
     }
     GemmArgs g{};
-    const int L = net.nlayers;
+    const int L = net.L;
     g.A = h[L]; g.sam = net.dims[L]; g.sak = 1;
     g.B = net.wout; g.sbk = 1; g.sbn = 1;
     g.C = dout; g.ldc = 1; g.M = batch; g.N = 1; g.K = net.dims[L];
@@ -711,13 +684,13 @@ static hipError_t critic_forward_pass(const CriticNet& net, float* const* h, flo
 struct CriticFork;
 static hipError_t critic_hand_over(CriticFork* fk, hipStream_t from);
 static hipStream_t critic_grad_stream(CriticFork* fk, hipStream_t st);
-static hipError_t critic_backward_chain(const CriticNet& net, float* const* h, float* const* v, int batch, float* grads,
+static hipError_t critic_backward_chain(const CriticLayout& net, float* const* h, float* const* v, int batch, float* grads,
                                         bool want_input_grad, bool bf16, hipStream_t st, CriticFork* fk = nullptr) {
     hipError_t e;
     const hipStream_t sg = critic_grad_stream(fk, st);        // weight gradients and bias sums (st itself without a fork)
-    long off_end = net.nparams - net.dims[net.nlayers];
+    long off_end = net.nparams - net.dims[net.L];
     long off = off_end;
-    for (int l = net.nlayers - 1; l >= 0; --l) {
+    for (int l = net.L - 1; l >= 0; --l) {
         const int nin = net.dims[l], nout = net.dims[l + 1];
         off -= nout;                    // bias of layer l
         const long off_b = off;
@@ -739,7 +712,7 @@ static hipError_t critic_backward_chain(const CriticNet& net, float* const* h, f
             g.A = v[l + 1]; g.sam = nout; g.sak = 1;
             g.B = net.W[l]; g.sbk = 1; g.sbn = nout;        // op(B)(k, i) = W[i][k]
             g.C = v[l]; g.ldc = nin; g.M = batch; g.N = nin; g.K = nout;
-            if (l > 0) { g.epilogue = EPI_MASK; g.mask = h[l]; g.ldm = nin; g.leak = net.leak; }
+            if (l > 0) { g.epilogue = EPI_MASK; g.mask = h[l]; g.ldm = nin; g.leak = net.act.leak; }
             else { g.alpha = 1.f; g.beta = 0.f; g.epilogue = EPI_PLAIN; }
             if ((e = gemm(g, bf16, st)) != hipSuccess) return e;
         }
@@ -757,51 +730,51 @@ size_t critic_workspace_floats(const int* dims, int nlayers, int batch_gd, int b
 
 // Wide plain critics on bf16 operands: D (mode 0) or D and the input gradient (mode 1) of `batch` rows whose input block h0 is
 // built, in two launches -- weights to B fragments, the row-block kernel (ssn_critic_rows.hip).  `free_ws`: workspace behind h0.
-static hipError_t critic_rows_eval(const float* params, const int* dims, int nlayers, float* h0, int batch, float* dvals, int mode,
-                                   float* gx, float scale, int nx, float leak, float* free_ws, hipStream_t st) {
+static hipError_t critic_rows_eval(const CriticLayout& net, float* h0, int batch, float* dvals, int mode, float* gx, float scale,
+                                   int nx, float* free_ws, hipStream_t st) {
     RowsArgs ra{};
-    ra.L = nlayers; ra.leak = leak; ra.mode = mode; ra.nx = nx; ra.dvals = dvals; ra.gx = gx; ra.scale = scale;
-    for (int l = 0; l <= nlayers; ++l) ra.dims[l] = dims[l];
+    ra.L = net.L; ra.leak = net.act.leak; ra.mode = mode; ra.nx = nx; ra.dvals = dvals; ra.gx = gx; ra.scale = scale;
+    for (int l = 0; l <= net.L; ++l) ra.dims[l] = net.dims[l];
     if (mode == 0) { ra.h[0] = h0; ra.ng = batch; } else { ra.hp[0] = h0; ra.np = batch; }
-    hipError_t e = critic_rows_pack(params, dims, nlayers, free_ws, ra, nullptr, 0, st);
+    hipError_t e = critic_rows_pack(net, free_ws, ra, nullptr, 0, st);
     return e != hipSuccess ? e : critic_rows_launch(ra, st);
 }
 
 // D values for a batch (inference / accuracy): out[batch]
-hipError_t critic_forward(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
-                          int hide_cell_type, float* out, float* ws, bool bf16, hipStream_t st, float leak) {
-    CriticNet net;
-    if (!parse_net(params, dims, nlayers, net, leak)) return hipErrorInvalidValue;
+hipError_t critic_forward(const CriticSpec& c, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st) {
+    CriticLayout net;
+    if (!critic_layout(c, net)) return hipErrorInvalidValue;
+    const int* const dims = net.dims;
     const int nc = cond ? 3 : 0, nx = dims[0] - nc;          // (no condition columns: the unconditional critic)
     float* h[10];
     float* p = ws;
-    for (int l = 0; l <= nlayers; ++l) { h[l] = p; p += (long)batch * dims[l]; }
-    hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)batch * dims[0])), dim3(256), 0, st, x, cond, h[0], batch, nx, hide_cell_type, nc);
-    if (bf16 && batch > 0 && critic_rows_supported(dims, nlayers))
-        return critic_rows_eval(params, dims, nlayers, h[0], batch, out, 0, nullptr, 0.f, nx, leak, h[1], st);
-    return critic_forward_pass(net, h, out, batch, bf16, st);
+    for (int l = 0; l <= net.L; ++l) { h[l] = p; p += (long)batch * dims[l]; }
+    hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)batch * dims[0])), dim3(256), 0, st, x, cond, h[0], batch, nx, c.hide_cell_type, nc);
+    if (c.bf16 && batch > 0 && critic_rows_supported(dims, net.L))
+        return critic_rows_eval(net, h[0], batch, out, 0, nullptr, 0.f, nx, h[1], st);
+    return critic_forward_pass(net, h, out, batch, c.bf16, st);
 }
 
 // D values of TWO batches in one pass over the stacked rows [xa; xb] (the accuracy mean D(xg) - mean D(xd) after every critic
 // update, cwgan.py:505-507): every output row depends on its own input row alone and a forward GEMM is never split over K,
 // so the values are those of two separate forwards, bit for bit, for one chain of launches instead of two.
 // out[na + nb]; ws as critic_forward with batch = na + nb (<= 2 max(na, nb): what the callers reserve).
-hipError_t critic_forward2(const float* params, const int* dims, int nlayers, const float* xa, const float* ca, int na,
-                           const float* xb, const float* cb, int nb, int hide_cell_type, float* out, float* ws, bool bf16,
-                           hipStream_t st, float leak, bool inputs_ready) {
-    CriticNet net;
-    if (!parse_net(params, dims, nlayers, net, leak)) return hipErrorInvalidValue;
+hipError_t critic_forward2(const CriticSpec& c, const float* xa, const float* ca, int na, const float* xb, const float* cb, int nb,
+                           float* out, float* ws, hipStream_t st, bool inputs_ready) {
+    CriticLayout net;
+    if (!critic_layout(c, net)) return hipErrorInvalidValue;
+    const int* const dims = net.dims;
     if ((ca == nullptr) != (cb == nullptr) && na > 0 && nb > 0) return hipErrorInvalidValue;
     const int nc = (ca || cb) ? 3 : 0, nx = dims[0] - nc, batch = na + nb;
     if (batch == 0) return hipSuccess;
     float* h[10];
     float* p = ws;
-    for (int l = 0; l <= nlayers; ++l) { h[l] = p; p += (long)batch * dims[l]; }
-    if (na > 0 && !inputs_ready) hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)na * dims[0])), dim3(256), 0, st, xa, ca, h[0], na, nx, hide_cell_type, nc);
-    if (nb > 0 && !inputs_ready) hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)nb * dims[0])), dim3(256), 0, st, xb, cb, h[0] + (long)na * dims[0], nb, nx, hide_cell_type, nc);
-    if (bf16 && critic_rows_supported(dims, nlayers))
-        return critic_rows_eval(params, dims, nlayers, h[0], batch, out, 0, nullptr, 0.f, nx, leak, h[1], st);
-    return critic_forward_pass(net, h, out, batch, bf16, st);
+    for (int l = 0; l <= net.L; ++l) { h[l] = p; p += (long)batch * dims[l]; }
+    if (na > 0 && !inputs_ready) hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)na * dims[0])), dim3(256), 0, st, xa, ca, h[0], na, nx, c.hide_cell_type, nc);
+    if (nb > 0 && !inputs_ready) hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)nb * dims[0])), dim3(256), 0, st, xb, cb, h[0] + (long)na * dims[0], nb, nx, c.hide_cell_type, nc);
+    if (c.bf16 && critic_rows_supported(dims, net.L))
+        return critic_rows_eval(net, h[0], batch, out, 0, nullptr, 0.f, nx, h[1], st);
+    return critic_forward_pass(net, h, out, batch, c.bf16, st);
 }
 
 // The two halves of a critic update -- the Wasserstein term on [xg; xd] and the gradient penalty on xp -- are independent
@@ -848,22 +821,22 @@ static hipError_t critic_hand_over(CriticFork* fk, hipStream_t from) { return fk
 static hipStream_t critic_grad_stream(CriticFork* fk, hipStream_t st) { return fk ? fk->gs : st; }
 
 // Full critic loss + gradient.  stats[0..3] = mean D(xg), mean D(xd), penalty, loss.
-hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, const float* xg, const float* cg,
-                            const float* xd, const float* cd, const float* xp, const float* cp, int ng, int nd, int np,
-                            float lmd, int hide_cell_type, float* grads, float* stats, float* dvals, float* ws, bool bf16,
-                            hipStream_t st, float leak, const float* eps, float* xp_out) {
+hipError_t critic_loss_grad(const CriticSpec& c, const float* xg, const float* cg, const float* xd, const float* cd, const float* xp,
+                            const float* cp, int ng, int nd, int np, float lmd, float* grads, float* stats, float* dvals, float* ws,
+                            hipStream_t st, const float* eps, float* xp_out) {
     // eps != nullptr: xp is not an input -- it is formed here, together with the three input blocks, in one launch (xp_out
     // receives it; ng = nd = np and ONE condition array for the three inputs: the single-process critic step)
-    CriticNet net;
-    if (!parse_net(params, dims, nlayers, net, leak)) return hipErrorInvalidValue;
+    CriticLayout net;
+    if (!critic_layout(c, net)) return hipErrorInvalidValue;
+    const int* const dims = net.dims;
     if (eps && (!xp_out || ng != nd || nd != np || cg != cd || cd != cp)) return hipErrorInvalidValue;
     hipError_t e;
     const int nc = (cg || cd || cp) ? 3 : 0;
     if (nc && ((ng && !cg) || (nd && !cd) || (np && !cp))) return hipErrorInvalidValue;   // conditions for all inputs or for none
-    const int L = nlayers, nx = dims[0] - nc;
+    const int L = net.L, nx = dims[0] - nc;
     const int bgd = ng + nd;
     // (the row-block path of wide plain critics zeroes the gradient in its weight-packing launch)
-    const bool rows_path = bf16 && bgd > 0 && np > 0 && critic_rows_supported(dims, nlayers);
+    const bool rows_path = c.bf16 && bgd > 0 && np > 0 && critic_rows_supported(dims, net.L);
     if (!rows_path && (e = hipMemsetAsync(grads, 0, net.nparams * sizeof(float), st)) != hipSuccess) return e;
     float* p = ws;
     // ---------------- (1) mean D(xg) - mean D(xd) on the concatenated batch -------------------
@@ -877,7 +850,7 @@ hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, c
     for (int l = 0; l <= L; ++l) { ep[l] = p; p += (long)np * dims[l]; }
     float* dp = p; p += np;
     float* tmp = p; p += dims[L];
-    critic_splitk_begin(p, critic_splitk_scratch_floats(dims, nlayers, bgd + np));     // the rest of the workspace
+    critic_splitk_begin(p, critic_splitk_scratch_floats(dims, net.L, bgd + np));     // the rest of the workspace
     struct PlanScope { ~PlanScope() { critic_splitk_begin(nullptr, 0); } } plan_scope;    // closed on every return path
     // second stream for the penalty half, when every weight-gradient GEMM of both halves goes to slabs (see critic_fork)
     bool par = np > 0 && bgd > 0 && choose_splits(dims[L], 1, bgd) > 1;
@@ -904,19 +877,19 @@ hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, c
     // then the weight-gradient GEMMs, whose operands are all there, on the three streams.  Same bits as the chains below.
     if (rows_path) {
         if (eps) hipLaunchKernelGGL(critic_step_inputs_kernel, dim3(blocks_for((long)ng * dims[0])), dim3(256), 0, st, xg, xd, cg, eps, xp_out,
-                                    h[0], hp[0], ng, nx, hide_cell_type, nc);
+                                    h[0], hp[0], ng, nx, c.hide_cell_type, nc);
         else {
-            hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)ng * dims[0])), dim3(256), 0, st, xg, cg, h[0], ng, nx, hide_cell_type, nc);
-            hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)nd * dims[0])), dim3(256), 0, st, xd, cd, h[0] + (long)ng * dims[0], nd, nx, hide_cell_type, nc);
-            hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)np * dims[0])), dim3(256), 0, st, xp, cp, hp[0], np, nx, hide_cell_type, nc);
+            hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)ng * dims[0])), dim3(256), 0, st, xg, cg, h[0], ng, nx, c.hide_cell_type, nc);
+            hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)nd * dims[0])), dim3(256), 0, st, xd, cd, h[0] + (long)ng * dims[0], nd, nx, c.hide_cell_type, nc);
+            hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)np * dims[0])), dim3(256), 0, st, xp, cp, hp[0], np, nx, c.hide_cell_type, nc);
         }
         RowsArgs ra{};
-        ra.L = L; ra.leak = leak; ra.mode = 2;
+        ra.L = L; ra.leak = net.act.leak; ra.mode = 2;
         for (int l = 0; l <= L; ++l) { ra.dims[l] = dims[l]; ra.h[l] = h[l]; ra.v[l] = v[l]; ra.hp[l] = hp[l]; ra.vp[l] = vp[l]; ra.ep[l] = ep[l]; }
         ra.up = up; ra.dvals = dvals; ra.ng = ng; ra.nd = nd; ra.np = np; ra.nx = nx;
-        float* const rws = p + critic_splitk_scratch_floats(dims, nlayers, bgd + np);
+        float* const rws = p + critic_splitk_scratch_floats(dims, net.L, bgd + np);
         ra.dnorm = rws;
-        if ((e = critic_rows_pack(params, dims, L, rws + np, ra, grads, net.nparams, st)) != hipSuccess) return e;
+        if ((e = critic_rows_pack(net, rws + np, ra, grads, net.nparams, st)) != hipSuccess) return e;
         if ((e = critic_rows_launch(ra, st)) != hipSuccess) return e;
         // every operand of the weight gradients is there: ONE launch for the GEMMs (split over K into slabs of their own, in the
         // order of the chains below), one for the bias sums, the w_out term of the penalty and the statistics, one for the slabs
@@ -936,7 +909,7 @@ hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, c
             g.B = up; g.sbk = 1; g.sbn = 1;
             g.C = grads + (net.nparams - dims[L]); g.ldc = 1; g.M = dims[L]; g.N = 1; g.K = bgd;
             g.alpha = 1.f; g.beta = 1.f; g.epilogue = EPI_PLAIN;
-            if ((e = gemm(g, bf16, st)) != hipSuccess) return e;
+            if ((e = gemm(g, c.bf16, st)) != hipSuccess) return e;
         }
         long off = net.nparams - dims[L];
         for (int l = L - 1; l >= 0; --l) {              // dW_l += h_l^T v_{l+1},  db_l += colsum(v_{l+1})
@@ -949,7 +922,7 @@ hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, c
             g.B = v[l + 1]; g.sbk = nout; g.sbn = 1;
             g.C = grads + off; g.ldc = nout; g.M = nin; g.N = nout; g.K = bgd;
             g.alpha = 1.f; g.beta = 1.f; g.epilogue = EPI_PLAIN;
-            if ((e = gemm(g, bf16, st)) != hipSuccess) return e;
+            if ((e = gemm(g, c.bf16, st)) != hipSuccess) return e;
             add_colsum(v[l + 1], grads + off_b, bgd, nout, 1.f, nullptr, 0.f);
         }
         off = 0;
@@ -960,7 +933,7 @@ hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, c
             g.B = vp[l + 1]; g.sbk = nout; g.sbn = 1;
             g.C = grads + off; g.ldc = nout; g.M = nin; g.N = nout; g.K = np;
             g.alpha = lmd; g.beta = 1.f; g.epilogue = EPI_PLAIN;
-            if ((e = gemm(g, bf16, st)) != hipSuccess) return e;
+            if ((e = gemm(g, c.bf16, st)) != hipSuccess) return e;
             off += (long)nin * nout + nout;
         }
         if ((e = gemm_batch_flush(st)) != hipSuccess) return e;
@@ -973,7 +946,7 @@ hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, c
     }
     if (eps)        // (in front of the fork: the penalty half reads hp[0])
         hipLaunchKernelGGL(critic_step_inputs_kernel, dim3(blocks_for((long)ng * dims[0])), dim3(256), 0, st, xg, xd, cg, eps, xp_out,
-                           h[0], hp[0], ng, nx, hide_cell_type, nc);
+                           h[0], hp[0], ng, nx, c.hide_cell_type, nc);
     if (fk) {
         if ((e = hipEventRecord(fk->fork, st)) != hipSuccess) return e;          // behind the memset and everything the caller queued
         join_scope.forked = true;
@@ -981,10 +954,10 @@ hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, c
         sp = fk->aux;
     }
     if (!eps) {
-        hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)ng * dims[0])), dim3(256), 0, st, xg, cg, h[0], ng, nx, hide_cell_type, nc);
-        hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)nd * dims[0])), dim3(256), 0, st, xd, cd, h[0] + (long)ng * dims[0], nd, nx, hide_cell_type, nc);
+        hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)ng * dims[0])), dim3(256), 0, st, xg, cg, h[0], ng, nx, c.hide_cell_type, nc);
+        hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)nd * dims[0])), dim3(256), 0, st, xd, cd, h[0] + (long)ng * dims[0], nd, nx, c.hide_cell_type, nc);
     }
-    if ((e = critic_forward_pass(net, h, dvals, bgd, bf16, st)) != hipSuccess) return e;
+    if ((e = critic_forward_pass(net, h, dvals, bgd, c.bf16, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(two_means_kernel, dim3(1), dim3(256), 0, st, dvals, stats, ng, nd);
     hipLaunchKernelGGL(fill_updown_kernel, dim3(blocks_for(bgd)), dim3(256), 0, st, up, ng, nd);
     // d/dw_out = sum_b up_b h_L[b][:]
@@ -995,17 +968,17 @@ hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, c
         g.C = grads + (net.nparams - dims[L]); g.ldc = 1; g.M = dims[L]; g.N = 1; g.K = bgd;
         g.alpha = 1.f; g.beta = 1.f; g.epilogue = EPI_PLAIN;
         if ((e = critic_hand_over(fk, st)) != hipSuccess) return e;              // h[L] and up are queued on st
-        if ((e = gemm(g, bf16, sg)) != hipSuccess) return e;
+        if ((e = gemm(g, c.bf16, sg)) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(critic_outgrad_kernel, dim3(blocks_for((long)bgd * dims[L])), dim3(256), 0, st, h[L], net.wout, up, v[L], bgd, dims[L], net.leak);
-    if ((e = critic_backward_chain(net, h, v, bgd, grads, false, bf16, st, fk)) != hipSuccess) return e;
+    hipLaunchKernelGGL(critic_outgrad_kernel, dim3(blocks_for((long)bgd * dims[L])), dim3(256), 0, st, h[L], net.wout, up, v[L], bgd, dims[L], net.act.leak);
+    if ((e = critic_backward_chain(net, h, v, bgd, grads, false, c.bf16, st, fk)) != hipSuccess) return e;
 
     // ---------------- (2) gradient penalty on xp ------------------------------------------------
-    if (!eps) hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)np * dims[0])), dim3(256), 0, sp, xp, cp, hp[0], np, nx, hide_cell_type, nc);
-    if ((e = critic_forward_pass(net, hp, dp, np, bf16, sp)) != hipSuccess) return e;
+    if (!eps) hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)np * dims[0])), dim3(256), 0, sp, xp, cp, hp[0], np, nx, c.hide_cell_type, nc);
+    if ((e = critic_forward_pass(net, hp, dp, np, c.bf16, sp)) != hipSuccess) return e;
     // input gradient g = dD/dh0 per sample: v_L = m_L * w_out, chain down to vp[0]
-    hipLaunchKernelGGL(critic_outgrad_kernel, dim3(blocks_for((long)np * dims[L])), dim3(256), 0, sp, hp[L], net.wout, (const float*)nullptr, vp[L], np, dims[L], net.leak);
-    if ((e = critic_backward_chain(net, hp, vp, np, nullptr, true, bf16, sp)) != hipSuccess) return e;
+    hipLaunchKernelGGL(critic_outgrad_kernel, dim3(blocks_for((long)np * dims[L])), dim3(256), 0, sp, hp[L], net.wout, (const float*)nullptr, vp[L], np, dims[L], net.act.leak);
+    if ((e = critic_backward_chain(net, hp, vp, np, nullptr, true, c.bf16, sp)) != hipSuccess) return e;
     // penalty and its gradient w.r.t. g: ep[0] = ghat (np x n0)
     hipLaunchKernelGGL(gp_head_kernel, dim3(1), dim3(256), 0, sp, vp[0], ep[0], stats + 2, np, dims[0], nx);
     // backprop through the linear chain g = v_1 W_1^T, v_{l} = m_l * (v_{l+1} W_{l+1}^T), v_L = m_L * w_out:
@@ -1020,15 +993,15 @@ hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, c
             g.C = grads + off; g.ldc = nout; g.M = nin; g.N = nout; g.K = np;
             g.alpha = lmd; g.beta = 1.f; g.epilogue = EPI_PLAIN;
             if ((e = critic_hand_over(fk, sp)) != hipSuccess) return e;          // e_l (and v_{l+1} before it) are queued on sp
-            if ((e = gemm(g, bf16, sg)) != hipSuccess) return e;
+            if ((e = gemm(g, c.bf16, sg)) != hipSuccess) return e;
         }
         {
             GemmArgs g{};                                       // e_{l+1} = m_{l+1} * (e_l W_l)
             g.A = ep[l]; g.sam = nin; g.sak = 1;
             g.B = net.W[l]; g.sbk = nout; g.sbn = 1;
             g.C = ep[l + 1]; g.ldc = nout; g.M = np; g.N = nout; g.K = nin;
-            g.epilogue = EPI_MASK; g.mask = hp[l + 1]; g.ldm = nout; g.leak = net.leak;
-            if ((e = gemm(g, bf16, sp)) != hipSuccess) return e;
+            g.epilogue = EPI_MASK; g.mask = hp[l + 1]; g.ldm = nout; g.leak = net.act.leak;
+            if ((e = gemm(g, c.bf16, sp)) != hipSuccess) return e;
         }
         off += (long)nin * nout + nout;
     }
@@ -1046,28 +1019,28 @@ hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, c
 
 // Gradient of  -mean D(x)  w.r.t. the tuning-curve part of the input (generator side, wgan.py:236):
 // gx[batch][nx];  also returns mean D in stats[0].
-hipError_t critic_input_grad(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
-                             int hide_cell_type, float scale, float* gx, float* stats, float* ws, bool bf16, hipStream_t st,
-                             float leak) {
-    CriticNet net;
-    if (!parse_net(params, dims, nlayers, net, leak)) return hipErrorInvalidValue;
+hipError_t critic_input_grad(const CriticSpec& c, const float* x, const float* cond, int batch, float scale, float* gx, float* stats,
+                             float* ws, hipStream_t st) {
+    CriticLayout net;
+    if (!critic_layout(c, net)) return hipErrorInvalidValue;
+    const int* const dims = net.dims;
     hipError_t e;
-    const int L = nlayers, nc = cond ? 3 : 0, nx = dims[0] - nc;
+    const int L = net.L, nc = cond ? 3 : 0, nx = dims[0] - nc;
     float *h[10], *v[10];
     float* p = ws;
     for (int l = 0; l <= L; ++l) { h[l] = p; p += (long)batch * dims[l]; }
     for (int l = 0; l <= L; ++l) { v[l] = p; p += (long)batch * dims[l]; }
     float* dv = p; p += batch;
-    hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)batch * dims[0])), dim3(256), 0, st, x, cond, h[0], batch, nx, hide_cell_type, nc);
-    if (bf16 && batch > 0 && critic_rows_supported(dims, nlayers)) {
-        if ((e = critic_rows_eval(params, dims, nlayers, h[0], batch, dv, 1, gx, scale, nx, leak, p, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)batch * dims[0])), dim3(256), 0, st, x, cond, h[0], batch, nx, c.hide_cell_type, nc);
+    if (c.bf16 && batch > 0 && critic_rows_supported(dims, net.L)) {
+        if ((e = critic_rows_eval(net, h[0], batch, dv, 1, gx, scale, nx, p, st)) != hipSuccess) return e;
         hipLaunchKernelGGL(two_means_kernel, dim3(1), dim3(256), 0, st, dv, stats, batch, 0);
         return hipGetLastError();
     }
-    if ((e = critic_forward_pass(net, h, dv, batch, bf16, st)) != hipSuccess) return e;
+    if ((e = critic_forward_pass(net, h, dv, batch, c.bf16, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(two_means_kernel, dim3(1), dim3(256), 0, st, dv, stats, batch, 0);
-    hipLaunchKernelGGL(critic_outgrad_kernel, dim3(blocks_for((long)batch * dims[L])), dim3(256), 0, st, h[L], net.wout, (const float*)nullptr, v[L], batch, dims[L], net.leak);
-    if ((e = critic_backward_chain(net, h, v, batch, nullptr, true, bf16, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(critic_outgrad_kernel, dim3(blocks_for((long)batch * dims[L])), dim3(256), 0, st, h[L], net.wout, (const float*)nullptr, v[L], batch, dims[L], net.act.leak);
+    if ((e = critic_backward_chain(net, h, v, batch, nullptr, true, c.bf16, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(gather_scale_kernel, dim3(blocks_for((long)batch * nx)), dim3(256), 0, st, v[0], gx, batch, dims[0], nx, scale);
     return hipGetLastError();
 }

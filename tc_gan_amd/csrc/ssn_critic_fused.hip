@@ -368,22 +368,21 @@ bool critic_fused_supported(const int* dims, int nlayers) {
     return dims[0] > 3;
 }
 
-static bool parse_fused(const float* params, const int* dims, const int* norm, int nlayers, FusedNet& net) {
-    if (!critic_fused_supported(dims, nlayers)) return false;
-    net.L = nlayers;
-    long off = 0;
-    for (int l = 0; l <= nlayers; ++l) net.dims[l] = dims[l];
-    for (int l = 0; l < nlayers; ++l) {
-        net.ln[l] = norm ? norm[l] : 0;
-        net.offW[l] = off; net.W[l] = params + off; off += (long)dims[l] * dims[l + 1];
-        net.offb[l] = off; net.b[l] = params + off; off += dims[l + 1];
+// The kernels' copy of the layout.  They compute rectify without scales at the sizes of critic_fused_supported: anything else
+// is refused here rather than computed as something it is not.
+static bool fused_net(const CriticSpec& c, FusedNet& net) {
+    CriticLayout lay;
+    if (!critic_fused_supported(c.dims, c.nlayers) || !critic_layout(c, lay)) return false;
+    if (lay.scaled || lay.smooth || lay.act.leak != 0.f) return false;
+    net.L = lay.L;
+    for (int l = 0; l <= lay.L; ++l) net.dims[l] = lay.dims[l];
+    for (int l = 0; l < lay.L; ++l) {
+        net.ln[l] = lay.ln[l];
+        net.W[l] = lay.W[l]; net.b[l] = lay.b[l]; net.offW[l] = lay.offW[l]; net.offb[l] = lay.offb[l];
     }
-    net.offout = off; net.wout = params + off; off += dims[nlayers];
-    net.nparams = off;
+    net.wout = lay.wout; net.offout = lay.offout; net.nparams = lay.nparams;
     return true;
 }
-
-static float* fcarve(float*& p, long n) { float* r = p; p += n; return r; }
 
 size_t critic_fused_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p) {
     long per_row = 0;
@@ -395,15 +394,15 @@ size_t critic_fused_workspace_floats(const int* dims, int nlayers, int batch_gd,
 
 static void carve_fused(float*& p, const FusedNet& net, int rows, int np, FusedArgs& a) {
     for (int l = 0; l <= net.L; ++l) {
-        a.A.h[l] = fcarve(p, (long)rows * net.dims[l]); a.A.y[l] = fcarve(p, (long)rows * net.dims[l]);
-        a.A.invs[l] = fcarve(p, rows); a.A.u[l] = fcarve(p, (long)rows * net.dims[l]);
-        a.A.p[l] = fcarve(p, (long)rows * net.dims[l]); a.A.c[l] = fcarve(p, (long)rows * net.dims[l]);
+        a.A.h[l] = carve(p, (long)rows * net.dims[l]); a.A.y[l] = carve(p, (long)rows * net.dims[l]);
+        a.A.invs[l] = carve(p, rows); a.A.u[l] = carve(p, (long)rows * net.dims[l]);
+        a.A.p[l] = carve(p, (long)rows * net.dims[l]); a.A.c[l] = carve(p, (long)rows * net.dims[l]);
     }
-    a.up = fcarve(p, rows); a.dall = fcarve(p, rows);
+    a.up = carve(p, rows); a.dall = carve(p, rows);
     for (int l = 0; l <= net.L; ++l) {
-        a.P.du[l] = fcarve(p, (long)np * net.dims[l]); a.P.dc[l] = fcarve(p, (long)np * net.dims[l]);
-        a.P.dyA[l] = fcarve(p, (long)np * net.dims[l]); a.P.dpre[l] = fcarve(p, (long)np * net.dims[l]);
-        a.P.da[l] = fcarve(p, (long)np * net.dims[l]); a.P.dsA[l] = fcarve(p, np);
+        a.P.du[l] = carve(p, (long)np * net.dims[l]); a.P.dc[l] = carve(p, (long)np * net.dims[l]);
+        a.P.dyA[l] = carve(p, (long)np * net.dims[l]); a.P.dpre[l] = carve(p, (long)np * net.dims[l]);
+        a.P.da[l] = carve(p, (long)np * net.dims[l]); a.P.dsA[l] = carve(p, np);
     }
 }
 
@@ -418,30 +417,28 @@ static hipError_t launch_rows(const FusedArgs& a, int rb, int nblocks, hipStream
     return hipGetLastError();
 }
 
-hipError_t critic_fused_forward(const float* params, const int* dims, const int* norm, int nlayers, const float* x,
-                                const float* cond, int batch, int hide, float* out, float* ws, hipStream_t st) {
+hipError_t critic_fused_forward(const CriticSpec& c, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st) {
     FusedArgs a{};
-    if (!parse_fused(params, dims, norm, nlayers, a.net)) return hipErrorInvalidValue;
+    if (!fused_net(c, a.net)) return hipErrorInvalidValue;
     float* p = ws;
     carve_fused(p, a.net, batch, 0, a);
-    a.xg = x; a.cg = cond; a.ng = batch; a.nd = 0; a.np = 0; a.hide = hide; a.mode = 0; a.part = nullptr;
+    a.xg = x; a.cg = cond; a.ng = batch; a.nd = 0; a.np = 0; a.hide = c.hide_cell_type; a.mode = 0; a.part = nullptr;
     const int rb = fused_rb(batch);
     a.nb_gd = (batch + rb - 1) / rb;
     a.dout = out; a.ndout = batch;
     return launch_rows(a, rb, a.nb_gd, st);
 }
 
-hipError_t critic_fused_input_grad(const float* params, const int* dims, const int* norm, int nlayers, const float* x,
-                                   const float* cond, int batch, int hide, float scale, float* gx, float* stats, float* ws,
-                                   hipStream_t st) {
+hipError_t critic_fused_input_grad(const CriticSpec& c, const float* x, const float* cond, int batch, float scale, float* gx,
+                                   float* stats, float* ws, hipStream_t st) {
     FusedArgs a{};
-    if (!parse_fused(params, dims, norm, nlayers, a.net)) return hipErrorInvalidValue;
+    if (!fused_net(c, a.net)) return hipErrorInvalidValue;
     float* p = ws;
     carve_fused(p, a.net, batch, 0, a);
-    a.xg = x; a.cg = cond; a.ng = batch; a.nd = 0; a.np = 0; a.hide = hide; a.mode = 1; a.scale = scale; a.gx = gx;
+    a.xg = x; a.cg = cond; a.ng = batch; a.nd = 0; a.np = 0; a.hide = c.hide_cell_type; a.mode = 1; a.scale = scale; a.gx = gx;
     const int rb = fused_rb(batch);
     a.nb_gd = (batch + rb - 1) / rb;
-    a.part = fcarve(p, (long)a.nb_gd * 4);
+    a.part = carve(p, (long)a.nb_gd * 4);
     hipError_t e = launch_rows(a, rb, a.nb_gd, st);
     if (e != hipSuccess) return e;
     WgradArgs w{};                                       // no tensors: workgroup 0 only adds the block sums of D
@@ -452,22 +449,21 @@ hipError_t critic_fused_input_grad(const float* params, const int* dims, const i
     return hipGetLastError();
 }
 
-hipError_t critic_fused_loss_grad(const float* params, const int* dims, const int* norm, int nlayers, const float* xg,
-                                  const float* cg, const float* xd, const float* cd, const float* xp, const float* cp, int ng,
-                                  int nd, int np, float lmd, int hide, float* grads, float* stats, float* dvals, float* ws,
-                                  hipStream_t st) {
+hipError_t critic_fused_loss_grad(const CriticSpec& c, const float* xg, const float* cg, const float* xd, const float* cd,
+                                  const float* xp, const float* cp, int ng, int nd, int np, float lmd, float* grads, float* stats,
+                                  float* dvals, float* ws, hipStream_t st) {
     FusedArgs a{};
-    if (!parse_fused(params, dims, norm, nlayers, a.net)) return hipErrorInvalidValue;
+    if (!fused_net(c, a.net)) return hipErrorInvalidValue;
     const FusedNet& net = a.net;
     const int L = net.L, bgd = ng + nd, rows = bgd + np;
     float* p = ws;
     carve_fused(p, net, rows, np, a);
-    a.xg = xg; a.cg = cg; a.xd = xd; a.cd = cd; a.xp = xp; a.cp = cp; a.ng = ng; a.nd = nd; a.np = np; a.hide = hide;
+    a.xg = xg; a.cg = cg; a.xd = xd; a.cd = cd; a.xp = xp; a.cp = cp; a.ng = ng; a.nd = nd; a.np = np; a.hide = c.hide_cell_type;
     a.lmd = lmd; a.mode = 2;
     const int rb = fused_rb(rows);
     a.nb_gd = (bgd + rb - 1) / rb;
     const int nb_p = (np + rb - 1) / rb, nblocks = a.nb_gd + nb_p;
-    a.part = fcarve(p, (long)nblocks * 4);
+    a.part = carve(p, (long)nblocks * 4);
     a.dout = dvals; a.ndout = bgd;
     hipError_t e = launch_rows(a, rb, nblocks, st);
     if (e != hipSuccess) return e;

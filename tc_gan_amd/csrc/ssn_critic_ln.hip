@@ -39,9 +39,7 @@ hipError_t critic_gather_scale(const float* v0, float* gx, int batch, int n0, in
 
 constexpr float LN_EPS = 1e-4f;
 
-// hidden nonlinearity: kind 0 = x > 0 ? x : leak x (rectify 0, leaky_rectify 0.01, very_leaky_rectify 1/3, linear 1),
-// 1 tanh, 2 sigmoid, 3 softplus (log1p(exp x)), 4 elu (x > 0 ? x : expm1 x)  -- lasagne.nonlinearities
-struct ActSpec { int kind; float leak; };
+// hidden nonlinearity: ActSpec of ssn_host.h
 __device__ __forceinline__ float act_f(const ActSpec a, float x) {
     switch (a.kind) {
         case 1: return tanhf(x);
@@ -200,59 +198,10 @@ __global__ void __launch_bounds__(256) scale_kernel(float* x, float a, long n) {
     for (long e = blockIdx.x * 256L + threadIdx.x; e < n; e += gridDim.x * 256L) x[e] *= a;
 }
 
-static int nblk(long n) { long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
-
-struct NormNet {
-    int L; int dims[10]; int ln[9];
-    const float* W[9]; const float* g[9]; const float* b[9]; const float* wout; long offW[9], offg[9], offb[9], offout, nparams;
-    ActSpec act; bool smooth, scaled;
-};
-// layer flags: bit 0 = layer normalisation, bit 1 = learnable scale after it (parameter order W, scales, b: lasagne's
-// get_all_params of Dense(no bias) -> LayerNorm -> ScaleLayer -> BiasLayer).  act: the public activation codes.
-static bool act_from_code(int code, ActSpec& a) {
-    switch (code) {
-        case 0: a = {0, 0.f}; return true;            // rectify
-        case 1: a = {0, 0.01f}; return true;          // leaky_rectify
-        case 2: a = {0, 1.f / 3.f}; return true;      // very_leaky_rectify
-        case 3: a = {0, 1.f}; return true;            // linear / identity
-        case 4: a = {1, 0.f}; return true;            // tanh
-        case 5: a = {2, 0.f}; return true;            // sigmoid
-        case 6: a = {3, 0.f}; return true;            // softplus
-        case 7: a = {4, 0.f}; return true;            // elu
-        default: return false;
-    }
-}
-static bool parse_norm_net(const float* params, const int* dims, const int* norm, int nlayers, NormNet& net, int act_code = 0) {
-    if (nlayers < 0 || nlayers > 8) return false;
-    if (!act_from_code(act_code, net.act)) return false;
-    net.smooth = net.act.kind != 0;
-    net.scaled = false;
-    net.L = nlayers;
-    long off = 0;
-    for (int l = 0; l <= nlayers; ++l) net.dims[l] = dims[l];
-    for (int l = 0; l < nlayers; ++l) {
-        const int flags = norm ? norm[l] : 0;
-        if (flags < 0 || flags > 3 || flags == 2) return false;      // a scale only follows a normalisation
-        net.ln[l] = flags & 1;
-        net.offW[l] = off; net.W[l] = params ? params + off : nullptr; off += (long)dims[l] * dims[l + 1];
-        net.g[l] = nullptr; net.offg[l] = -1;
-        if (flags & 2) { net.offg[l] = off; net.g[l] = params ? params + off : nullptr; off += dims[l + 1]; net.scaled = true; }
-        net.offb[l] = off; net.b[l] = params ? params + off : nullptr; off += dims[l + 1];
-    }
-    net.offout = off; net.wout = params ? params + off : nullptr; off += dims[nlayers];
-    net.nparams = off;
-    return true;
-}
-long critic_act_num_params(const int* dims, const int* flags, int nlayers) {
-    NormNet net;
-    return parse_norm_net(nullptr, dims, flags, nlayers, net) ? net.nparams : -1;
-}
-
 struct Acts {            // per batch of rows
     float *h[10], *y[10], *invs[10], *u[10], *p[10], *c[10], *py[10];
 };
-static float* carve(float*& p, long n) { float* r = p; p += n; return r; }
-static void carve_acts(float*& p, const NormNet& net, int rows, Acts& A) {
+static void carve_acts(float*& p, const CriticLayout& net, int rows, Acts& A) {
     for (int l = 0; l <= net.L; ++l) {
         A.h[l] = carve(p, (long)rows * net.dims[l]);
         A.y[l] = carve(p, (long)rows * net.dims[l]);
@@ -264,7 +213,7 @@ static void carve_acts(float*& p, const NormNet& net, int rows, Acts& A) {
     }
 }
 
-static hipError_t norm_forward(const NormNet& net, const Acts& A, float* dout, int rows, bool bf16, hipStream_t st) {
+static hipError_t norm_forward(const CriticLayout& net, const Acts& A, float* dout, int rows, bool bf16, hipStream_t st) {
     hipError_t e;
     for (int l = 0; l < net.L; ++l) {
         const int nin = net.dims[l], nout = net.dims[l + 1];
@@ -277,10 +226,10 @@ static hipError_t norm_forward(const NormNet& net, const Acts& A, float* dout, i
 }
 
 // input-gradient chain given per-row upstream `up` of D: fills p, c, u; u[0] = dD/dh0 (times up)
-static hipError_t norm_chain(const NormNet& net, const Acts& A, const float* up, int rows, bool bf16, hipStream_t st) {
+static hipError_t norm_chain(const CriticLayout& net, const Acts& A, const float* up, int rows, bool bf16, hipStream_t st) {
     hipError_t e;
     const int L = net.L;
-    hipLaunchKernelGGL(top_seed_kernel, dim3(nblk((long)rows * net.dims[L])), dim3(256), 0, st, net.wout, up, A.u[L], rows, net.dims[L]);
+    hipLaunchKernelGGL(top_seed_kernel, dim3(blocks_for((long)rows * net.dims[L])), dim3(256), 0, st, net.wout, up, A.u[L], rows, net.dims[L]);
     for (int l = L; l >= 1; --l) {
         const int nin = net.dims[l - 1], nout = net.dims[l];
         // p_l = f'(pre_l) u_l ; c_l = LNback(g_l p_l)
@@ -293,7 +242,7 @@ static hipError_t norm_chain(const NormNet& net, const Acts& A, const float* up,
 }
 
 // standard parameter gradient of sum_b up_b D_b given the chain results (c_l = dL/da_l, p_l = dL/dpre_l)
-static hipError_t norm_param_grads(const NormNet& net, const Acts& A, const float* up, float* grads, int rows, bool bf16, hipStream_t st) {
+static hipError_t norm_param_grads(const CriticLayout& net, const Acts& A, const float* up, float* grads, int rows, bool bf16, hipStream_t st) {
     hipError_t e;
     const int L = net.L;
     // w_out: sum_b up_b h_L
@@ -316,45 +265,45 @@ size_t critic_norm_workspace_floats(const int* dims, int nlayers, int batch_gd, 
            critic_splitk_scratch_floats(dims, nlayers, batch_gd + batch_p);
 }
 
-hipError_t critic_norm_forward(const float* params, const int* dims, const int* norm, int nlayers, const float* x,
-                               const float* cond, int batch, int hide, float* out, float* ws, bool bf16, hipStream_t st, int act) {
-    NormNet net;
-    if (!parse_norm_net(params, dims, norm, nlayers, net, act)) return hipErrorInvalidValue;
+hipError_t critic_norm_forward(const CriticSpec& c, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st) {
+    CriticLayout net;
+    if (!critic_layout(c, net)) return hipErrorInvalidValue;
+    const int* const dims = net.dims;
     hipError_t e;
     float* p = ws;
     Acts A;
     carve_acts(p, net, batch, A);
-    if ((e = critic_make_input(x, cond, A.h[0], batch, dims[0] - (cond ? 3 : 0), hide, st)) != hipSuccess) return e;
-    return norm_forward(net, A, out, batch, bf16, st);
+    if ((e = critic_make_input(x, cond, A.h[0], batch, dims[0] - (cond ? 3 : 0), c.hide_cell_type, st)) != hipSuccess) return e;
+    return norm_forward(net, A, out, batch, c.bf16, st);
 }
 
-hipError_t critic_norm_input_grad(const float* params, const int* dims, const int* norm, int nlayers, const float* x,
-                                  const float* cond, int batch, int hide, float scale, float* gx, float* stats, float* ws,
-                                  bool bf16, hipStream_t st, int act) {
-    NormNet net;
-    if (!parse_norm_net(params, dims, norm, nlayers, net, act)) return hipErrorInvalidValue;
+hipError_t critic_norm_input_grad(const CriticSpec& c, const float* x, const float* cond, int batch, float scale, float* gx,
+                                  float* stats, float* ws, hipStream_t st) {
+    CriticLayout net;
+    if (!critic_layout(c, net)) return hipErrorInvalidValue;
+    const int* const dims = net.dims;
     hipError_t e;
     float* p = ws;
     Acts A;
     carve_acts(p, net, batch, A);
     float* dv = carve(p, batch);
-    if ((e = critic_make_input(x, cond, A.h[0], batch, dims[0] - (cond ? 3 : 0), hide, st)) != hipSuccess) return e;
-    if ((e = norm_forward(net, A, dv, batch, bf16, st)) != hipSuccess) return e;
+    if ((e = critic_make_input(x, cond, A.h[0], batch, dims[0] - (cond ? 3 : 0), c.hide_cell_type, st)) != hipSuccess) return e;
+    if ((e = norm_forward(net, A, dv, batch, c.bf16, st)) != hipSuccess) return e;
     if ((e = critic_two_means(dv, stats, batch, 0, st)) != hipSuccess) return e;
-    if ((e = norm_chain(net, A, nullptr, batch, bf16, st)) != hipSuccess) return e;
+    if ((e = norm_chain(net, A, nullptr, batch, c.bf16, st)) != hipSuccess) return e;
     return critic_gather_scale(A.u[0], gx, batch, dims[0], dims[0] - (cond ? 3 : 0), scale, st);
 }
 
-hipError_t critic_norm_loss_grad(const float* params, const int* dims, const int* norm, int nlayers, const float* xg,
-                                 const float* cg, const float* xd, const float* cd, const float* xp, const float* cp, int ng,
-                                 int nd, int np, float lmd, int hide, float* grads, float* stats, float* dvals, float* ws,
-                                 bool bf16, hipStream_t st, int act) {
-    NormNet net;
-    if (!parse_norm_net(params, dims, norm, nlayers, net, act)) return hipErrorInvalidValue;
+hipError_t critic_norm_loss_grad(const CriticSpec& c, const float* xg, const float* cg, const float* xd, const float* cd,
+                                 const float* xp, const float* cp, int ng, int nd, int np, float lmd, float* grads, float* stats,
+                                 float* dvals, float* ws, hipStream_t st) {
+    CriticLayout net;
+    if (!critic_layout(c, net)) return hipErrorInvalidValue;
+    const int* const dims = net.dims;
     hipError_t e;
     const int nc = (cg || cd || cp) ? 3 : 0;            // (no condition columns: the unconditional critic, networks/wgan.py:66-97)
     if (nc && ((ng && !cg) || (nd && !cd) || (np && !cp))) return hipErrorInvalidValue;
-    const int L = nlayers, nx = dims[0] - nc, bgd = ng + nd;
+    const int L = net.L, nx = dims[0] - nc, bgd = ng + nd;
     if ((e = hipMemsetAsync(grads, 0, net.nparams * sizeof(float), st)) != hipSuccess) return e;
     float* p = ws;
     // The rows of the three inputs are STACKED ([xg; xd; xp]): one forward pass and one backward chain over
@@ -384,27 +333,27 @@ hipError_t critic_norm_loss_grad(const float* params, const int* dims, const int
     }
     float* prod = net.scaled ? carve(p, (long)np * maxd) : nullptr;       // dq p, then dpre y: summed over the rows at once
     // (dh_{l-1} of sweep 2 is written into dc[l-1], which is free by then)
-    critic_splitk_begin(p, critic_splitk_scratch_floats(dims, nlayers, rows));      // the rest of the workspace
+    critic_splitk_begin(p, critic_splitk_scratch_floats(dims, L, rows));      // the rest of the workspace
     struct PlanScope { ~PlanScope() { critic_splitk_begin(nullptr, 0); } } plan_scope;    // closed on every return path
-    if ((e = critic_make_input(xg, cg, A.h[0], ng, nx, hide, st)) != hipSuccess) return e;
-    if ((e = critic_make_input(xd, cd, A.h[0] + (long)ng * dims[0], nd, nx, hide, st)) != hipSuccess) return e;
-    if ((e = critic_make_input(xp, cp, P.h[0], np, nx, hide, st)) != hipSuccess) return e;
-    if ((e = norm_forward(net, A, dall, rows, bf16, st)) != hipSuccess) return e;
+    if ((e = critic_make_input(xg, cg, A.h[0], ng, nx, c.hide_cell_type, st)) != hipSuccess) return e;
+    if ((e = critic_make_input(xd, cd, A.h[0] + (long)ng * dims[0], nd, nx, c.hide_cell_type, st)) != hipSuccess) return e;
+    if ((e = critic_make_input(xp, cp, P.h[0], np, nx, c.hide_cell_type, st)) != hipSuccess) return e;
+    if ((e = norm_forward(net, A, dall, rows, c.bf16, st)) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(dvals, dall, sizeof(float) * bgd, hipMemcpyDeviceToDevice, st)) != hipSuccess) return e;
     if ((e = critic_two_means(dall, stats, ng, nd, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(fill_updown2_kernel, dim3(nblk(rows)), dim3(256), 0, st, up, ng, nd, np);
-    if ((e = norm_chain(net, A, up, rows, bf16, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(fill_updown2_kernel, dim3(blocks_for(rows)), dim3(256), 0, st, up, ng, nd, np);
+    if ((e = norm_chain(net, A, up, rows, c.bf16, st)) != hipSuccess) return e;
     // ---- (1) mean D(xg) - mean D(xd): parameter gradients from the first bgd rows ---------------------
-    if ((e = norm_param_grads(net, A, up, grads, bgd, bf16, st)) != hipSuccess) return e;
+    if ((e = norm_param_grads(net, A, up, grads, bgd, c.bf16, st)) != hipSuccess) return e;
     // ---- (2) gradient penalty on the last np rows -----------------------------------------------------
     // du_0 = lmd * dP/dg
     if ((e = critic_gp_head(P.u[0], du[0], stats + 2, np, dims[0], nx, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(scale_kernel, dim3(nblk((long)np * dims[0])), dim3(256), 0, st, du[0], lmd, (long)np * dims[0]);
+    hipLaunchKernelGGL(scale_kernel, dim3(blocks_for((long)np * dims[0])), dim3(256), 0, st, du[0], lmd, (long)np * dims[0]);
     // sweep 1
     for (int l = 1; l <= L; ++l) {
         const int nin = dims[l - 1], nout = dims[l];
-        if ((e = critic_gemm(du[l - 1], 1, nin, P.c[l], nout, 1, grads + net.offW[l - 1], nout, nin, nout, np, 1.f, 1.f, bf16, st)) != hipSuccess) return e;
-        if ((e = critic_gemm(du[l - 1], nin, 1, net.W[l - 1], nout, 1, dc[l], nout, np, nout, nin, 1.f, 0.f, bf16, st)) != hipSuccess) return e;
+        if ((e = critic_gemm(du[l - 1], 1, nin, P.c[l], nout, 1, grads + net.offW[l - 1], nout, nin, nout, np, 1.f, 1.f, c.bf16, st)) != hipSuccess) return e;
+        if ((e = critic_gemm(du[l - 1], nin, 1, net.W[l - 1], nout, 1, dc[l], nout, np, nout, nin, 1.f, 0.f, c.bf16, st)) != hipSuccess) return e;
         float* gp = net.g[l - 1] ? prod : nullptr;
         hipLaunchKernelGGL(ln_sweep1_kernel, dim3(np), dim3(64), 0, st, dc[l], P.p[l], P.c[l], P.y[l], P.invs[l], net.g[l - 1],
                            net.b[l - 1], P.u[l], du[l], dyA[l], dsA[l], preA[l], gp, nout, net.ln[l - 1], net.act);
@@ -421,9 +370,9 @@ hipError_t critic_norm_loss_grad(const float* params, const int* dims, const int
                            P.y[l], P.invs[l], dpre[l], da[l], gp, nout, net.ln[l - 1], net.act);
         if ((e = critic_colsum(dpre[l], grads + net.offb[l - 1], np, nout, 1.f, st)) != hipSuccess) return e;
         if (gp && (e = critic_colsum(gp, grads + net.offg[l - 1], np, nout, 1.f, st)) != hipSuccess) return e;
-        if ((e = critic_gemm(P.h[l - 1], 1, nin, da[l], nout, 1, grads + net.offW[l - 1], nout, nin, nout, np, 1.f, 1.f, bf16, st)) != hipSuccess) return e;
+        if ((e = critic_gemm(P.h[l - 1], 1, nin, da[l], nout, 1, grads + net.offW[l - 1], nout, nin, nout, np, 1.f, 1.f, c.bf16, st)) != hipSuccess) return e;
         if (l > 1) {
-            if ((e = critic_gemm(da[l], nout, 1, net.W[l - 1], 1, nout, dc[l - 1], nin, np, nin, nout, 1.f, 0.f, bf16, st)) != hipSuccess) return e;
+            if ((e = critic_gemm(da[l], nout, 1, net.W[l - 1], 1, nout, dc[l - 1], nin, np, nin, nout, 1.f, 0.f, c.bf16, st)) != hipSuccess) return e;
             dh_cur = dc[l - 1];
         }
     }

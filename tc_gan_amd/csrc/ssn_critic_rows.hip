@@ -364,27 +364,28 @@ size_t critic_rows_workspace_floats(const int* dims, int nlayers, int batch_p) {
     return (size_t)(rows_pack_halfs(dims, nlayers, nullptr, nullptr, nullptr) + 1) / 2 + (size_t)batch_p + 16;
 }
 
-hipError_t critic_rows_pack(const float* params, const int* dims, int L, float* ws_pack, RowsArgs& ra, float* zero, long nzero, hipStream_t st) {
+hipError_t critic_rows_pack(const CriticLayout& net, float* ws_pack, RowsArgs& ra, float* zero, long nzero, hipStream_t st) {
+    const int* const dims = net.dims;
+    const int L = net.L;
     long off_f[9], off_b[9], off_o;
     rows_pack_halfs(dims, L, off_f, off_b, &off_o);
     unsigned short* base = reinterpret_cast<unsigned short*>((reinterpret_cast<size_t>(ws_pack) + 15) & ~(size_t)15);
     RowsPackArgs pa{};
-    long start = 0, poff = 0;
+    long start = 0;
     int ns = 0;
     for (int l = 0; l < L; ++l) {
         const int nin = dims[l], nout = dims[l + 1];
-        const float* W = params + poff;
+        const float* W = net.W[l];
         RowsPackSeg f{W, base + off_f[l], nin, nout, nout / 32, (nin + 15) / 16, 0, start};
         pa.seg[ns++] = f; start += (long)f.NT * f.KS * 64;
         RowsPackSeg b{W, base + off_b[l], nin, nout, (nin + 31) / 32, nout / 16, 1, start};
         pa.seg[ns++] = b; start += (long)b.NT * b.KS * 64;
         ra.pf[l] = f.dst; ra.pb[l] = b.dst;
-        ra.b[l] = W + (long)nin * nout;
-        poff += (long)nin * nout + nout;
+        ra.b[l] = net.b[l];
     }
-    RowsPackSeg o{params + poff, base + off_o, dims[L], 1, 1, dims[L] / 16, 2, start};
+    RowsPackSeg o{net.wout, base + off_o, dims[L], 1, 1, dims[L] / 16, 2, start};
     pa.seg[ns++] = o; start += (long)o.NT * o.KS * 64;
-    ra.po = o.dst; ra.wout = params + poff;
+    ra.po = o.dst; ra.wout = net.wout;
     pa.nseg = ns; pa.total = start;
     pa.zero = zero; pa.nzero = zero ? nzero : 0;
     long zblocks = (pa.nzero + 1023) / 1024;            // four elements per thread of the zeroing blocks

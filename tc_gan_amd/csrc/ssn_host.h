@@ -202,36 +202,82 @@ struct OptArgs {
     // the gradient (a draw whose fp16 adjoint outgrew its scale) and applies that
     int skip_nonfinite = 0;
 };
-size_t critic_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p);
-hipError_t critic_forward(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
-                          int hide_cell_type, float* out, float* ws, bool bf16, hipStream_t st, float leak = 0.f);
-hipError_t critic_forward2(const float* params, const int* dims, int nlayers, const float* xa, const float* ca, int na,
-                           const float* xb, const float* cb, int nb, int hide_cell_type, float* out, float* ws, bool bf16,
-                           hipStream_t st, float leak = 0.f, bool inputs_ready = false);
-// (inputs_ready: ws already starts with the input block of [xa; xb] -- critic_loss_grad on the same rows leaves it there)
-hipError_t critic_loss_grad(const float* params, const int* dims, int nlayers, const float* xg, const float* cg,
-                            const float* xd, const float* cd, const float* xp, const float* cp, int ng, int nd, int np,
-                            float lmd, int hide_cell_type, float* grads, float* stats, float* dvals, float* ws, bool bf16,
-                            hipStream_t st, float leak = 0.f, const float* eps = nullptr, float* xp_out = nullptr);
-// (leak: slope of the hidden nonlinearity below zero -- 0 rectify, 0.01 leaky_rectify, 1/3 very_leaky_rectify, 1 linear)
-hipError_t critic_input_grad(const float* params, const int* dims, int nlayers, const float* x, const float* cond, int batch,
-                             int hide_cell_type, float scale, float* gx, float* stats, float* ws, bool bf16, hipStream_t st,
-                             float leak = 0.f);
 hipError_t optimizer_step(const OptArgs& o, hipStream_t st);
-// ssn_critic_ln.hip (per-layer LayerNorm flags; norm == nullptr -> all plain layers)
+
+// ---- the WGAN-GP critic: ONE description (CriticSpec, filled by the C surface) and ONE walk of its flat parameter vector
+// (critic_layout) for the three back ends below
+// hidden nonlinearity: kind 0 = x > 0 ? x : leak x (rectify 0, leaky_rectify 0.01, very_leaky_rectify 1/3, linear 1),
+// 1 tanh, 2 sigmoid, 3 softplus (log1p(exp x)), 4 elu (x > 0 ? x : expm1 x)  -- lasagne.nonlinearities
+struct ActSpec { int kind; float leak; };      // (goes to the kernels of ssn_critic_ln.hip by value)
+// the public activation codes: 0 rectify, 1 leaky_rectify, 2 very_leaky_rectify, 3 linear, 4 tanh, 5 sigmoid, 6 softplus, 7 elu
+inline bool act_from_code(int code, ActSpec& a) {
+    constexpr ActSpec table[8] = {{0, 0.f}, {0, 0.01f}, {0, 1.f / 3.f}, {0, 1.f}, {1, 0.f}, {2, 0.f}, {3, 0.f}, {4, 0.f}};
+    if (code < 0 || code > 7) return false;
+    a = table[code];
+    return true;
+}
+struct CriticSpec {
+    const float* params; const int* dims;
+    const int* flags;        // HOST int[nlayers] or NULL (all plain): bit 0 = layer normalisation, bit 1 = learnable scale after it
+    int nlayers;
+    int act;                 // the public activation code
+    float leak;              // slope below zero of a piecewise-linear act: the code's own, or any value in [0, 1] under code 0
+                             // (the _leaky entry points, ssn_critic_step.leak)
+    int hide_cell_type; bool bf16;
+};
+// Parameter order per layer: W, [scales], b -- lasagne's get_all_params of Dense(no bias) -> LayerNorm -> ScaleLayer -> BiasLayer;
+// then w_out.  Pointers are null when spec.params is (counting).
+struct CriticLayout {
+    int L; int dims[10]; int ln[9];
+    const float *W[9], *g[9], *b[9], *wout; long offW[9], offg[9], offb[9], offout, nparams;      // g / offg: nullptr / -1 without a scale
+    ActSpec act; bool smooth, scaled;
+};
+inline bool critic_layout(const CriticSpec& c, CriticLayout& net) {
+    if (c.nlayers < 0 || c.nlayers > 8 || !act_from_code(c.act, net.act) || !(c.leak >= 0.f) || c.leak > 1.f) return false;
+    net.smooth = net.act.kind != 0;
+    if (!net.smooth) net.act.leak = c.leak;
+    net.scaled = false;
+    net.L = c.nlayers;
+    const float* const p = c.params;
+    long off = 0;
+    for (int l = 0; l <= c.nlayers; ++l) net.dims[l] = c.dims[l];
+    for (int l = 0; l < c.nlayers; ++l) {
+        const int flags = c.flags ? c.flags[l] : 0;
+        if (flags < 0 || flags > 3 || flags == 2) return false;      // a scale only follows a normalisation
+        net.ln[l] = flags & 1;
+        net.offW[l] = off; net.W[l] = p ? p + off : nullptr; off += (long)c.dims[l] * c.dims[l + 1];
+        net.g[l] = nullptr; net.offg[l] = -1;
+        if (flags & 2) { net.offg[l] = off; net.g[l] = p ? p + off : nullptr; off += c.dims[l + 1]; net.scaled = true; }
+        net.offb[l] = off; net.b[l] = p ? p + off : nullptr; off += c.dims[l + 1];
+    }
+    net.offout = off; net.wout = p ? p + off : nullptr; off += c.dims[c.nlayers];
+    net.nparams = off;
+    return true;
+}
+// grid of a grid-stride kernel of 256-thread blocks over n elements; the next n floats of a workspace
+inline int blocks_for(long n) { long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
+inline float* carve(float*& p, long n) { float* r = p; p += n; return r; }
+
+// ssn_critic.hip: plain layers, any slope (the layer-by-layer MFMA GEMM chain)
+size_t critic_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p);
+hipError_t critic_forward(const CriticSpec& c, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st);
+// (inputs_ready: ws already starts with the input block of [xa; xb] -- critic_loss_grad on the same rows leaves it there)
+hipError_t critic_forward2(const CriticSpec& c, const float* xa, const float* ca, int na, const float* xb, const float* cb, int nb,
+                           float* out, float* ws, hipStream_t st, bool inputs_ready);
+// (eps != nullptr: xp is not an input -- it is formed here into xp_out, together with the three input blocks, in one launch)
+hipError_t critic_loss_grad(const CriticSpec& c, const float* xg, const float* cg, const float* xd, const float* cd, const float* xp,
+                            const float* cp, int ng, int nd, int np, float lmd, float* grads, float* stats, float* dvals, float* ws,
+                            hipStream_t st, const float* eps, float* xp_out);
+hipError_t critic_input_grad(const CriticSpec& c, const float* x, const float* cond, int batch, float scale, float* gx, float* stats,
+                             float* ws, hipStream_t st);
+// ssn_critic_ln.hip: the general form (layer normalisation, scales, smooth nonlinearities)
 size_t critic_norm_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p);
-// (norm[l]: bit 0 layer normalisation, bit 1 learnable scale after it; act: 0 rectify, 1 leaky_rectify, 2 very_leaky_rectify,
-// 3 linear, 4 tanh, 5 sigmoid, 6 softplus, 7 elu)
-long critic_act_num_params(const int* dims, const int* flags, int nlayers);
-hipError_t critic_norm_forward(const float* params, const int* dims, const int* norm, int nlayers, const float* x,
-                               const float* cond, int batch, int hide, float* out, float* ws, bool bf16, hipStream_t st, int act = 0);
-hipError_t critic_norm_input_grad(const float* params, const int* dims, const int* norm, int nlayers, const float* x,
-                                  const float* cond, int batch, int hide, float scale, float* gx, float* stats, float* ws,
-                                  bool bf16, hipStream_t st, int act = 0);
-hipError_t critic_norm_loss_grad(const float* params, const int* dims, const int* norm, int nlayers, const float* xg,
-                                 const float* cg, const float* xd, const float* cd, const float* xp, const float* cp, int ng,
-                                 int nd, int np, float lmd, int hide, float* grads, float* stats, float* dvals, float* ws,
-                                 bool bf16, hipStream_t st, int act = 0);
+hipError_t critic_norm_forward(const CriticSpec& c, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st);
+hipError_t critic_norm_input_grad(const CriticSpec& c, const float* x, const float* cond, int batch, float scale, float* gx,
+                                  float* stats, float* ws, hipStream_t st);
+hipError_t critic_norm_loss_grad(const CriticSpec& c, const float* xg, const float* cg, const float* xd, const float* cd,
+                                 const float* xp, const float* cp, int ng, int nd, int np, float lmd, float* grads, float* stats,
+                                 float* dvals, float* ws, hipStream_t st);
 
 // ssn_critic_rows.hip: wide plain critics (hidden widths multiples of 32 up to 512), the row-local part of an update in one launch
 struct RowsPackSeg { const float* src; unsigned short* dst; int nin, nout, NT, KS, kind; long start; };
@@ -250,21 +296,19 @@ struct RowsArgs {
 };
 bool critic_rows_supported(const int* dims, int nlayers);
 size_t critic_rows_workspace_floats(const int* dims, int nlayers, int batch_p);
-hipError_t critic_rows_pack(const float* params, const int* dims, int L, float* ws_pack, RowsArgs& ra, float* zero, long nzero, hipStream_t st);
+// (fills the weight and bias pointers of ra as well)
+hipError_t critic_rows_pack(const CriticLayout& net, float* ws_pack, RowsArgs& ra, float* zero, long nzero, hipStream_t st);
 hipError_t critic_rows_launch(const RowsArgs& ra, hipStream_t st);
 
-// ssn_critic_fused.hip: critics whose layer widths are all <= 128 (3 launches per update; fp32 arithmetic)
+// ssn_critic_fused.hip: critics whose layer widths are all <= 128 (3 launches per update; fp32 arithmetic), rectify, flags 0 / 1
 bool critic_fused_supported(const int* dims, int nlayers);
 size_t critic_fused_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p);
-hipError_t critic_fused_forward(const float* params, const int* dims, const int* norm, int nlayers, const float* x,
-                                const float* cond, int batch, int hide, float* out, float* ws, hipStream_t st);
-hipError_t critic_fused_input_grad(const float* params, const int* dims, const int* norm, int nlayers, const float* x,
-                                   const float* cond, int batch, int hide, float scale, float* gx, float* stats, float* ws,
-                                   hipStream_t st);
-hipError_t critic_fused_loss_grad(const float* params, const int* dims, const int* norm, int nlayers, const float* xg,
-                                  const float* cg, const float* xd, const float* cd, const float* xp, const float* cp, int ng,
-                                  int nd, int np, float lmd, int hide, float* grads, float* stats, float* dvals, float* ws,
-                                  hipStream_t st);
+hipError_t critic_fused_forward(const CriticSpec& c, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st);
+hipError_t critic_fused_input_grad(const CriticSpec& c, const float* x, const float* cond, int batch, float scale, float* gx,
+                                   float* stats, float* ws, hipStream_t st);
+hipError_t critic_fused_loss_grad(const CriticSpec& c, const float* xg, const float* cg, const float* xd, const float* cd,
+                                  const float* xp, const float* cp, int ng, int nd, int np, float lmd, float* grads, float* stats,
+                                  float* dvals, float* ws, hipStream_t st);
 
 // ssn_ff.hip
 struct FFArgs {

@@ -86,3 +86,64 @@ def test_product_package_never_imports_oracle():
                 text = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r'^\s*(from|import)\s+oracle', text, flags=re.M), f
                 assert 'liboracle' not in text and '_ref/' not in text, f
+
+
+# ---- the critic's description: parameter counts and refusals are host arithmetic, decided before any HIP call ------------------
+def _ints(v):
+    import ctypes
+    return (ctypes.c_int * max(len(v), 1))(*v)
+
+
+_COUNT_CASES = [          # (dims n_0 .. n_L, flags per hidden layer)
+    ([11], []),
+    ([7], []),
+    ([11, 32], [0]),
+    ([11, 32], [1]),
+    ([11, 33], [3]),
+    ([11, 128, 64, 5], [0, 0, 0]),
+    ([11, 128, 64, 5], [0, 1, 3]),
+    ([8, 40, 40, 40], [3, 3, 3]),
+    ([11, 16, 24, 32, 40, 48, 56, 64, 72], [0] * 8),
+    ([11, 16, 24, 32, 40, 48, 56, 64, 72], [0, 1, 3, 0, 1, 3, 0, 1]),
+]
+
+
+@pytest.mark.parametrize('dims, flags', _COUNT_CASES)
+def test_critic_num_params_is_the_closed_form(dims, flags):
+    import ctypes
+    from tc_gan_amd.clib import libssnode
+    L = len(flags)
+    want = sum(dims[l] * dims[l + 1] + dims[l + 1] * (1 + (flags[l] >> 1)) for l in range(L)) + dims[L]
+    d, f = _ints(dims), _ints(flags)
+    assert libssnode.ssn_critic_num_params_act(ctypes.addressof(d), ctypes.addressof(f), L) == want
+    if not any(flags):
+        assert libssnode.ssn_critic_num_params(d, L) == want
+        assert libssnode.ssn_critic_num_params_act(ctypes.addressof(d), None, L) == want
+
+
+@pytest.mark.parametrize('dims, flags', [([11, 32, 32], [0, 2]), ([11, 32, 32], [4, 0]), ([11] + [16] * 9, [0] * 9)])
+def test_critic_num_params_refuses_what_no_critic_has(dims, flags):
+    import ctypes
+    from tc_gan_amd.clib import libssnode
+    d, f = _ints(dims), _ints(flags)
+    assert libssnode.ssn_critic_num_params_act(ctypes.addressof(d), ctypes.addressof(f), len(flags)) == -1
+
+
+def test_critic_passes_refuse_a_bad_description_before_touching_the_device():
+    """A slope outside [0, 1] or NaN, a scaled layer given to the _norm family and an unknown activation code are refused from
+    the description alone (null data pointers, no GPU needed): SSN_ERR_BASE + hipErrorInvalidValue and a message."""
+    import ctypes
+    from tc_gan_amd import clib
+    lib = clib.libssnode
+    invalid = clib.SSN_ERR_BASE + 1                  # hipErrorInvalidValue
+    dims, flags = _ints([11, 32, 32]), _ints([0, 3])
+    pf, batch = ctypes.addressof(flags), 4
+    calls = [
+        lambda: lib.ssn_critic_forward_leaky(None, dims, 2, None, None, batch, 0, 2.0, None, None, 1, None),
+        lambda: lib.ssn_critic_forward_leaky(None, dims, 2, None, None, batch, 0, float('nan'), None, None, 1, None),
+        lambda: lib.ssn_critic_forward_norm(None, dims, flags, 2, None, None, batch, 0, None, None, 1, None),
+        lambda: lib.ssn_critic_forward_act(None, ctypes.addressof(dims), pf, 2, 8, None, None, batch, 0, None, None, 1, None),
+    ]
+    for call in calls:
+        assert call() == invalid
+        assert clib.last_error()
