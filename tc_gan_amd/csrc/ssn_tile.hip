@@ -36,16 +36,6 @@
 #ifndef SSN_TILE_MIXED
 #define SSN_TILE_MIXED 1
 #endif
-// diagnostic switches for the step loop of the fp32 NB = 1 kernels (A/B builds; 1 = product setting):
-// SSN_TILE_LOOP: the loop rotated by half a step so that one test of the verdict word ends it; the flag slots are rotating
-//                LDS addresses and the state buffer a toggled offset (no step % 3, no frozen / code / nsteps bookkeeping)
-// SSN_TILE_EXEC: no exec-mask regions around the state store, the flag stores and the flag clear
-#ifndef SSN_TILE_LOOP
-#define SSN_TILE_LOOP 1
-#endif
-#ifndef SSN_TILE_EXEC
-#define SSN_TILE_EXEC 1
-#endif
 
 namespace ssn {
 
@@ -70,16 +60,21 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     // ---- prologue: my RA x C tile of W -> registers (and LDS for the last RL rows) -----------------
     constexpr bool SPLIT = RL > 0 || PK;        // SplitTile: packed row pairs in VGPRs (+ RL rows in LDS)
     T w[!SPLIT ? RA : 1][!SPLIT ? C : 1];       // plain all-register shape
-    // the FMA block of the solver (SplitTile::matvec's MODE): SSN_TILE_FMA bit 0 asks for the one-statement form in the light
-    // wave of the mixed kernel (all rows packed, none in LDS), bit 2 in the waves with LDS-resident rows
-    constexpr int FMA_MODE = (SSN_TILE_FMA & 2) | ((SSN_TILE_FMA >> ((PK && RL == 0) ? 0 : 2)) & 1);
-    SplitTile<T, RA, C, RL> sw;
+    // OPAIR: the waves of the fp32 NB = 1 split kernels at C = 25 whose tile is two packed row pairs, an odd row and two
+    // LDS-resident rows.  They have one form: the odd row in column pairs inside the one-statement FMA block, and a
+    // transpose-reduce of their 7 rows that forms no zero row 7.
+    constexpr bool OPAIR = SSN_PK_ASM && sizeof(T) == 4 && NB == 1 && !PK && RA == 7 && RL == 2 && C % 4 == 1;
+    // the FMA block of the solver (SplitTile::matvec's MODE): the first product of every chain is a multiply, and the light
+    // wave of the mixed kernel (all rows packed, none in LDS) runs the one-statement form as well
+    constexpr int FMA_MODE = 2 | ((OPAIR || (PK && RL == 0)) ? 1 : 0);
+    SplitTile<T, RA, C, RL, OPAIR> sw;
     if constexpr (SPLIT) sw.template load<false>(a.W + (size_t)b * M * M, M, rowbase, colbase, wlds, threadIdx.x);
     else tile_load<T, RA, C, false>(a.W + (size_t)b * M * M, M, rowbase, colbase, w);
-    // fp32, NB = 1: the step loop below without the NB-generic bookkeeping (LOOP1) and without exec-mask regions (FLAT)
+    // fp32, NB = 1: the step loop below without the NB-generic bookkeeping (FAST1: rotated by half a step so that one test of
+    // the verdict word ends it, rotating flag addresses, a toggled buffer offset) and without exec-mask regions around the
+    // state store, the flag stores and the flag clear (FLAT)
     constexpr bool FAST1 = NB == 1 && sizeof(T) == 4 && !SSN_ABLATE;
-    constexpr bool LOOP1 = FAST1 && SSN_TILE_LOOP;
-    constexpr bool FLAT = FAST1 && SSN_TILE_EXEC && CP > C;      // (C = 4 has no pad float to absorb a dummy store)
+    constexpr bool FLAT = FAST1 && CP > C;      // (C = 4 has no pad float to absorb a dummy store)
     // the row this lane finishes each step (a = cg), its LDS slot, input and state
     const int myrow = rowbase + cg;
     const bool fin = (cg < RA) && (myrow < M);
@@ -119,7 +114,7 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     // slot (i+1)%3 is cleared for iteration i+1.  The FMAs of the extra iteration are discarded.
     int cur = 0;
     int step = 0;
-    if constexpr (LOOP1 || FLAT) {
+    if constexpr (FAST1) {
         using LdsI = __attribute__((address_space(3))) int*;
         using LdsS = __attribute__((address_space(3))) short*;
         using LdsV = const __attribute__((address_space(3))) void*;
@@ -152,7 +147,7 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
         // reduce, Euler update and stop tests of one step: the new state goes to the OTHER buffer, the tests to the flag
         // word at byte address fcur, and the word at fnext is cleared for the next step
         auto update = [&](T (&acc)[1][8], unsigned boff, unsigned fcur, unsigned fnext) {
-            const T u = reduce_rows_to_lane<RA>(acc[0], cg);
+            const T u = reduce_rows_to_lane<RA, T, OPAIR>(acc[0], cg);
             const T r1 = rc[0] + (-rc[0] + io_eval(u + ex[0], a.io)) * eps;
             const bool moving = abs_t(r1 - rc[0]) >= a.st.atol;
             const bool beyond = a.st.check_hard && r1 >= a.st.hard_stop;
@@ -183,43 +178,25 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
         };
         auto stops = [](int fu) { return !(fu & 0xffff) || (fu >> 16); };
         int stopword = 1;
-        if constexpr (LOOP1) {
-            // The loop rotated by half a step: [update of step k, barrier, flag word of step k, FMA block of step k + 1,
-            // verdict], so that ONE test at the bottom ends it -- on the verdict of the step just taken or at max_iter,
-            // where the FMA block of a step that is never taken is discarded just as after a stop.  The flag slots are
-            // three byte addresses that rotate and the state buffer is an offset that toggles: no step % 3, no multiply.
-            if (a.st.max_iter > 0) {
-                unsigned fcur = fbase, fnext = fbase + 4, fafter = fbase + 8, boff = 0;
-                T acc[1][8];
-                partial_sums(boff, acc);
-                do {
-                    update(acc, boff, fcur, fnext);
-                    __syncthreads();
-                    ++step;
-                    boff ^= BUF;                                   // 0 <-> BUF
-                    const int fl = *(LdsI)(size_t)fcur;
-                    const unsigned t = fcur; fcur = fnext; fnext = fafter; fafter = t;
-                    partial_sums(boff, acc);
-                    stopword = verdict(fl, acc);
-                } while (!stops(stopword) && step < a.st.max_iter);
-                cur = boff != 0;
-            }
-        } else {
-            for (; step < a.st.max_iter; ++step) {
-                const unsigned fprev = fbase + 4 * ((step + 2) % 3), fcur = fbase + 4 * (step % 3), fnext = fbase + 4 * ((step + 1) % 3);
-                int fl = 1;
-                if (step > 0) fl = *(LdsI)(size_t)fprev;
-                T acc[1][8];
-                partial_sums(cur * BUF, acc);
-                if (step > 0) {
-                    stopword = verdict(fl, acc);
-                    if (stops(stopword)) break;
-                }
-                update(acc, cur * BUF, fcur, fnext);
+        // The loop rotated by half a step: [update of step k, barrier, flag word of step k, FMA block of step k + 1,
+        // verdict], so that ONE test at the bottom ends it -- on the verdict of the step just taken or at max_iter,
+        // where the FMA block of a step that is never taken is discarded just as after a stop.  The flag slots are
+        // three byte addresses that rotate and the state buffer is an offset that toggles: no step % 3, no multiply.
+        if (a.st.max_iter > 0) {
+            unsigned fcur = fbase, fnext = fbase + 4, fafter = fbase + 8, boff = 0;
+            T acc[1][8];
+            partial_sums(boff, acc);
+            do {
+                update(acc, boff, fcur, fnext);
                 __syncthreads();
-                cur ^= 1;
-            }
-            if (step == a.st.max_iter && step > 0) stopword = flags[(step + 2) % 3][0];      // the last step's own verdict
+                ++step;
+                boff ^= BUF;                                   // 0 <-> BUF
+                const int fl = *(LdsI)(size_t)fcur;
+                const unsigned t = fcur; fcur = fnext; fnext = fafter; fafter = t;
+                partial_sums(boff, acc);
+                stopword = verdict(fl, acc);
+            } while (!stops(stopword) && step < a.st.max_iter);
+            cur = boff != 0;
         }
         // code and step count once, from the word that ended the loop
         if (stops(stopword)) { code[0] = (stopword & 0xffff) ? 2 : 0; nsteps[0] = step; }
@@ -313,7 +290,7 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     // NB == 1: nothing runs after the stop, so the buffer that was read in the last update still holds x_{k-1}
     if constexpr (NB == 1) { if (step > 0 && fin) rp[0] = rbuf[cur ^ 1][0][myslot]; }
     // verdict of the last executed iteration (no extra step was taken, so no roll-back)
-    if (!(SSN_ABLATE & 4) && !(LOOP1 || FLAT) && step == a.st.max_iter && step > 0) {
+    if (!(SSN_ABLATE & 4) && !FAST1 && step == a.st.max_iter && step > 0) {
 #pragma unroll
         for (int s = 0; s < NB; ++s) {
             if (!frozen[s]) {

@@ -20,12 +20,6 @@
 #ifndef SSN_REDUCE4
 #define SSN_REDUCE4 1            // diagnostic: 0 = 8-row transpose-reduce also for tiles of <= 4 rows
 #endif
-// diagnostic switch, fp32 solver only (bit mask; the generator kernels always run SplitTile::matvec<NB, 0>):
-// 1 = light wave of the mixed kernel: the packed FMAs of a quad of columns as ONE asm statement, 2 = the first column as a
-// multiply (no accumulator zeroed first), 4 = the one-statement form also in the waves with LDS-resident rows
-#ifndef SSN_TILE_FMA
-#define SSN_TILE_FMA 3
-#endif
 
 namespace ssn {
 
@@ -95,24 +89,43 @@ __device__ __forceinline__ T reduce8_to_lane(const T (&acc)[8], int cg) {
 // fp32: the first exchange without selects.  Bit 2 of the lane index (= bit 2 of cg) is a DPP bank boundary, so the
 // two halves are formed by two v_add_f32_dpp, the second one writing only the lanes that keep rows 4..7
 // (bank_mask 0xa = lanes 4-7 and 12-15 of every row of 16): 8 instructions instead of 12 for this stage.
+// ROW7 = false: the tile has 7 rows and acc[7] is not read.  Lanes 4-7 then keep, in n4[3], the sum of their own and
+// their mirror lane's partial sums of row 3 where row 7 would stand.  The second exchange sends it from lanes 4, 5 to
+// lanes 6, 7, which add it to their own as n2[1], and the third leaves lane 6 with n2[0] (row 6, from both) and lane 7
+// with n2[1]: lane cg = 7 of every row group is the only lane whose result has that value in it, and with 7 rows per
+// row group it finishes no row (fin = cg < RA).  Lanes 0-6 hold the same bits as with a zero row.
 #ifndef SSN_REDUCE_PLAIN
-template <>
-__device__ __forceinline__ float reduce8_to_lane<float>(const float (&acc)[8], int cg) {
+template <bool ROW7>
+__device__ __forceinline__ float reduce8_f32(const float (&acc)[8], int cg) {
     const bool bB = cg & 2, bC = cg & 1;
     float n4[4], n2[2];
     // A DPP read of a VGPR needs two wait states after the VALU write of that VGPR and the hardware does not
     // interlock; the compiler inserts them for its own DPP instructions but cannot see into inline asm.  One s_nop
     // that "redefines" all eight inputs puts every producing FMA in front of it, and with it two wait states in front
     // of every DPP read below.
-    float a0 = acc[0], a1 = acc[1], a2 = acc[2], a3 = acc[3], a4 = acc[4], a5 = acc[5], a6 = acc[6], a7 = acc[7];
-    asm volatile("s_nop 1" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7));
-    const float lo[4] = {a0, a1, a2, a3}, hi[4] = {a4, a5, a6, a7};
+    if constexpr (ROW7) {
+        float a0 = acc[0], a1 = acc[1], a2 = acc[2], a3 = acc[3], a4 = acc[4], a5 = acc[5], a6 = acc[6], a7 = acc[7];
+        asm volatile("s_nop 1" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7));
+        const float lo[4] = {a0, a1, a2, a3}, hi[4] = {a4, a5, a6, a7};
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float r;
-        asm("v_add_f32_dpp %0, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(r) : "v"(lo[k]));
-        asm("v_add_f32_dpp %0, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xa" : "+v"(r) : "v"(hi[k]));
-        n4[k] = r;
+        for (int k = 0; k < 4; ++k) {
+            float r;
+            asm("v_add_f32_dpp %0, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(r) : "v"(lo[k]));
+            asm("v_add_f32_dpp %0, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xa" : "+v"(r) : "v"(hi[k]));
+            n4[k] = r;
+        }
+    } else {
+        // The whole exchange as one statement: its inputs put every producing FMA in front of it, the s_nop gives the DPP
+        // reads their two wait states, and the masked adds follow the full ones without the wait state the compiler would
+        // put between two statements (they read rows 4-6, written long before, and only write n4).
+#define SSN_DPP_FULL(r, a) "v_add_f32_dpp %[" r "], %[" a "], %[" a "] row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
+#define SSN_DPP_HIGH(r, a) "v_add_f32_dpp %[" r "], %[" a "], %[" a "] row_half_mirror row_mask:0xf bank_mask:0xa\n"
+        asm("s_nop 1\n" SSN_DPP_FULL("r0", "a0") SSN_DPP_FULL("r1", "a1") SSN_DPP_FULL("r2", "a2") SSN_DPP_FULL("r3", "a3")
+            SSN_DPP_HIGH("r0", "a4") SSN_DPP_HIGH("r1", "a5") SSN_DPP_HIGH("r2", "a6")
+            : [r0] "=&v"(n4[0]), [r1] "=&v"(n4[1]), [r2] "=&v"(n4[2]), [r3] "=&v"(n4[3])
+            : [a0] "v"(acc[0]), [a1] "v"(acc[1]), [a2] "v"(acc[2]), [a3] "v"(acc[3]), [a4] "v"(acc[4]), [a5] "v"(acc[5]), [a6] "v"(acc[6]));
+#undef SSN_DPP_FULL
+#undef SSN_DPP_HIGH
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -124,12 +137,18 @@ __device__ __forceinline__ float reduce8_to_lane<float>(const float (&acc)[8], i
     const float send = bC ? n2[0] : n2[1];
     return keep + dpp_get_f<0xB1>(send);                // quad_perm:[1,0,3,2]: lane i <-> i^1
 }
+template <>
+__device__ __forceinline__ float reduce8_to_lane<float>(const float (&acc)[8], int cg) { return reduce8_f32<true>(acc, cg); }
 #endif
 
 // Tiles of at most 4 rows (acc[4..7] == 0): the first exchange only has to fold the two halves of the lane group
 // together -- four DPP adds, no second masked add, no zero inputs to materialise; lanes 0-3 end with rows 0-3.
-template <int ROWS, typename T>
+// TRIM (fp32 tiles of 7 rows): no zero row 7 is formed and folded in; lane cg = 7 ends with a value nobody may use.
+template <int ROWS, typename T, bool TRIM = false>
 __device__ __forceinline__ T reduce_rows_to_lane(const T (&acc)[8], int cg) {
+#ifndef SSN_REDUCE_PLAIN
+    if constexpr (TRIM && ROWS == 7 && sizeof(T) == 4) return reduce8_f32<false>(acc, cg);
+#endif
     if constexpr (ROWS > 4 || sizeof(T) != 4 || !SSN_REDUCE4) {
         return reduce8_to_lane(acc, cg);
     } else {
@@ -259,13 +278,18 @@ template <int RA, int C, int RL> struct TileSplit {
 // FMA block keeps the pipe full even while the other waves of the SIMD sit at the barrier.
 // At RA = 7, RL = 2: rows (0,1), (2,3) packed, row 4 plain, LDS rows (5,6) packed -> 4 instead of 7
 // instructions per column.  (fp64 has no packed form; the same code compiles to scalar v_fma_f64.)
-template <typename T, int RA, int C, int RL> struct SplitTile {
+// OP (fp32 solver, C = 4k + 1): the odd row is held as PAIRS of columns, (o[c], o[c+1]) for even c, which is how the
+// 16-byte read leaves r: one plain v_pk_fma_f32 per two columns into a two-float accumulator (even columns in one half,
+// odd columns in the other), column C - 1 with one FMA into the low half, the row's partial sum = low + high.
+template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
     using S = TileSplit<RA, C, RL>;
     static constexpr int RR = S::RR, NP = RR / 2, ODD = RR % 2;
+    static_assert(!OP || (sizeof(T) == 4 && ODD && NP == 2 && C % 4 == 1 && C >= 5), "odd row in column pairs: 5 register rows, whole quads + one column");
     using V2 = T __attribute__((ext_vector_type(2)));
     using V4 = T __attribute__((ext_vector_type(4)));
     V2 p[NP > 0 ? NP : 1][C];      // p[k][c] = (W[row 2k][c], W[row 2k+1][c])
-    T o[ODD ? C : 1];              // last register row when RR is odd
+    T o[ODD && !OP ? C : 1];       // last register row when RR is odd (OP: its last column only)
+    V2 oc[OP ? C / 2 : 1];         // OP: oc[j] = (W[odd row][2j], W[odd row][2j+1])
 
     template <bool TRANSPOSED>
     __device__ __forceinline__ void load(const T* A, int M, int rowbase, int colbase, T* wl, int tid) {
@@ -322,8 +346,18 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
             fetch_row(rowbase + r, t);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                if (ODD && r == RR - 1) o[c] = t[c];
-                else if (r & 1) p[r / 2][c].y = t[c];
+                if constexpr (OP) {
+                    if (r == RR - 1) {
+                        if (c == C - 1) o[0] = t[c];
+                        else if (c & 1) oc[c / 2].y = t[c];
+                        else oc[c / 2].x = t[c];
+                        continue;
+                    }
+                } else if (ODD && r == RR - 1) {
+                    o[c] = t[c];
+                    continue;
+                }
+                if (r & 1) p[r / 2][c].y = t[c];
                 else p[r / 2][c].x = t[c];
             }
         }
@@ -337,6 +371,8 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
     // have the LDS reads between them.  MUL: column 0 is a multiply (the accumulators are outputs only).
     // TIE: `tie` rides along as an in-out operand that no instruction touches.  It is the accumulator of the LDS-resident
     // rows, whose FMAs wait for their W units and therefore have to stay BEHIND the block that covers that wait.
+    // ODDP (whole quads only): the odd row's two column pairs of the quad join the statement as a third chain, plain
+    // v_pk_fma_f32 on the pairs (r0, r1) and (r2, r3); no two consecutive instructions share an accumulator.
 #define SSN_PK_LO(a, w, r) "v_pk_fma_f32 %[" a "], %[" w "], %[" r "], %[" a "] op_sel_hi:[1,0,1]\n"
 #define SSN_PK_HI(a, w, r) "v_pk_fma_f32 %[" a "], %[" w "], %[" r "], %[" a "] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n"
 #define SSN_PK_MUL(a, w, r) "v_pk_mul_f32 %[" a "], %[" w "], %[" r "] op_sel_hi:[1,0]\n"
@@ -345,6 +381,11 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
 #define SSN_PK_COL1 SSN_PK_HI("a0", "u1", "rl") SSN_PK_HI("a1", "v1", "rl")
 #define SSN_PK_COL2 SSN_PK_LO("a0", "u2", "rh") SSN_PK_LO("a1", "v2", "rh")
 #define SSN_PK_COL3 SSN_PK_HI("a0", "u3", "rh") SSN_PK_HI("a1", "v3", "rh")
+#define SSN_PK_ODD01 "v_pk_fma_f32 %[ao], %[o0], %[rl], %[ao]\n"
+#define SSN_PK_ODD01M "v_pk_mul_f32 %[ao], %[o0], %[rl]\n"
+#define SSN_PK_ODD23 "v_pk_fma_f32 %[ao], %[o1], %[rh], %[ao]\n"
+#define SSN_PK_QUAD_ODD SSN_PK_COL0 SSN_PK_ODD01 SSN_PK_COL1 SSN_PK_COL2 SSN_PK_ODD23 SSN_PK_COL3
+#define SSN_PK_QUAD_ODDM SSN_PK_COL0M SSN_PK_ODD01M SSN_PK_COL1 SSN_PK_COL2 SSN_PK_ODD23 SSN_PK_COL3
 #define SSN_PK_IN [rl] "v"(rlo), [rh] "v"(rhi), [u0] "v"(w0[0]), [u1] "v"(w0[NC > 1 ? 1 : 0]), [u2] "v"(w0[NC > 2 ? 2 : 0]), \
                   [u3] "v"(w0[NC > 3 ? 3 : 0]), [v0] "v"(w1[0]), [v1] "v"(w1[NC > 1 ? 1 : 0]), [v2] "v"(w1[NC > 2 ? 2 : 0]), \
                   [v3] "v"(w1[NC > 3 ? 3 : 0])
@@ -353,10 +394,20 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
         if constexpr (TIE) asm(text : [a0] how(a0), [a1] how(a1), [t] "+v"(tie) : SSN_PK_IN);       \
         else asm(text : [a0] how(a0), [a1] how(a1) : SSN_PK_IN);                                    \
     } while (0)
-    template <int NC, bool MUL, bool TIE>
-    static __device__ __forceinline__ void pk_block(V2& a0, V2& a1, V2& tie, const V2* w0, const V2* w1, const V2& rlo, const V2& rhi) {
+#define SSN_PK_STMT_ODD(text, how)                                                                                  \
+    do {                                                                                                            \
+        if constexpr (TIE) asm(text : [a0] how(a0), [a1] how(a1), [ao] how(ao), [t] "+v"(tie) : SSN_PK_IN, [o0] "v"(wo[0]), [o1] "v"(wo[1])); \
+        else asm(text : [a0] how(a0), [a1] how(a1), [ao] how(ao) : SSN_PK_IN, [o0] "v"(wo[0]), [o1] "v"(wo[1]));    \
+    } while (0)
+    template <int NC, bool MUL, bool TIE, bool ODDP = false>
+    static __device__ __forceinline__ void pk_block(V2& a0, V2& a1, V2& ao, V2& tie, const V2* w0, const V2* w1, const V2* wo,
+                                                    const V2& rlo, const V2& rhi) {
         static_assert(NC >= 1 && NC <= 4, "columns of one 16-byte read");
-        if constexpr (MUL) {
+        static_assert(!ODDP || NC == 4, "the odd row joins whole quads only");
+        if constexpr (ODDP) {
+            if constexpr (MUL) SSN_PK_STMT_ODD(SSN_PK_QUAD_ODDM, "=&v");
+            else SSN_PK_STMT_ODD(SSN_PK_QUAD_ODD, "+v");
+        } else if constexpr (MUL) {
             if constexpr (NC == 1) SSN_PK_STMT(SSN_PK_COL0M, "=&v");
             else if constexpr (NC == 2) SSN_PK_STMT(SSN_PK_COL0M SSN_PK_COL1, "=&v");
             else if constexpr (NC == 3) SSN_PK_STMT(SSN_PK_COL0M SSN_PK_COL1 SSN_PK_COL2, "=&v");
@@ -368,6 +419,20 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
             else SSN_PK_STMT(SSN_PK_COL0 SSN_PK_COL1 SSN_PK_COL2 SSN_PK_COL3, "+v");
         }
     }
+    // The four packed FMAs of the two LDS-resident rows for one whole quad of columns, as one statement behind pk_block:
+    // with the odd row inside the block the compiler has no instruction of its own left to put between them.
+    // (x, y): the quad's two 16-byte W units = (row 5, row 6) of columns 0, 1 and of columns 2, 3.
+    template <bool MUL>
+    static __device__ __forceinline__ void lds_block(V2& al, const V4& x, const V4& y, const V2& rlo, const V2& rhi) {
+        const V2 u0 = {x.x, x.y}, u1 = {x.z, x.w}, u2 = {y.x, y.y}, u3 = {y.z, y.w};
+        if constexpr (MUL)
+            asm(SSN_PK_MUL("a0", "u0", "rl") SSN_PK_HI("a0", "u1", "rl") SSN_PK_LO("a0", "u2", "rh") SSN_PK_HI("a0", "u3", "rh")
+                : [a0] "=&v"(al) : [rl] "v"(rlo), [rh] "v"(rhi), [u0] "v"(u0), [u1] "v"(u1), [u2] "v"(u2), [u3] "v"(u3));
+        else
+            asm(SSN_PK_LO("a0", "u0", "rl") SSN_PK_HI("a0", "u1", "rl") SSN_PK_LO("a0", "u2", "rh") SSN_PK_HI("a0", "u3", "rh")
+                : [a0] "+v"(al) : [rl] "v"(rlo), [rh] "v"(rhi), [u0] "v"(u0), [u1] "v"(u1), [u2] "v"(u2), [u3] "v"(u3));
+    }
+#undef SSN_PK_STMT_ODD
 #undef SSN_PK_STMT
 #undef SSN_PK_IN
 
@@ -375,7 +440,8 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
     // Software pipeline per quad q of columns: issue the x reads of quad q+1 and the W units of quad q, run the
     // register FMAs of quad q (which cover the LDS latency), then the LDS-row FMAs.
     // MODE (fp32 with SSN_PK_ASM only; 0 = the generator kernels' block): bit 0 = pk_block for a tile with two register row
-    // pairs; bit 1 = the first product of every chain is a multiply, so no accumulator is zeroed first.  fma(w, r, +0) and
+    // pairs (a tile with OP always asks for it: its odd row and, in lds_block, its LDS-resident rows are part of that form);
+    // bit 1 = the first product of every chain is a multiply, so no accumulator is zeroed first.  fma(w, r, +0) and
     // w * r are the same bits unless the product is an exact zero of negative sign (+0 from the FMA, -0 from the
     // multiply); a chain can then end in -0 instead of +0 only if every one of its products is a zero, the
     // transpose-reduce adds it to the other partial sums (x + -0 = x, and -0 + +0 = +0), and a row whose partial sums are
@@ -388,6 +454,7 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
         constexpr bool F32ASM = sizeof(T) == 4 && SSN_PK_ASM;
         constexpr bool BLK = F32ASM && (MODE & 1) && NP == 2;
         constexpr bool MUL0 = F32ASM && (MODE & 2);
+        static_assert(!OP || BLK, "the odd row in column pairs lives in the one-statement block");
         // Stage boundaries are enforced with data dependencies (an empty asm that "redefines" the LDS
         // addresses and the accumulators): the reads of stage q+1 cannot be hoisted above it, the FMAs of
         // stage q cannot sink below it.  __builtin_amdgcn_sched_barrier alone is not enough -- instruction
@@ -398,14 +465,14 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
         using LdsT = const __attribute__((address_space(3))) T*;
         unsigned xa = (unsigned)(size_t)(LdsT)(xs + cg * CP);
         unsigned wa = (unsigned)(size_t)(LdsT)(wl + tid * 4);
-        V2 a2[NB][NP > 0 ? NP : 1], al2[NB];
+        V2 a2[NB][NP > 0 ? NP : 1], al2[NB], ao2[NB];     // ao2 (OP): odd row, even columns in .x, odd columns in .y
         T ao[NB], al1[NB];
         if constexpr (!MUL0) {
 #pragma unroll
             for (int s = 0; s < NB; ++s) {
 #pragma unroll
                 for (int k = 0; k < NP; ++k) a2[s][k] = (V2){(T)0, (T)0};
-                al2[s] = (V2){(T)0, (T)0};
+                al2[s] = ao2[s] = (V2){(T)0, (T)0};
                 ao[s] = al1[s] = (T)0;
             }
         }
@@ -457,18 +524,18 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
                     // (q is a constant once the loop is unrolled; the other branches fold away.  In the first quad
                     // under MUL0 the accumulator of the LDS-resident rows does not exist yet: no tie there.)
                     const int nc = C - 4 * q < 4 ? C - 4 * q : 4;
-                    const V2 *w0 = &p[0][4 * q], *w1 = &p[1][4 * q];
-                    V2 &x0 = a2[s][0], &x1 = a2[s][1], &t = al2[s];
+                    const V2 *w0 = &p[0][4 * q], *w1 = &p[1][4 * q], *wo = &oc[OP ? 2 * q : 0];
+                    V2 &x0 = a2[s][0], &x1 = a2[s][1], &xo = ao2[s], &t = al2[s];
                     if (MUL0 && q == 0) {
-                        if (nc == 1) pk_block<1, true, false>(x0, x1, t, w0, w1, rlo, rhi);
-                        else if (nc == 2) pk_block<2, true, false>(x0, x1, t, w0, w1, rlo, rhi);
-                        else if (nc == 3) pk_block<3, true, false>(x0, x1, t, w0, w1, rlo, rhi);
-                        else pk_block<4, true, false>(x0, x1, t, w0, w1, rlo, rhi);
+                        if (nc == 1) pk_block<1, true, false>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+                        else if (nc == 2) pk_block<2, true, false>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+                        else if (nc == 3) pk_block<3, true, false>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+                        else pk_block<4, true, false, OP>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
                     } else {
-                        if (nc == 1) pk_block<1, false, RL == 2>(x0, x1, t, w0, w1, rlo, rhi);
-                        else if (nc == 2) pk_block<2, false, RL == 2>(x0, x1, t, w0, w1, rlo, rhi);
-                        else if (nc == 3) pk_block<3, false, RL == 2>(x0, x1, t, w0, w1, rlo, rhi);
-                        else pk_block<4, false, RL == 2>(x0, x1, t, w0, w1, rlo, rhi);
+                        if (nc == 1) pk_block<1, false, RL == 2>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+                        else if (nc == 2) pk_block<2, false, RL == 2>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+                        else if (nc == 3) pk_block<3, false, RL == 2>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+                        else pk_block<4, false, RL == 2, OP>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
                     }
                 }
 #pragma unroll
@@ -479,13 +546,22 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
 #pragma unroll
                             for (int k = 0; k < NP; ++k) pk_bcast(a2[s][k], p[k][c], e, c == 0);
                         }
-                        if (ODD) ao[s] = (MUL0 && c == 0) ? o[c] * rr[e] : fma(o[c], rr[e], ao[s]);
+                        if constexpr (OP) {
+                            // column C - 1 into the low half, then the two halves: the row's partial sum
+                            if (c == C - 1) ao[s] = fma(o[0], rr[e], ao2[s].x) + ao2[s].y;
+                        } else if (ODD) ao[s] = (MUL0 && c == 0) ? o[c] * rr[e] : fma(o[c], rr[e], ao[s]);
+                    }
+                }
+                if constexpr (OP && RL == 2) {
+                    if (C - 4 * q >= 4) {
+                        if (MUL0 && q == 0) lds_block<true>(al2[s], wu[2 * q], wu[2 * q + 1], rlo, rhi);
+                        else lds_block<false>(al2[s], wu[2 * q], wu[2 * q + 1], rlo, rhi);
                     }
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int c = 4 * q + e;
-                    if (c < C) {
+                    if (c < C && !(OP && RL == 2 && C - 4 * q >= 4)) {
                         if constexpr (RL == 2) {
                             const int j = c * 2;
                             const V2 wp = {wu[j / 4][j % 4], wu[j / 4][j % 4 + 1]};
@@ -501,7 +577,8 @@ template <typename T, int RA, int C, int RL> struct SplitTile {
                 for (int s = 0; s < NB; ++s) {
 #pragma unroll
                     for (int k = 0; k < NP; ++k) asm volatile("" : "+v"(a2[s][k]));
-                    if (ODD) asm volatile("" : "+v"(ao[s]));
+                    if (OP) asm volatile("" : "+v"(ao2[s]));
+                    else if (ODD) asm volatile("" : "+v"(ao[s]));
                     if (RL == 2) asm volatile("" : "+v"(al2[s]));
                     if (RL == 1) asm volatile("" : "+v"(al1[s]));
                 }
