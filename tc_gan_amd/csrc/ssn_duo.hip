@@ -30,19 +30,21 @@
 
 namespace ssn {
 
+// Diagnostic build (SSN_DUO_STAMP): the kernel that ran last leaves, for every wave w = 4 draw + wave of workgroup 0, its
+// DuoStamp row in duo_stamps[8 w ..].  Segments -- forward (steps before the window): chain, early tile, barrier, rest of the
+// serial part, publication, barrier; solver: chain + early tile, verdict, barrier, serial part, barrier; adjoint sweep (steps
+// after the window): serial part, barrier, chain (+ early tile), barrier.
+using Stamp = DuoStamp<SSN_DUO_STAMP != 0>;
 #if SSN_DUO_STAMP
-__device__ unsigned long long duo_stamps[16];
-// SSN_DUO_STAMP=2 (forward only): workgroup 0, every wave w = 0 .. 7: [8 w + 0 .. 5] = chain, early tile, barrier, rest of the
-// serial part, publication, barrier (ticks summed over the steps before the window); [8 w + 6] = ticks from the first to the
-// last step; [8 w + 7] = steps
-__device__ unsigned long long duo_stamps_fine[64];
+__device__ unsigned long long duo_stamps[64];
+__device__ __forceinline__ unsigned long long* duo_stamp_row(int w) { return duo_stamps + 8 * w; }
+#else
+__device__ __forceinline__ unsigned long long* duo_stamp_row(int) { return nullptr; }
 #endif
-
-
 
 template <int MK, int WV, bool SAVE, bool FREE, bool HT>
 __device__ __forceinline__ void duo_forward_wave(const GenFwdArgs<float>& a, int rshift, int d, int b, int s0, bool valid,
-                                                 int lane, char* dlds, char* wlds, unsigned* wmax) {
+                                                 int lane, char* dlds, unsigned* wmax) {
     using S = Duo16<MK>;
     using WS = DuoWave<MK, WV>;
     constexpr int NT = WS::NT, NTF = WS::NTF, RT0 = WS::RT0;
@@ -55,23 +57,15 @@ __device__ __forceinline__ void duo_forward_wave(const GenFwdArgs<float>& a, int
     auto row_of = [&](int i) { return (HTW && i == NE - 1) ? row_tail : 16 * (RT0 + i / 2) + 4 * lg + 2 * hi + (i & 1); };
     const __amdgpu_buffer_rsrc_t rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W + (size_t)b * M * M), 0, M * M * 4, 0x00020000);
-    // ---- W: pass 1 = max |W| of the draw, pass 2 = the two fp16 parts of W 2^a
-    using Ops = DuoOperands<MK, WV, S::nl(SAVE)>;
-#if SSN_DUO_ONEPASS
+    // ---- W, read once: max |W| of the draw, then the two fp16 parts of W 2^a (every unit in registers: Duo16)
+    using Ops = DuoOperands<MK, WV, 0>;
     typename Ops::Raw raw;
     atomicMax(wmax, __builtin_bit_cast(unsigned, Ops::fetch(rsrc, M, li, lg, raw)));
-#else
-    atomicMax(wmax, __builtin_bit_cast(unsigned, Ops::max_abs(rsrc, M, li, lg)));
-#endif
     __syncthreads();                                                          // (A)
     const int wexp = duo_w_exp(*wmax);
     const float sa = duo_pow2(wexp), usc = duo_pow2(-wexp - rshift), rs = duo_pow2(rshift);
     Ops ops;
-#if SSN_DUO_ONEPASS
-    ops.split(raw, sa, wlds, lane);
-#else
-    ops.load(rsrc, M, li, lg, sa, wlds, lane);
-#endif
+    ops.split(raw, sa, nullptr, lane);
     // ---- the values this lane finishes: row tile RT0 + tf, rows 4 lg + 2 hi + e, stimulus s0 + st
     const IoSelect io(a.io);
     const int s = s0 + st;
@@ -92,9 +86,6 @@ __device__ __forceinline__ void duo_forward_wave(const GenFwdArgs<float>& a, int
         rs_traj = __builtin_amdgcn_make_buffer_rsrc(a.traj + (size_t)b * blk_elems, 0, (int)(blk_elems * 4), 0x00020000);
         rs_df = __builtin_amdgcn_make_buffer_rsrc(a.df + (size_t)b * blk_elems, 0, (int)(blk_elems * 4), 0x00020000);
         toff = live ? (int)(((size_t)s * T_ * M + 4 * lg + 2 * hi) * 4) : -1;
-#if SSN_DUO_STORE_LAYOUT
-        toff = live ? (int)((st * 16 + 4 * lg + 2 * hi) * 4) : -1;      // TIMING ONLY (wrong results): [T][row tile][stimulus][16 rows]
-#endif
     }
     const int toff_tail = (SAVE && live && row_tail < M) ? (int)(((size_t)s * T_ * M + row_tail) * 4) : -1;
     using LdsH8 = const __attribute__((address_space(3))) hv8*;
@@ -112,14 +103,10 @@ __device__ __forceinline__ void duo_forward_wave(const GenFwdArgs<float>& a, int
     const unsigned sync = bimg + (unsigned)S::SYNC;
     bool dead = false;
     mf4 acc[NT];
-    // lock-step form: the B operand of the k tile this wave publishes itself is read in front of the barrier (see own_kt)
-    constexpr bool PREB = !FREE && SSN_DUO_PREB && Ops::own_kt() >= 0;
-    hv8 bpre = hv8{};
     auto chain = [&](int it) {
         // free-running form: all four waves of the draw must have stored the state of step it - 1 (image it & 1)
         if (FREE && it > 0) duo_wait_ge(sync, S::WM * it, dead);
-        if constexpr (PREB && SSN_DUO_PREB == 2) ops.template chain<true, true, 1>(b_rd, acc, bpre);      // (its head ran in front of the barrier)
-        else ops.template chain<SSN_DUO_PREB != 0, PREB>(b_rd + (FREE ? (unsigned)((it & 1) * S::BB) : 0u), acc, bpre);
+        ops.chain(b_rd + (FREE ? (unsigned)((it & 1) * S::BB) : 0u), acc);
         if constexpr (WS::TAIL_SHARED) {
             *(LdsF4)(size_t)(xs + (unsigned)(WV * S::XS)) = acc[NT - 1];
             if (FREE) duo_signal_set(sync + 4u * (1 + WV), (unsigned)(it + 1), lane);
@@ -151,8 +138,8 @@ __device__ __forceinline__ void duo_forward_wave(const GenFwdArgs<float>& a, int
                     }
                 }
                 // lane s (hi = 0) finishes rows 0, 1, lane 8 + s rows 2, 3 (duo_join)
-                const float j0 = tf == T0 ? duo_join<true>(sm.x, sm.z, hi, sm.y, sm.w) : duo_join<false>(sm.x, sm.z, hi);
-                const float j1 = duo_join<false>(sm.y, sm.w, hi);
+                const float j0 = tf == T0 ? duo_join<true>(sm.x, sm.z, hi) : duo_join<false>(sm.x, sm.z, hi);
+                const float j1 = duo_join(sm.y, sm.w, hi);
                 if (is_tail) {
                     uu[NV - 1] = fmaf(duo_tail_take(j0, j1), usc, ex[NE - 1]);
                 } else {
@@ -162,12 +149,7 @@ __device__ __forceinline__ void duo_forward_wave(const GenFwdArgs<float>& a, int
             }
 #pragma unroll
             for (int jv = 0; jv < NV; ++jv) dfn[jv] = 0.f;
-            if (SSN_DUO_ABLATE & 1) {                    // (no nonlinearity: the rest of the serial part stays)
-#pragma unroll
-                for (int jv = 0; jv < NV; ++jv) ff[jv] = uu[jv];
-            } else {
-                duo_eval<SAVE, NV>(io, uu, ff, dfn);
-            }
+            duo_eval<SAVE, NV>(io, uu, ff, dfn);
             const float win2 = (it > a.skip) ? 1.f : 0.f;
 #pragma unroll
             for (int jv = 0; jv < NV; ++jv) {
@@ -185,19 +167,16 @@ __device__ __forceinline__ void duo_forward_wave(const GenFwdArgs<float>& a, int
 #pragma unroll
                 for (int tf = T0; tf < T1; ++tf) {
                     const int rt = RT0 + tf;
-#if SSN_DUO_STORE_LAYOUT
-                    const int off = (toff < 0 || 16 * rt + 4 * lg + 2 * hi >= M) ? -1 : toff + ((it * S::NRT + rt) * 8) * 64;
-#else
+                    // (a layout in which every wave stores 512 contiguous bytes ran at 5.19-5.20 against 5.24-5.46 ms: DESIGN 3.13c)
                     const int off = (toff < 0 || 16 * rt + 4 * lg + 2 * hi >= M) ? -1 : toff + (it * M + 16 * rt) * 4;
-#endif
                     const fv2 rv = {rc[2 * tf], rc[2 * tf + 1]}, dv = {dfn[2 * (tf - T0)], dfn[2 * (tf - T0) + 1]};
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(unsigned __attribute__((ext_vector_type(2))), rv), rs_traj, off, 0, SSN_DUO_STORE_AUX);
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(unsigned __attribute__((ext_vector_type(2))), dv), rs_df, off, 0, SSN_DUO_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(unsigned __attribute__((ext_vector_type(2))), rv), rs_traj, off, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(unsigned __attribute__((ext_vector_type(2))), dv), rs_df, off, 0, 0);
                 }
                 if constexpr (TAIL) {
                     const int off = toff_tail < 0 ? -1 : toff_tail + it * M * 4;
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, rc[NE - 1]), rs_traj, off, 0, SSN_DUO_STORE_AUX);
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dfn[NV - 1]), rs_df, off, 0, SSN_DUO_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, rc[NE - 1]), rs_traj, off, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dfn[NV - 1]), rs_df, off, 0, 0);
                 }
             }
         }
@@ -221,13 +200,9 @@ __device__ __forceinline__ void duo_forward_wave(const GenFwdArgs<float>& a, int
             *(LdsH)(size_t)(wr + 128u) = (unsigned short)m;
         }
         if (FREE) duo_signal_add(sync, lane);
-        if constexpr (PREB) {
-            bpre = Ops::read_b(b_rd, Ops::own_kt());
-            if constexpr (SSN_DUO_PREB == 2) ops.template chain<true, true, 0, 1>(b_rd, acc, bpre);      // head of the next step's chain
-        }
     };
     // row tiles finished behind the own chain: the last ones (never the first, which may wait for a neighbour's partial sum)
-    constexpr int EARLY = (FREE || !((SSN_DUO_EARLY_MASK >> WV) & 1)) ? 0 : (SSN_DUO_EARLY < NP - 1 ? SSN_DUO_EARLY : NP - 1);
+    constexpr int EARLY = FREE ? 0 : (S::EARLY < NP - 1 ? S::EARLY : NP - 1);
     constexpr std::integral_constant<int, 0> TB{};
     constexpr std::integral_constant<int, NP - EARLY> TM{};
     constexpr std::integral_constant<int, NP> TE{};
@@ -242,81 +217,30 @@ __device__ __forceinline__ void duo_forward_wave(const GenFwdArgs<float>& a, int
     constexpr std::integral_constant<bool, true> W1{};
     const int nskip = a.skip < T_ ? (a.skip > 0 ? a.skip : 0) : T_;
     __syncthreads();                                                          // (B)
-    if constexpr (PREB) {                                                      // (the initial image: zeros)
-        bpre = Ops::read_b(b_rd, Ops::own_kt());
-        if constexpr (SSN_DUO_PREB == 2) ops.template chain<true, true, 0, 1>(b_rd, acc, bpre);
-    }
     if constexpr (FREE) {
         // no workgroup barrier from here on: the four waves of a draw meet at their own counters, the two draws drift
         for (int it = 0; it < nskip; ++it) { chain(it); serial(W0, it); }
         for (int it = nskip; it < T_; ++it) { chain(it); serial(W1, it); }
     } else {
         if (d) __syncthreads();                        // draw 1 runs one phase behind draw 0
-#if SSN_DUO_STAMP == 2
-        {
-            unsigned long long acc6[6] = {0, 0, 0, 0, 0, 0};
-            auto now = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); return (unsigned long long)__builtin_amdgcn_s_memtime(); };
-            const unsigned long long tstart = now();
-            for (int it = 0; it < nskip; ++it) {
-                const unsigned long long t0 = now();
-                chain(it);
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned long long t1 = now();
-                early(W0, it);
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned long long t2 = now();
-                __syncthreads();
-                const unsigned long long t3 = now();
-                compute(W0, it, TB, TM, HAS_TAIL);
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned long long t4 = now();
-                publish(it);
-                const unsigned long long t5 = now();
-                __syncthreads();
-                const unsigned long long t6 = now();
-                acc6[0] += t1 - t0; acc6[1] += t2 - t1; acc6[2] += t3 - t2; acc6[3] += t4 - t3; acc6[4] += t5 - t4; acc6[5] += t6 - t5;
-            }
-            const unsigned long long tend = now();
-            if (blockIdx.x == 0 && lane == 0) {
-                const int w = 4 * d + WV;
-                for (int i = 0; i < 6; ++i) duo_stamps_fine[8 * w + i] = acc6[i];
-                duo_stamps_fine[8 * w + 6] = tend - tstart;
-                duo_stamps_fine[8 * w + 7] = (unsigned long long)nskip;
-            }
-        }
-#elif SSN_DUO_STAMP
-        unsigned long long tc = 0, tb1 = 0, ts = 0, tb2 = 0;
-        for (int it = 0; it < nskip; ++it) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-            chain(it);
-            early(W0, it);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-            __syncthreads();
-            const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-            serial(W0, it);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-            __syncthreads();
-            const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-            tc += t1 - t0; tb1 += t2 - t1; ts += t3 - t2; tb2 += t4 - t3;
-        }
-        if (blockIdx.x == 0 && WV == 0 && lane == 0) {
-            duo_stamps[4 * d + 0] = tc; duo_stamps[4 * d + 1] = tb1; duo_stamps[4 * d + 2] = ts; duo_stamps[4 * d + 3] = tb2;
-            duo_stamps[8] = (unsigned long long)nskip;
-        }
-        if (blockIdx.x == 0 && WV == 3 && lane == 0) {
-            duo_stamps[9 + 3 * d + 0] = tc; duo_stamps[9 + 3 * d + 1] = ts; duo_stamps[9 + 3 * d + 2] = tb1 + tb2;
-        }
-#else
+        Stamp ts;                                      // (the steps before the window, the serial part as its two pieces)
+        ts.start();
         for (int it = 0; it < nskip; ++it) {
             chain(it);
+            ts.lap(0);
             early(W0, it);
+            ts.lap(1);
             duo_phase_barrier();
-            serial(W0, it);
+            ts.lap(2);
+            compute(W0, it, TB, TM, HAS_TAIL);
+            ts.lap(3);
+            publish(it);
+            ts.lap(4);
             duo_phase_barrier();
+            ts.lap(5);
+            ts.tick();
         }
-#endif
+        ts.flush(duo_stamp_row(4 * d + WV));
         for (int it = nskip; it < T_; ++it) {
             chain(it);
             early(W1, it);
@@ -345,8 +269,7 @@ __device__ __forceinline__ void duo_forward_wave(const GenFwdArgs<float>& a, int
 template <int MK, bool SAVE, bool FREE, bool HT>
 __global__ void __launch_bounds__(512, 2) gen_forward_duo_kernel(GenFwdArgs<float> a, int rshift) {
     using S = Duo16<MK>;
-    constexpr int WL = S::nl(SAVE) * 1024;          // LDS-resident part of W, per wave
-    __shared__ __align__(16) char lds[S::LDS + 8 * WL + 16];
+    __shared__ __align__(16) char lds[S::LDS + 16];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (uniform: buffer descriptors stay in SGPRs)
     const int d = wave >> 2;
@@ -359,13 +282,12 @@ __global__ void __launch_bounds__(512, 2) gen_forward_duo_kernel(GenFwdArgs<floa
     for (int c = threadIdx.x; c < S::LDS / 4; c += blockDim.x) reinterpret_cast<unsigned*>(lds)[c] = 0u;
     __syncthreads();                                // (zeroed before any wave records max |W|; state 0 = the B images)
     char* const dlds = lds + d * S::DRAW;
-    char* const wlds = lds + S::LDS + wave * WL;
     unsigned* const wmax = reinterpret_cast<unsigned*>(lds + 2 * S::DRAW) + d;
     switch (wave & 3) {
-        case 0: duo_forward_wave<MK, 0, SAVE, FREE, HT>(a, rshift, d, b, s0, valid, lane, dlds, wlds, wmax); break;
-        case 1: duo_forward_wave<MK, 1, SAVE, FREE, HT>(a, rshift, d, b, s0, valid, lane, dlds, wlds, wmax); break;
-        case 2: duo_forward_wave<MK, 2, SAVE, FREE, HT>(a, rshift, d, b, s0, valid, lane, dlds, wlds, wmax); break;
-        default: duo_forward_wave<MK, 3, SAVE, FREE, HT>(a, rshift, d, b, s0, valid, lane, dlds, wlds, wmax); break;
+        case 0: duo_forward_wave<MK, 0, SAVE, FREE, HT>(a, rshift, d, b, s0, valid, lane, dlds, wmax); break;
+        case 1: duo_forward_wave<MK, 1, SAVE, FREE, HT>(a, rshift, d, b, s0, valid, lane, dlds, wmax); break;
+        case 2: duo_forward_wave<MK, 2, SAVE, FREE, HT>(a, rshift, d, b, s0, valid, lane, dlds, wmax); break;
+        default: duo_forward_wave<MK, 3, SAVE, FREE, HT>(a, rshift, d, b, s0, valid, lane, dlds, wmax); break;
     }
 }
 
@@ -403,21 +325,14 @@ __device__ __forceinline__ void duo_solve_wave(const SolveArgs<float>& a, int d,
     const __amdgpu_buffer_rsrc_t rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W + (size_t)b * M * M), 0, M * M * 4, 0x00020000);
     using Ops = DuoOperands<MK, WV, S::nl_solve()>;
-#if SSN_DUO_ONEPASS_SOLVE
-    typename Ops::Raw raw;
-    __hip_atomic_fetch_max(wmax, __builtin_bit_cast(unsigned, Ops::fetch(rsrc, M, li, lg, raw)), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
+    // (W in two passes, max_abs here and load behind barrier (A): see DuoOperands)
     __hip_atomic_fetch_max(wmax, __builtin_bit_cast(unsigned, Ops::max_abs(rsrc, M, li, lg)), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
     // ---- the values this lane finishes
     const IoSelect io(a.io);
     const int s = s0 + st;
     const bool live = valid && s < a.NB;
-    // (One-pass prologue: the W units are 176-184 live registers across barrier (A), so the lane's state, input and
-    // constants are read BEHIND the split -- alive across it they were spilled and reloaded from scratch in every step;
-    // max |r0| comes from a first read of the same 6-8 values.)
+    // (max |r0| comes from a first read of the lane's 6-8 values, the state, input and constants from a second one)
     float rc[NE], ex[NE], eps[NE];
     float r0max = 0.f;
     auto read_values = [&](bool keep) {
@@ -437,13 +352,13 @@ __device__ __forceinline__ void duo_solve_wave(const SolveArgs<float>& a, int d,
         }
     };
     read_values(false);
-    if (!SSN_DUO_ONEPASS_SOLVE) read_values(true);
+    read_values(true);
     __hip_atomic_fetch_max(wmax + 1, __builtin_bit_cast(unsigned, r0max), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     auto store_prev = [&]() {
         rp_slot[0] = (mf4){rc[0], rc[1], NE > 2 ? rc[2 % NE] : 0.f, NE > 2 ? rc[3 % NE] : 0.f};
         if constexpr (NE > 4) rp_slot[64] = (mf4){rc[4 % NE], rc[5 % NE], NE > 6 ? rc[6 % NE] : 0.f, NE > 6 ? rc[7 % NE] : 0.f};
     };
-    if (!SSN_DUO_ONEPASS_SOLVE) store_prev();                  // (zero steps: previous = initial state; a slot only its own lane reads)
+    store_prev();                                        // (zero steps: previous = initial state; a slot only its own lane reads)
     __syncthreads();                                                          // (A) max |W|, max |r0| of both draws
     // state scale: bound 2^rshift < 2^14 for bound = max(rate_hard_bound, max |r0|): every later state is a convex
     // combination of values inside that bound
@@ -453,13 +368,7 @@ __device__ __forceinline__ void duo_solve_wave(const SolveArgs<float>& a, int d,
     const int wexp = duo_w_exp(wmax[0]);
     const float sa = duo_pow2(wexp), usc = duo_pow2(-wexp - rshift), rs = duo_pow2(rshift);
     Ops ops;
-#if SSN_DUO_ONEPASS_SOLVE
-    ops.split(raw, sa, wwlds, lane);
-    read_values(true);
-    store_prev();
-#else
     ops.load(rsrc, M, li, lg, sa, wwlds, lane);
-#endif
     using LdsH8 = const __attribute__((address_space(3))) hv8*;
     using LdsF4 = __attribute__((address_space(3))) mf4*;
     using LdsU = __attribute__((address_space(3))) unsigned*;
@@ -510,15 +419,15 @@ __device__ __forceinline__ void duo_solve_wave(const SolveArgs<float>& a, int d,
                 sm.x += xp.x; sm.y += xp.y; sm.z += xp.z; sm.w += xp.w;
             }
         }
-        const float j0 = first ? duo_join<true>(sm.x, sm.z, hi, sm.y, sm.w) : duo_join<false>(sm.x, sm.z, hi);
+        const float j0 = first ? duo_join<true>(sm.x, sm.z, hi) : duo_join<false>(sm.x, sm.z, hi);
         u0 = fmaf(j0, usc, ex[2 * tf]);
-        u1 = fmaf(duo_join<false>(sm.y, sm.w, hi), usc, ex[2 * tf + 1]);
+        u1 = fmaf(duo_join(sm.y, sm.w, hi), usc, ex[2 * tf + 1]);
     };
     // One row tile early (as the forward, 3.13c): the wave that has ended its chain computes the candidate state of its LAST
     // row tile right behind the chain, in the chain's phase -- join, f(u), Euler step: registers only; whether the step is
     // applied, the stop flags, the previous state and the publication stay in the serial phase.  Same values bit for bit.
     constexpr int TE = NTF - 1;
-    constexpr bool EARLY = SSN_DUO_EARLY_SOLVE == 2 ? NTF > 3 : (SSN_DUO_EARLY_SOLVE && NTF > 1);    // (2: the four-tile wave only)
+    constexpr bool EARLY = S::early_solve(NTF);             // (the four-tile wave only)
     constexpr int NS = EARLY ? NE - 2 : NE;                 // values the serial phase still finishes (row tiles 0 .. TE - 1)
     float r1e[2] = {0.f, 0.f};
     auto early = [&]() {
@@ -546,11 +455,8 @@ __device__ __forceinline__ void duo_solve_wave(const SolveArgs<float>& a, int d,
         }
         const bool take = live && !((frozen >> st) & 1u);
         const bool ncv = dmax >= a.st.atol;                                      // ssnode.c:84-90 (a NaN difference does not count)
-#if SSN_DUO_TEST_EVERY > 1
-        // TIMING BUILD ONLY (wrong stop steps): the cross-lane part of the stop test every SSN_DUO_TEST_EVERY-th step, to price
-        // what a k-step test with exact replay could save at most
-        if ((it & (SSN_DUO_TEST_EVERY - 1)) == SSN_DUO_TEST_EVERY - 1 || it >= max_iter - 1) {
-#endif
+        // (timing builds with the cross-lane part of the stop test only every 4th step, and with the previous state written in
+        // every step as a state ring would need, priced what a k-step test with exact replay could save: DESIGN 3.13c, round 5)
         unsigned long long votes = __builtin_amdgcn_ballot_w64(take && ncv);
         unsigned bits;
         if (a.st.check_hard) {                                                   // (uniform; never with the saturating I/O function)
@@ -570,15 +476,11 @@ __device__ __forceinline__ void duo_solve_wave(const SolveArgs<float>& a, int d,
         const unsigned fbase = (unsigned)(size_t)flags;
         if (WV == 0 && lane == 0) *(LdsW)(size_t)(fbase + 4u * (unsigned)(slot == 2 ? 0 : slot + 1)) = 0u;
         if (lane == 0 && bits) asm volatile("ds_or_b32 %0, %1" : : "v"(fbase + 4u * (unsigned)slot), "v"(bits) : "memory");
-#if SSN_DUO_TEST_EVERY > 1
-        }
-        if (SSN_DUO_TEST_RING && take) store_prev();       // (what a state ring would write per step)
-#endif
         if (take) {
             // r_prev = the state before the LAST applied step.  The last applied step of a stimulus is the one at which all of
             // its rows pass the convergence test (or step max_iter - 1), so a lane whose own rows do not pass it knows that this
             // step is not the last and need not save -- unless a rate-bound test (any row of any lane) can end the solve too.
-            if (SSN_DUO_PREV_ALWAYS || !ncv || it >= max_iter - 1 || a.st.check_hard) store_prev();
+            if (!ncv || it >= max_iter - 1 || a.st.check_hard) store_prev();
 #pragma unroll
             for (int i = 0; i < NE; ++i) rc[i] = r1[i];         // (a row that does not exist steps from 0 to 0: see above)
             store_state();
@@ -587,10 +489,7 @@ __device__ __forceinline__ void duo_solve_wave(const SolveArgs<float>& a, int d,
     __syncthreads();                                                          // (B)
     bool finished = !valid;
     int it = 0;
-#if SSN_DUO_STAMP
-    unsigned long long st_c = 0, st_v = 0, st_b1 = 0, st_s = 0, st_b2 = 0; int st_n = 0;
-#define SSN_SOLVE_NOW() ({ asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); (unsigned long long)__builtin_amdgcn_s_memtime(); })
-#endif
+    Stamp ts;
     for (int p = 0;; ++p) {
         // flag word of my draw's last finished step (lanes 0-7) and both `done` words of the previous phase (lanes 8, 9): the
         // read is issued here and first used BEHIND the chain -- nothing in front of the chain waits for LDS
@@ -600,10 +499,7 @@ __device__ __forceinline__ void duo_solve_wave(const SolveArgs<float>& a, int d,
             const LdsI src = lane < 8 ? flags + (slot == 0 ? 2 : slot - 1) : (LdsI)(done + ((p + 1) & 1) * 2 + (lane & 1));
             if (lane < 10) word = *src;
         }
-#if SSN_DUO_STAMP
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        unsigned long long t1 = t0;
-#endif
+        ts.start();
         if (chain_phase && p >= d) {
             // The chain of step `it` runs before the verdict on step it - 1 is known: it reads the state that step published
             // whatever the verdict says, and if the verdict ends the solve its sums are simply not used.
@@ -618,14 +514,8 @@ __device__ __forceinline__ void duo_solve_wave(const SolveArgs<float>& a, int d,
                 for (int t = 0; t < NT; ++t) asm volatile("" : "=v"(acc[t]));
                 asm volatile("" : "=v"(r1e[0]), "=v"(r1e[1]));
             }
-#if SSN_DUO_STAMP
-            t1 = SSN_SOLVE_NOW();
-#endif
-#if SSN_DUO_TEST_EVERY > 1
-            if (!finished && it >= 1 && (((it - 1) & (SSN_DUO_TEST_EVERY - 1)) == SSN_DUO_TEST_EVERY - 1 || it >= max_iter - 1)) verdict(it - 1, word);
-#else
+            ts.lap(0, !finished);
             if (!finished && it >= 1) verdict(it - 1, word);
-#endif
             if (frozen == 0xffu || it >= max_iter) finished = true;
         } else if (p >= d) {
             if (!finished) serial(it);
@@ -634,25 +524,14 @@ __device__ __forceinline__ void duo_solve_wave(const SolveArgs<float>& a, int d,
         }
         if (WV == 0 && lane == 0) done[(p & 1) * 2 + d] = finished ? 1u : 0u;
         const bool both = p >= 1 && __builtin_amdgcn_readlane(word, 8) != 0 && __builtin_amdgcn_readlane(word, 9) != 0;
-#if SSN_DUO_STAMP
-        const unsigned long long t2 = SSN_SOLVE_NOW();
+        const bool timed = p >= d && !finished;         // (segments 0 .. 2: a chain phase, 3 and 4: a serial phase)
+        ts.lap(chain_phase ? 1 : 3, timed);
         duo_phase_barrier();
-        const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-        if (p >= d && !finished) {
-            if (chain_phase) { st_c += t1 - t0; st_v += t2 - t1; st_b1 += t3 - t2; ++st_n; }
-            else { st_s += t2 - t0; st_b2 += t3 - t2; }
-        }
-#else
-        duo_phase_barrier();
-#endif
+        ts.lap(chain_phase ? 2 : 4, timed);
+        ts.tick(chain_phase && timed);
         if (both) break;
     }
-#if SSN_DUO_STAMP
-    if (blockIdx.x == 0 && lane == 0) {             // every wave of workgroup 0: [8 w + 0 .. 4] segment sums, [8 w + 5] steps
-        unsigned long long* o = duo_stamps_fine + 8 * (4 * d + WV);
-        o[0] = st_c; o[1] = st_v; o[2] = st_b1; o[3] = st_s; o[4] = st_b2; o[5] = (unsigned long long)st_n;
-    }
-#endif
+    ts.flush(duo_stamp_row(4 * d + WV));
     if (valid && s < a.NB) {
         const size_t unit = (size_t)b * a.NB + s;
 #pragma unroll
@@ -729,12 +608,8 @@ __device__ __forceinline__ void duo_backward_wave(const GenBwdArgs<float>& a, in
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W + (size_t)b * M * M), 0, M * M * 4, 0x00020000);
     using Ops = DuoOperands<MK, WV, S::nl_bwd_win(WV, WS::NTF), true>;             // window steps
     using OpsN = DuoOperands<MK, WV, S::nl_bwd(WS::NTF, GEXT), true>;            // the steps after the window
-#if SSN_DUO_ONEPASS
     typename Ops::Raw raw;
     atomicMax(wmax, __builtin_bit_cast(unsigned, Ops::fetch(rsrc, M, li, lg, raw)));
-#else
-    atomicMax(wmax, __builtin_bit_cast(unsigned, Ops::max_abs(rsrc, M, li, lg)));
-#endif
     using LdsH8 = const __attribute__((address_space(3))) hv8*;
     using LdsF4 = __attribute__((address_space(3))) mf4*;
     using LdsU = __attribute__((address_space(3))) unsigned*;
@@ -775,7 +650,7 @@ __device__ __forceinline__ void duo_backward_wave(const GenBwdArgs<float>& a, in
     auto store2 = [&](const __amdgpu_buffer_rsrc_t& rs, bool on, const At& p, float x0, float x1) {
         const fv2 q = {x0, x1};
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(unsigned __attribute__((ext_vector_type(2))), q), on ? rs : rs_none,
-                                              voff[p.tf], on ? soff(p) : 0, SSN_DUO_STORE_AUX);
+                                              voff[p.tf], on ? soff(p) : 0, 0);
     };
     // f'(u) of three consecutive steps in a rotating set of registers: the step with phase PH = (T - tau) % 3 uses
     // df3[(PH + 1) % 3] and loads, two steps ahead, into df3[PH] -- no register copies between steps, so the wait for a
@@ -791,11 +666,7 @@ __device__ __forceinline__ void duo_backward_wave(const GenBwdArgs<float>& a, in
     __syncthreads();                                                          // (A) max |W|
     const int wexp = duo_w_exp(*wmax);
     Ops ops;
-#if SSN_DUO_ONEPASS
     ops.split(raw, duo_pow2(wexp), wwlds, lane);
-#else
-    ops.load(rsrc, M, li, lg, duo_pow2(wexp), wwlds, lane);
-#endif
     // (the per-value state is set up AFTER the W prologue, the one place where every register is taken: set up before it,
     // two of the window's constants were spilled there and reloaded from scratch -- with s_waitcnt vmcnt(0) -- in every step)
     float m0 = 0.f;
@@ -859,9 +730,8 @@ __device__ __forceinline__ void duo_backward_wave(const GenBwdArgs<float>& a, in
                 sm.x += xp.x; sm.y += xp.y; sm.z += xp.z; sm.w += xp.w;
             }
         }
-        // (every join_tile call may be the first reader of a chain's sums: the wait states go with each tile's first join)
-        carry[2 * tf] = fmaf(duo_join<true>(sm.x, sm.z, hi, sm.y, sm.w), usc, carry[2 * tf]);
-        carry[2 * tf + 1] = fmaf(duo_join<false>(sm.y, sm.w, hi), usc, carry[2 * tf + 1]);
+        carry[2 * tf] = fmaf(duo_join(sm.x, sm.z, hi), usc, carry[2 * tf]);
+        carry[2 * tf + 1] = fmaf(duo_join(sm.y, sm.w, hi), usc, carry[2 * tf + 1]);
     };
     auto early = [&](auto PH, int tau) {             // step tau (no window terms), tile TE; runs behind the chain of step tau + 1
         constexpr int ph = decltype(PH)::value;
@@ -956,55 +826,35 @@ __device__ __forceinline__ void duo_backward_wave(const GenBwdArgs<float>& a, in
     constexpr std::integral_constant<bool, true> W1{};
     __syncthreads();                                                          // (B)
     if (d) __syncthreads();                            // draw 1 runs one phase behind draw 0
-#if SSN_DUO_STAMP
-    unsigned long long st_s = 0, st_b1 = 0, st_c = 0, st_b2 = 0; int st_n = 0;
-#endif
+    Stamp ts;                                          // (the steps after the window)
     constexpr std::integral_constant<bool, false> E0{};
     constexpr std::integral_constant<bool, true> E1{};
     auto step = [&](auto WIN, auto PH, int tau, const auto& o) {
-#if SSN_DUO_STAMP
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+        constexpr bool timed = !decltype(WIN)::value;
+        ts.start();
         serial(WIN, PH, tau, E0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+        ts.lap(0, timed);
         duo_phase_barrier();
-        const unsigned long long t2 = __builtin_amdgcn_s_memtime();
+        ts.lap(1, timed);
         chain(o);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long t3 = __builtin_amdgcn_s_memtime();
+        ts.lap(2, timed);
         duo_phase_barrier();
-        const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-        if (!decltype(WIN)::value) { st_s += t1 - t0; st_b1 += t2 - t1; st_c += t3 - t2; st_b2 += t4 - t3; ++st_n; }   // steps after the window
-#else
-        serial(WIN, PH, tau, E0);
-        duo_phase_barrier();
-        chain(o);
-        duo_phase_barrier();
-#endif
+        ts.lap(3, timed);
+        ts.tick(timed);
     };
     // a step after the window whose last tile was finished early, finishing the next step's last tile behind its own chain
     auto step_e = [&](auto PH, auto PHN, int tau, bool more, const auto& o) {
-#if SSN_DUO_STAMP
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+        ts.start();
         serial(W0, PH, tau, E1);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+        ts.lap(0);
         duo_phase_barrier();
-        const unsigned long long t2 = __builtin_amdgcn_s_memtime();
+        ts.lap(1);
         chain(o);
         if (more) early(PHN, tau - 1);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long t3 = __builtin_amdgcn_s_memtime();
+        ts.lap(2);
         duo_phase_barrier();
-        const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-        st_s += t1 - t0; st_b1 += t2 - t1; st_c += t3 - t2; st_b2 += t4 - t3; ++st_n;
-#else
-        serial(W0, PH, tau, E1);
-        duo_phase_barrier();
-        chain(o);
-        if (more) early(PHN, tau - 1);
-        duo_phase_barrier();
-#endif
+        ts.lap(3);
+        ts.tick();
     };
     constexpr std::integral_constant<int, 0> P0{};
     constexpr std::integral_constant<int, 1> P1{};
@@ -1031,7 +881,7 @@ __device__ __forceinline__ void duo_backward_wave(const GenBwdArgs<float>& a, in
     OpsN opsn;                                         // the window is over: its registers go to W^T (fewer LDS reads per chain)
     opsn.promote_from(ops);
     while (tau >= 1 && ph != 0) step_any(W0, opsn);
-    if constexpr (SSN_DUO_EARLY_BWD && NTF > 3) {       // (the four-tile wave only: for the others chain + tile outlasts the serial part it shortens)
+    if constexpr (S::EARLY_BWD && NTF > 3) {       // (the four-tile wave only: for the others chain + tile outlasts the serial part it shortens)
         if (tau >= 3) early(P0, tau);                  // (primes the pipeline: once, outside a chain phase)
         for (; tau >= 3; tau -= 3) {
             step_e(P0, P1, tau, true, opsn);
@@ -1046,12 +896,7 @@ __device__ __forceinline__ void duo_backward_wave(const GenBwdArgs<float>& a, in
         }
     }
     while (tau >= 1) step_any(W0, opsn);
-#if SSN_DUO_STAMP
-    if (blockIdx.x == 0 && (WV == 0 || WV == 3) && d == 0 && lane == 0) {
-        unsigned long long* o = duo_stamps + (WV == 0 ? 0 : 4);
-        o[0] = st_c; o[1] = st_b2; o[2] = st_s; o[3] = st_b1; duo_stamps[8] = (unsigned long long)st_n;
-    }
-#endif
+    ts.flush(duo_stamp_row(4 * d + WV));
     if (!d) __syncthreads();
     // the bound ssn_gw.hip scales the draw's delta with (the prologue's estimate of max |delta_T| in the first word read
     // only makes it larger; a poisoned step stores NaN and the products are NaN whatever the scale)
@@ -1186,10 +1031,7 @@ hipError_t launch_gen_backward_duo(const GenBwdArgs<float>& a, hipStream_t st) {
 }  // namespace ssn
 
 #if SSN_DUO_STAMP
-extern "C" int ssn_debug_duo_stamps_fine(unsigned long long* out64) {
-    return (int)hipMemcpyFromSymbol(out64, HIP_SYMBOL(ssn::duo_stamps_fine), 64 * sizeof(unsigned long long));
-}
-extern "C" int ssn_debug_duo_stamps(unsigned long long* out16) {
-    return (int)hipMemcpyFromSymbol(out16, HIP_SYMBOL(ssn::duo_stamps), 16 * sizeof(unsigned long long));
+extern "C" int ssn_debug_duo_stamps(unsigned long long* out64) {
+    return (int)hipMemcpyFromSymbol(out64, HIP_SYMBOL(ssn::duo_stamps), 64 * sizeof(unsigned long long));
 }
 #endif

@@ -10,68 +10,9 @@
 #include "ssn_mfma_io.h"
 
 
-#ifndef SSN_DUO_EARLY
-#define SSN_DUO_EARLY 1         // row tiles a wave finishes right behind its own chain (forward kernels; 0 = none)
-#endif
-#ifndef SSN_DUO_EARLY_MASK
-#define SSN_DUO_EARLY_MASK 0xf  // ... for the waves w of a draw with bit w set (the others finish every tile in the serial phase)
-#endif
-#ifndef SSN_DUO_PREB
-#define SSN_DUO_PREB 0          // forward: 1 = the B operand of the wave's own k tile is read in front of the phase barrier and the
-                                // chain starts with that tile (measured at C3, same box, three alternating runs: 3.14 ms against
-                                // 3.16 -- the first read behind the barrier is not what stretches a chain; off); 2 = the MFMAs of
-                                // that tile as well, at the end of the serial phase (3.17-3.22 against 3.13-3.14: they take
-                                // from the partner wave's chain what they save the own one)
-#endif
-#ifndef SSN_DUO_TEST_EVERY
-#define SSN_DUO_TEST_EVERY 1   // > 1 (power of two): TIMING BUILD, wrong stop steps -- see solve serial part in ssn_duo.hip
-#endif
-#ifndef SSN_DUO_PREV_ALWAYS
-#define SSN_DUO_PREV_ALWAYS 0
-#endif
-#ifndef SSN_DUO_TEST_RING
-#define SSN_DUO_TEST_RING 0
-#endif
-#ifndef SSN_DUO_EARLY_SOLVE
-#define SSN_DUO_EARLY_SOLVE 2   // solver: the candidate state of a wave's last row tile behind its own chain: 2 = the four-tile wave only
-                                // (27.4 ms at C2 with 8 stimuli against 28.3 with 1 = every wave and 29.1 with 0 = none, same box)
-#endif
-#ifndef SSN_DUO_EARLY_BWD
-#define SSN_DUO_EARLY_BWD 1     // adjoint sweep: the last row tile of a step after the window behind the previous step's chain (0 = off)
-#endif
-#ifndef SSN_DUO_SOLVE_NL
-#define SSN_DUO_SOLVE_NL 4      // solver, 2N > 152: units of every wave whose low part W_m lives in LDS instead of registers
-#endif
-#ifndef SSN_DUO_BPF
-#define SSN_DUO_BPF 1           // chains: the B operand of k tile kk + 1 is requested before the MFMAs of tile kk (0 = compiler's order)
-#endif
-#ifndef SSN_DUO_ABLATE
-#define SSN_DUO_ABLATE 0        // diagnostic builds (timing only, wrong results): 1 = no nonlinearity, 2 = one FMA per MFMA,
-                                // 4 / 8 = serial part / chain at s_setprio 1
-#endif
-
 #ifndef SSN_DUO_STAMP
-#define SSN_DUO_STAMP 0         // diagnostic build: s_memtime stamps of workgroup 0 (waves 0 and 4) summed per segment into
-                                // duo_stamps[] (read back by ssn_debug_duo_stamps; tools/time_fwd.py prints them)
-#endif
-
-
-#ifndef SSN_DUO_NL_SAVE
-#define SSN_DUO_NL_SAVE 0           // W parts per wave the forward with stores keeps in LDS (2N > 152; 4 until round 4: 5.1-5.3 against 5.02 ms)
-#endif
-#ifndef SSN_DUO_STORE_LAYOUT
-#define SSN_DUO_STORE_LAYOUT 0    // 1: timing experiment, WRONG results -- every wave store 512 contiguous bytes
-#endif
-#ifndef SSN_DUO_ONEPASS
-#define SSN_DUO_ONEPASS 1         // W prologue: 1 = the units fetched for max |W| stay in registers and are split from there (W read once);
-                                  // 0 = round 4's two passes (max |W|, barrier, fetch again and split)
-#endif
-#ifndef SSN_DUO_ONEPASS_SOLVE
-#define SSN_DUO_ONEPASS_SOLVE 0   // ... in solve_duo_kernel (2N > 152: the one kernel whose time loop has no register to spare -- with the
-                                  // fp32 units alive across barrier (A) the allocator reloads 11 values from scratch in every step)
-#endif
-#ifndef SSN_DUO_STORE_AUX
-#define SSN_DUO_STORE_AUX 0       // cache policy of the trajectory / f' / delta stores (raw buffer store aux: 1 sc0, 2 nt, 16 sc1)
+#define SSN_DUO_STAMP 0         // diagnostic build: s_memtime ticks of workgroup 0, per wave and segment of a step, in
+                                // duo_stamps[] (DuoStamp below; read back by ssn_debug_duo_stamps, printed by tools/time_*.py)
 #endif
 
 namespace ssn {
@@ -106,9 +47,17 @@ struct Duo16 {
     // plain forward 3.38 ms with NL = 0 against 3.67 with 4 (the extra reads sit on the chain's critical path, and it did not
     // spill); forward with stores 6.1 -> 5.6 ms, solver 40.2 -> 34.3 ms with NL = 4.  (Round 4: with the chain's B operand one tile
     // ahead and the serial part as it is now, the forward with stores no longer spills in the time loop at NL = 0: 5.02 ms
-    // against 5.1-5.3 with 4, SSN_DUO_NL_SAVE.)
-    static constexpr int nl(bool heavy) { return (heavy && MK > 152) ? SSN_DUO_NL_SAVE : 0; }
-    static constexpr int nl_solve() { return MK > 152 ? SSN_DUO_SOLVE_NL : 0; }
+    // against 5.1-5.3 with 4, so both forward kernels keep every unit in registers.)
+    static constexpr int SOLVE_NL = 4;                                   // solver, 2N > 152: units of every wave whose low part W_m lives in LDS
+    static constexpr int nl_solve() { return MK > 152 ? SOLVE_NL : 0; }
+    // Row tiles a wave finishes right behind its own chain, in the chain's phase (ssn_duo.hip):
+    // forward kernels: one, every wave (only the four-tile wave: 3.07-3.09 against 3.07-3.23 ms at C3, no gain)
+    static constexpr int EARLY = 1;
+    // solver: the candidate state of the last row tile, the four-tile wave only (27.4 ms at C2 with 8 stimuli against 28.3
+    // with every wave and 29.1 with none, same box)
+    static constexpr bool early_solve(int ntf) { return ntf > 3; }
+    // adjoint sweep: the last row tile of a step after the window behind the previous step's chain (the four-tile wave only)
+    static constexpr bool EARLY_BWD = true;
     // adjoint sweep: 10 state values per row and stimulus -- by the number of row tiles a wave finishes (6 or 8 values per lane)
     // (window steps / the steps after the window: the window keeps four trajectory rows per value in registers)
     // (wave 0 of the window loop is the one short of registers: it takes three units from its two three-tile neighbours)
@@ -156,49 +105,35 @@ __device__ __forceinline__ float dpp_ror8(float x) {                  // lane li
 // Join of the two parts of a row tile's sums.  After the chain lanes s and 8 + s of a 16-lane row hold, for rows 0 .. 3 of the
 // tile (registers x, y, z, w), the products with the two fp16 parts of stimulus s; lane s (DPP banks 0, 1 of its row)
 // finishes rows 0, 1 and lane 8 + s (banks 2, 3) rows 2, 3: value e of a lane is lo_e + ror8(lo_e) in banks 0, 1 and
-// hi_e + ror8(hi_e) in banks 2, 3.  Two DPP adds with complementary bank masks write each half of the row from its own
-// register -- no selects (the builtin form, `hi ? z : x` twice and one DPP add, is three instructions per value).
-// Inline asm hides the instructions from the compiler's hazard recognizer, so the wait states are spelled out: FIRST = the
-// first join after a chain or after compiler-generated VALU writes of the operands: 11 wait states cover a finished
-// 8-pass MFMA -> VALU read and the 2 a VALU write -> DPP read needs.  The joins are volatile: they keep their order.
-// MEASURED (C3 forward, same box, both builds loaded in alternation): 3.20 ms with the asm form, 3.21 ms with the builtin
-// form -- 7 instructions fewer per serial part (of ~130) buy nothing, the wait states cost what the selects did.  The
-// builtin form is the default; -DSSN_DUO_JOIN_ASM=1 builds the other one (parity-green on the same tests).
-#ifndef SSN_DUO_JOIN_ASM
-#define SSN_DUO_JOIN_ASM 0
-#endif
-// (`also0/1`: the operands of the tile's SECOND join, named as inputs of the first so that compiler-generated writes
-// of them -- the partial sum of a neighbour wave added to a shared tile -- sit in front of the wait states as well.)
-template <bool FIRST>
-__device__ __forceinline__ float duo_join(float lo, float hi, int is_hi, float also0 = 0.f, float also1 = 0.f) {
-#if SSN_DUO_JOIN_ASM
-    float r;
-    if (FIRST) asm volatile("s_nop 10\n\tv_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3"
-                            : "=v"(r) : "v"(lo), "v"(hi), "v"(also0), "v"(also1));
-    else asm volatile("v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3" : "=v"(r) : "v"(lo));
-    asm volatile("v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xc" : "+v"(r) : "v"(hi));
-    return r;
-#else
+// hi_e + ror8(hi_e) in banks 2, 3 -- `hi ? z : x` twice and one DPP add, three instructions per value.
+// MEASURED (C3 forward, same box, both builds loaded in alternation): two inline-assembly DPP adds with complementary bank
+// masks and no selects, the MFMA -> VALU wait states spelled out, took 3.20 ms against 3.21 ms for this form -- 7 instructions
+// fewer per serial part (of ~130) buy nothing, the wait states cost what the selects did.
+// FIRST marks a tile's first join behind a chain (where that form put its wait states) and changes nothing in this one.  The
+// forward's and the solver's serial parts still name it, `first ? duo_join<true>(..) : duo_join<false>(..)`: with one plain
+// call there the compiler orders their instructions differently (same arithmetic, other select operands and schedule), and a
+// time loop's schedule changes only with a measurement.
+template <bool FIRST = false>
+__device__ __forceinline__ float duo_join(float lo, float hi, int is_hi) {
     const float k = is_hi ? hi : lo, o = is_hi ? lo : hi;
     return k + dpp_ror8(o);
-#endif
 }
 
 // max over the wave of a non-negative float (bit patterns order like the values), the same value in every lane's SGPR copy
 __device__ __forceinline__ unsigned duo_wave_max_bits(float x) {
     unsigned v = __builtin_bit_cast(unsigned, x);
-#define SSN_DUO_DPP_MAX(CTRL, ROWMASK)                                                                                   \
+#define DUO_DPP_MAX(CTRL, ROWMASK)                                                                                   \
     {                                                                                                                     \
         const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWMASK, 0xf, false);                   \
         v = o > v ? o : v;                                                                                                \
     }
-    SSN_DUO_DPP_MAX(0xB1, 0xf)     // quad_perm [1,0,3,2]
-    SSN_DUO_DPP_MAX(0x4E, 0xf)     // quad_perm [2,3,0,1]
-    SSN_DUO_DPP_MAX(0x141, 0xf)    // row_half_mirror
-    SSN_DUO_DPP_MAX(0x140, 0xf)    // row_mirror: every lane = row max
-    SSN_DUO_DPP_MAX(0x142, 0xa)    // row_bcast15 -> rows 1, 3
-    SSN_DUO_DPP_MAX(0x143, 0xc)    // row_bcast31 -> rows 2, 3
-#undef SSN_DUO_DPP_MAX
+    DUO_DPP_MAX(0xB1, 0xf)     // quad_perm [1,0,3,2]
+    DUO_DPP_MAX(0x4E, 0xf)     // quad_perm [2,3,0,1]
+    DUO_DPP_MAX(0x141, 0xf)    // row_half_mirror
+    DUO_DPP_MAX(0x140, 0xf)    // row_mirror: every lane = row max
+    DUO_DPP_MAX(0x142, 0xa)    // row_bcast15 -> rows 1, 3
+    DUO_DPP_MAX(0x143, 0xc)    // row_bcast31 -> rows 2, 3
+#undef DUO_DPP_MAX
     return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
@@ -223,7 +158,9 @@ struct DuoOperands {
     hv8 Ah[NU], Am[NR > 0 ? NR : 1];
     unsigned wl;                                  // LDS byte address of this lane's slot of the first LDS-resident unit
 
-    // pass 1 over the wave's units: max |W|
+    // Two passes over W, for solve_duo_kernel only (and max_abs for the fused sweep, which splits into its own layout): its
+    // time loop has no register to spare for fetch()'s fp32 units, alive across barrier (A) (the allocator reloaded 11 values
+    // from scratch in every step: 32.6 against 29.9 ms).  Pass 1 over the wave's units: max |W|
     static __device__ __forceinline__ float max_abs(const __amdgpu_buffer_rsrc_t& rsrc, int M, int li, int lg) {
         float mx = 0.f;
         for (int u = U0; u < U1; ++u) {
@@ -235,7 +172,7 @@ struct DuoOperands {
         }
         return mx;
     }
-    // ONE pass over W (SSN_DUO_ONEPASS, default): the wave's units stay in registers as fp32 from the fetch that finds max |W|
+    // ONE pass over W (forward, adjoint sweep): the wave's units stay in registers as fp32 from the fetch that finds max |W|
     // (NU x 8 = 176-184 registers, the size of the two fp16 parts they become: each unit's 8 registers turn into its
     // 4 + 4), so the draw's W crosses HBM once per launch instead of twice.  Same loads, same arithmetic, same bits.
     struct Raw { float w[NU][8]; };
@@ -303,53 +240,27 @@ struct DuoOperands {
         }
         wl = o.wl + (unsigned)((NR - NR2) * 1024);
     }
-    // The k tile whose B rows (row tiles 2 kt and 2 kt + 1) this wave finishes and publishes ITSELF, or -1: its B operand can
-    // be read back right after the wave's own stores (the DS instructions of one wave execute in order), in front of the
-    // barrier that the other k tiles have to wait for.
-    static constexpr int own_kt() {
-        for (int kt = 0; kt < S::NKT; ++kt) {
-            const int r0 = 2 * kt, r1 = 2 * kt + 1;
-            const bool in0 = r0 >= RT0 && r0 < RT0 + WS::NTF;
-            const bool in1 = r1 >= S::NRT || (r1 >= RT0 && r1 < RT0 + WS::NTF);
-            if (in0 && in1) return kt;
-        }
-        return -1;
-    }
     static __device__ __forceinline__ hv8 read_b(unsigned rd, int kt) {
         using LdsB = const __attribute__((address_space(3))) hv8*;
         return *(LdsB)(size_t)(rd + (unsigned)(kt * 4 * S::BROW));
     }
     // acc[t] = (W_h + W_m)[row tile RT0 + t, my k range] . B, B read from the image at LDS byte address rd (per lane).
-    // ROT: the k tiles in the order own_kt(), own_kt() + 1, ... (mod NKT); PRE: the first of them comes in `bpre`.
-    // KA .. KB: the part of that order to run (the whole chain by default; SSN_DUO_PREB = 2 runs [0, 1) -- the wave's own k
-    // tile -- in front of the barrier, at the end of the serial phase, and [1, NKT) behind it); the sums start at zero with KA = 0.
-    template <bool ROT = false, bool PRE = false, int KA = 0, int KB = S::NKT>
-    __device__ __forceinline__ void chain(unsigned rd, mf4 (&acc)[NT], const hv8& bpre = hv8{}) const {
+    // (The wave's own k tile read in front of the phase barrier and run first: 3.14 against 3.16 ms at C3, neutral; with its
+    // MFMAs in front of the barrier as well 3.17-3.22 against 3.13-3.14, taken from the partner wave's chain: DESIGN 3.13c.)
+    __device__ __forceinline__ void chain(unsigned rd, mf4 (&acc)[NT]) const {
         using LdsB = const __attribute__((address_space(3))) hv8*;
-        constexpr int K0 = (ROT && own_kt() >= 0) ? own_kt() : 0;
-        if constexpr (KA == 0) {
 #pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = (mf4){0.f, 0.f, 0.f, 0.f};
-        }
-        // B operands one k tile AHEAD of the MFMAs that take them (SSN_DUO_BPF): left to itself the compiler issues a tile's
+        for (int t = 0; t < NT; ++t) acc[t] = (mf4){0.f, 0.f, 0.f, 0.f};
+        // B operands one k tile AHEAD of the MFMAs that take them: left to itself the compiler issues a tile's
         // ds_read_b128 right in front of its first MFMA and waits (seen in the assembly: read, s_waitcnt lgkmcnt(0), six MFMAs,
         // seven times per chain in the register-bound kernels) -- ~100 cycles of LDS latency per k tile with the matrix pipe idle.
         // The scheduling fence keeps the prefetch in front of the tile's MFMAs; the wait it needs is a counted one, one tile later.
-        hv8 bnext = hv8{};
-        if constexpr (SSN_DUO_BPF && KA < KB) {
-            if (!(PRE && ROT && own_kt() >= 0 && KA == 0)) bnext = read_b(rd, (K0 + KA) % S::NKT);
-        }
+        hv8 bnext = read_b(rd, 0);
 #pragma unroll
-        for (int kk = KA; kk < KB; ++kk) {
-            const int kt = (K0 + kk) % S::NKT;
-            hv8 b1;
-            if constexpr (SSN_DUO_BPF) {
-                b1 = (PRE && ROT && own_kt() >= 0 && kk == 0) ? bpre : bnext;
-                if (kk + 1 < KB) bnext = read_b(rd, (K0 + kk + 1) % S::NKT);
-                __builtin_amdgcn_sched_barrier(0);
-            } else {
-                b1 = (PRE && ROT && own_kt() >= 0 && kk == 0) ? bpre : read_b(rd, kt);
-            }
+        for (int kt = 0; kt < S::NKT; ++kt) {
+            const hv8 b1 = bnext;
+            if (kt + 1 < S::NKT) bnext = read_b(rd, kt + 1);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int part = 0; part < 2; ++part) {
 #pragma unroll
@@ -361,8 +272,7 @@ struct DuoOperands {
                         if (part == 0) aop = Ah[ui];
                         else if (ui < NR) aop = Am[ui < NR ? ui : 0];
                         else aop = *(LdsB)(size_t)(wl + (unsigned)((ui - NR) * 1024));
-                        if (SSN_DUO_ABLATE & 2) acc[t].x += (float)aop[0] * (float)b1[0];   // (one FMA per MFMA)
-                        else acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aop, b1, acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aop, b1, acc[t], 0, 0, 0);
                     }
                 }
             }
@@ -402,6 +312,37 @@ __device__ __forceinline__ void duo_phase_barrier() {
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
 }
+
+// In-kernel segment timers of the diagnostic builds (SSN_DUO_STAMP, SSN_FUSE_STAMP): a time loop calls them unconditionally,
+// every member is empty in the product.  lap(s) ends segment s and starts the next one (the wave's LDS traffic drained, nothing
+// scheduled across it), so the segments of a step add up to its ticks; a row of the device array is segments 0 .. 5, the
+// ticks from the first start() to the last lap, the steps counted (the ticks are shader cycles here).
+template <bool ON>
+struct DuoStamp {
+    __device__ __forceinline__ void start() {}
+    __device__ __forceinline__ void lap(int, bool = true) {}
+    __device__ __forceinline__ void tick(bool = true) {}
+    __device__ __forceinline__ void flush(unsigned long long*) const {}
+};
+template <>
+struct DuoStamp<true> {
+    unsigned long long seg[6] = {0, 0, 0, 0, 0, 0}, first = 0, t = 0, steps = 0;
+    __device__ __forceinline__ void start() { t = __builtin_amdgcn_s_memtime(); first = first ? first : t; }
+    __device__ __forceinline__ void lap(int s, bool on = true) {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const unsigned long long now = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+        if (on) seg[s] += now - t;
+        t = now;
+    }
+    __device__ __forceinline__ void tick(bool on = true) { steps += on ? 1 : 0; }
+    __device__ __forceinline__ void flush(unsigned long long* row) const {          // row: 8 words of this wave, workgroup 0 only
+        if (blockIdx.x != 0 || (threadIdx.x & 63) != 0) return;
+        for (int i = 0; i < 6; ++i) row[i] = seg[i];
+        row[6] = t - first; row[7] = steps;
+    }
+};
 
 template <bool WANT_DF, int NE>
 __device__ __forceinline__ void duo_eval(const IoSelect& io, const float (&uu)[NE], float (&ff)[NE], float (&dfn)[NE]) {

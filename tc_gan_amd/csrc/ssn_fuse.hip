@@ -4,7 +4,7 @@
 // two launches at small draw counts and is 7 % slower at 1024 draws (8.93 against 8.3-8.4 ms), DESIGN 3.7d says why.
 //
 //   workgroup = 4 waves = ONE draw, one wave per SIMD, so a wave may use the whole 512-entry register file: its quarter of
-//   W^T as fp16 parts (SSN_FUSE_NPREG 16 x 32 parts in registers, the rest in LDS) AND a strip of the 13 x 13 grid of 16 x 16
+//   W^T as fp16 parts (FuseLds::NPREG 16 x 32 parts in registers, the rest in LDS) AND a strip of the 13 x 13 grid of 16 x 16
 //   accumulator tiles of dL/dW (FuseTiles: 43 / 42 / 42 / 42 tiles = 172 accumulator registers), which stay there for the
 //   whole sweep.  Per step tau, two phases, one s_barrier each:
 //     A: serial part of step tau (as gen_backward_duo: join of the chain's sums, delta_tau = eps f'(u_tau) a_tau, carry,
@@ -41,22 +41,6 @@
 #ifndef SSN_FUSE_STAMP
 #define SSN_FUSE_STAMP 0        // diagnostic build: s_memtime ticks of workgroup 0 per segment (ssn_debug_fuse_stamps)
 #endif
-#ifndef SSN_FUSE_NPREG
-#define SSN_FUSE_NPREG 28       // 2N > 152: 16 x 32 parts of W^T (of a wave's 44-46: two fp16 parts of 22-23 units) kept in registers; the rest
-                                // lives in LDS and is read by the chain.  18 ... 36 build without spills; chain 1300 -> 880 cycles
-                                // from 18 to 32, 28 leaves the dL/d ext build its registers
-#endif
-#ifndef SSN_FUSE_NV
-#define SSN_FUSE_NV 0
-#endif
-#if SSN_FUSE_NV
-#define SSN_FUSE_ASM asm
-#else
-#define SSN_FUSE_ASM asm volatile
-#endif
-#ifndef SSN_FUSE_ABLATE
-#define SSN_FUSE_ABLATE 0       // timing only (wrong results): 1 = no rank-8 update, 2 = no chain
-#endif
 
 namespace ssn {
 
@@ -65,8 +49,13 @@ __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<N, I + 1>(f); }
 }
 
+// Diagnostic build: DuoStamp rows of the four waves of workgroup 0 (steps after the window): update + serial part, barrier, chain, barrier
+using FuseStamp = DuoStamp<SSN_FUSE_STAMP != 0>;
 #if SSN_FUSE_STAMP
 __device__ unsigned long long fuse_stamps[32];
+__device__ __forceinline__ unsigned long long* fuse_stamp_row(int w) { return fuse_stamps + 8 * w; }
+#else
+__device__ __forceinline__ unsigned long long* fuse_stamp_row(int) { return nullptr; }
 #endif
 
 typedef short sv4 __attribute__((ext_vector_type(4)));
@@ -97,7 +86,10 @@ template <int MK>
 struct FuseLds {
     using S = Duo16<MK>;
     static constexpr int NPMAX = 2 * ((S::UNITS + S::WM - 1) / S::WM);                          // parts of the largest share
-    static constexpr int NPREG = MK > 152 ? SSN_FUSE_NPREG : NPMAX;
+    // 2N > 152: 16 x 32 parts of W^T (of a wave's 44-46: two fp16 parts of 22-23 units) kept in registers; the rest lives in LDS
+    // and is read by the chain.  18 ... 36 build without spills; chain 1300 -> 880 cycles from 18 to 32, 28 leaves the
+    // dL/d ext build its registers
+    static constexpr int NPREG = MK > 152 ? 28 : NPMAX;
     static constexpr int NPL = NPMAX - NPREG;                                                  // parts per wave in LDS
     static constexpr int DIMG = 0, XIMG = 2 * S::BB, XSL = 4 * S::BB, SLOTS = XSL + (S::WM - 1) * S::XS, WMAX = SLOTS + 16,
                          WLDS = WMAX + 16, RSC = WLDS + S::WM * NPL * 1024, TOTAL = RSC + S::WM * 1024;    // RSC: 1 KB per wave for rescaling
@@ -278,7 +270,6 @@ __device__ __forceinline__ void fuse_backward_wave(const GenBwdArgs<float>& a, f
     int sexp = 0x7fffffff;                          // running minimum of bexp: the scale exponent of the accumulators
     unsigned lastref = 0u;
     auto chain = [&](unsigned img) {
-        if (SSN_FUSE_ABLATE & 2) return;
         ops.chain(b_rd + (unsigned)FL::DIMG + img, acc);
         if constexpr (WS::TAIL_SHARED) *(LdsF4)(size_t)(xs + (unsigned)(WV * S::XS)) = acc[NT - 1];
     };
@@ -309,17 +300,17 @@ __device__ __forceinline__ void fuse_backward_wave(const GenBwdArgs<float>& a, f
             ubop = ubn;
             if (c + 1 < NRT) ubn = fuse_read_tr(tr_b + (unsigned)FL::XIMG + uimg + (unsigned)((c + 1) * 512));
         }
-        if (i < NFR) SSN_FUSE_ASM("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(gwf[i < NFR ? i : 0][c < NRT ? c : 0]) : "v"(aopf[i < NFR ? i : 0]), "v"(ubop));
+        if (i < NFR) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(gwf[i < NFR ? i : 0][c < NRT ? c : 0]) : "v"(aopf[i < NFR ? i : 0]), "v"(ubop));
         else {
             const int r = i - NFR < NLR ? i - NFR : 0, cc = c - FT::C0 < CW ? (c - FT::C0 >= 0 ? c - FT::C0 : 0) : 0;
-            SSN_FUSE_ASM("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(gwl[r][cc]) : "v"(aopl[r]), "v"(ubop));
+            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(gwl[r][cc]) : "v"(aopl[r]), "v"(ubop));
         }
     };
     // site k of NSITE in the serial part issues MFMAs k NM / NSITE ... (k + 1) NM / NSITE - 1: one, sometimes two -- a second MFMA
     // right behind the first waits 12 cycles for the pipe, and every vector instruction behind it waits too
     constexpr int NSITE = 2 * NTF + 3 * NE + 4 * NTF + 2;
     auto update_slot = [&](auto UPD, auto KK) {
-        if constexpr (decltype(UPD)::value && !(SSN_FUSE_ABLATE & 1)) {
+        if constexpr (decltype(UPD)::value) {
             constexpr int k = decltype(KK)::value, j0 = k * NM / NSITE, j1 = (k + 1) * NM / NSITE;
             static_assert(k < NSITE && j1 - j0 <= 3, "MFMAs per site");
             // (fences: left alone, the scheduler gathers the MFMAs back into groups of three or four)
@@ -339,14 +330,14 @@ __device__ __forceinline__ void fuse_backward_wave(const GenBwdArgs<float>& a, f
                 sm.x += xp.x; sm.y += xp.y; sm.z += xp.z; sm.w += xp.w;
             }
         }
-        carry[2 * tf] = fmaf(duo_join<true>(sm.x, sm.z, hi, sm.y, sm.w), usc, carry[2 * tf]);
+        carry[2 * tf] = fmaf(duo_join(sm.x, sm.z, hi), usc, carry[2 * tf]);
         update_slot(UPD, std::integral_constant<int, 2 * tf>{});
-        carry[2 * tf + 1] = fmaf(duo_join<false>(sm.y, sm.w, hi), usc, carry[2 * tf + 1]);
+        carry[2 * tf + 1] = fmaf(duo_join(sm.y, sm.w, hi), usc, carry[2 * tf + 1]);
         update_slot(UPD, std::integral_constant<int, 2 * tf + 1>{});
     };
     auto serial = [&](auto WIN, auto UPD, int tau) {
         constexpr bool win_on = decltype(WIN)::value;
-        if constexpr (decltype(UPD)::value && !(SSN_FUSE_ABLATE & 1)) update_begin((unsigned)(((tau + 1) & 1) * S::BB));
+        if constexpr (decltype(UPD)::value) update_begin((unsigned)(((tau + 1) & 1) * S::BB));
         float (&dfc)[NE] = dfA;
         float (&xm)[NE] = xA;                            // x_{tau-1}: the operand of this step's update, and of the window terms
         const unsigned img = (unsigned)((tau & 1) * S::BB);
@@ -424,13 +415,10 @@ __device__ __forceinline__ void fuse_backward_wave(const GenBwdArgs<float>& a, f
     constexpr std::integral_constant<bool, false> W0{};
     constexpr std::integral_constant<bool, true> W1{};
     __syncthreads();                                                          // (B)
-#if SSN_FUSE_STAMP
-    unsigned long long st_a = 0, st_b1 = 0, st_c = 0, st_b2 = 0; int st_n = 0;
-#endif
+    FuseStamp ts;
     auto step = [&](auto WIN, auto UPD, int tau) {
-#if SSN_FUSE_STAMP
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-#endif
+        constexpr bool timed = !decltype(WIN)::value;
+        ts.start();
         // phase A: the update of step tau + 1 (images of the other parity) and the serial part of step tau, one instruction stream
         const int snew = serial(WIN, UPD, tau);
         if (snew != sexp) {                                                    // |delta| reached a new binade: the sums follow
@@ -458,22 +446,14 @@ __device__ __forceinline__ void fuse_backward_wave(const GenBwdArgs<float>& a, f
             }
             sexp = snew;
         }
-#if SSN_FUSE_STAMP
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+        ts.lap(0, timed);
         duo_phase_barrier();
-        const unsigned long long t2 = __builtin_amdgcn_s_memtime();
+        ts.lap(1, timed);
         chain((unsigned)((tau & 1) * S::BB));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long t3 = __builtin_amdgcn_s_memtime();
+        ts.lap(2, timed);
         duo_phase_barrier();
-        const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-        if (!decltype(WIN)::value) { st_a += t1 - t0; st_b1 += t2 - t1; st_c += t3 - t2; st_b2 += t4 - t3; ++st_n; }
-#else
-        duo_phase_barrier();
-        chain((unsigned)((tau & 1) * S::BB));
-        duo_phase_barrier();
-#endif
+        ts.lap(3, timed);
+        ts.tick(timed);
     };
     const int tw = a.skip + 1 > 1 ? a.skip + 1 : 1;     // window steps first (time runs backwards): tau = T ... tw
     step(W1, W0, T_);                                   // (step T lies in the window: skip < T; no update before it)
@@ -481,12 +461,7 @@ __device__ __forceinline__ void fuse_backward_wave(const GenBwdArgs<float>& a, f
     for (; tau >= tw; --tau) step(W1, W1, tau);
     for (; tau >= 1; --tau) step(W0, W1, tau);
     // (the update of step 1 pairs delta_1 with x_0 = 0: nothing to add)
-#if SSN_FUSE_STAMP
-    if (blockIdx.x == 0 && lane == 0) {
-        unsigned long long* o = fuse_stamps + 8 * WV;
-        o[0] = st_a; o[1] = st_b1; o[2] = st_c; o[3] = st_b2; o[4] = (unsigned long long)st_n;
-    }
-#endif
+    ts.flush(fuse_stamp_row(WV));
     // ---- dL/dW of this draw: acc 2^-(sexp + xexp); accumulator lane (lg, li) holds rows 4 lg .. 4 lg + 3 of column li
     {
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");

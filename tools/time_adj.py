@@ -18,13 +18,14 @@ e0.record()
 for _ in range(3): bwd()
 e1.record(); torch.cuda.synchronize()
 print('adjoint (in place, repeated) %.3f ms' % (e0.elapsed_time(e1) / 3))
-if hasattr(genops.libssnode, 'ssn_debug_duo_stamps'):
+if hasattr(genops.libssnode, 'ssn_debug_duo_stamps'):       # diagnostic build (-DSSN_DUO_STAMP=1): the steps after the window
     import ctypes
-    buf = (ctypes.c_ulonglong * 16)()
+    buf = (ctypes.c_ulonglong * 64)()
     genops.libssnode.ssn_debug_duo_stamps(buf)
-    n = max(int(buf[8]), 1)
-    for name, o in (('wave 0', 0), ('wave 3', 4)):
-        print('  draw 0 %s: chain %.0f  barrier %.0f  serial %.0f  barrier %.0f cycles per step' % ((name,) + tuple(buf[o + i] / n for i in range(4))))
+    for w in (0, 3):                                        # draw 0: the lightest and the four-tile wave
+        n = max(int(buf[8 * w + 7]), 1)
+        print('  draw 0 wave %d: serial %.0f  barrier %.0f  chain %.0f  barrier %.0f cycles per step (%d steps)'
+              % ((w,) + tuple(buf[8 * w + i] / n for i in range(4)) + (n,)))
 xmax = genops.rate_bound(gp)
 out = genops.gen_forward(W, ext, gp, save=True)      # (the loop above ran the in-place sweep over its own output)
 traj, df = out['traj'], out['df']
@@ -47,5 +48,5 @@ if hasattr(genops.libssnode, 'ssn_debug_fuse_stamps'):
     buf = (ctypes.c_ulonglong * 32)()
     genops.libssnode.ssn_debug_fuse_stamps(buf)
     for w in range(4):
-        n = max(int(buf[8 * w + 4]), 1)
+        n = max(int(buf[8 * w + 7]), 1)
         print('  wave %d: update+serial %.0f  barrier %.0f  chain %.0f  barrier %.0f cycles per step' % ((w,) + tuple(buf[8 * w + i] / n for i in range(4))))

@@ -37,26 +37,22 @@ def main():
         ta = genops.gen_forward(W, ext, gp)['time_avg']
         if ref is None:
             ref = ta
-        if k == 8 and '--fine' in args and hasattr(genops.libssnode, 'ssn_debug_duo_stamps_fine'):   # -DSSN_DUO_STAMP=2
+        if k == 8 and hasattr(genops.libssnode, 'ssn_debug_duo_stamps'):      # diagnostic build (-DSSN_DUO_STAMP=1)
             import ctypes
             buf = (ctypes.c_ulonglong * 64)()
             torch.cuda.synchronize()
-            genops.libssnode.ssn_debug_duo_stamps_fine(buf)
+            genops.libssnode.ssn_debug_duo_stamps(buf)
+            # per wave of workgroup 0: chain, early tile, barrier, rest of the serial part, publication, barrier; total; steps
             for w in range(8):
                 n = max(int(buf[8 * w + 7]), 1)
                 seg = [buf[8 * w + i] / n for i in range(6)]
-                print('  draw %d wave %d: chain %5.0f early %5.0f barrier %5.0f | serial %5.0f publish %5.0f barrier %5.0f | step %6.0f ticks (%d steps)'
-                      % (w // 4, w % 4, *seg, buf[8 * w + 6] / n, n))
+                if '--fine' in args:
+                    print('  draw %d wave %d: chain %5.0f early %5.0f barrier %5.0f | serial %5.0f publish %5.0f barrier %5.0f | sum %6.0f step %6.0f ticks (%d steps)'
+                          % (w // 4, w % 4, *seg, sum(seg), buf[8 * w + 6] / n, n))
+                elif w % 4 in (0, 3):
+                    print('  draw %d wave %d: chain %.0f  barrier %.0f  serial %.0f  barrier %.0f cycles per step (s_memtime ticks)'
+                          % (w // 4, w % 4, seg[0] + seg[1], seg[2], seg[3] + seg[4], seg[5]))
             print('  (kernel %.3f ms for %d steps: compare with the ticks per step to calibrate the counter)' % (ms, T))
-        elif k == 8 and hasattr(genops.libssnode, 'ssn_debug_duo_stamps'):      # diagnostic build (-DSSN_DUO_STAMP=1)
-            import ctypes
-            buf = (ctypes.c_ulonglong * 16)()
-            torch.cuda.synchronize()
-            genops.libssnode.ssn_debug_duo_stamps(buf)
-            n = max(int(buf[8]), 1)
-            for d in (0, 1):
-                print('  draw %d wave 0: chain %.0f  barrier %.0f  serial %.0f  barrier %.0f cycles per step (s_memtime ticks); wave 3: chain %.0f serial %.0f barriers %.0f'
-                      % ((d,) + tuple(buf[4 * d + i] / n for i in range(4)) + tuple(buf[9 + 3 * d + i] / n for i in range(3))))
         print('kernel %d: forward%s %.3f ms   max |time_avg - first kernel| %.3e (max %.3e)' % (
             k, ' + stores' if save else '', ms, float((ta - ref).abs().max()), float(ref.abs().max())), flush=True)
 
