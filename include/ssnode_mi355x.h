@@ -648,6 +648,9 @@ int ssn_build_w_philox_f64(unsigned long long seed, unsigned long long offset, c
  * ssn_build_w_philox_f32 in that order: the same numbers, without the host between them): zin / amp = the heterogeneous-input
  * signs and 1 + v zin from stream elements off_zin.. (v device [M]; v NULL: none, plain stimulus), ext[B][NB][M] the (amplified)
  * stimulus of bandwidths bw and contrasts con (device [B][NB]), W[B][M][M] from stream elements off_z.. (z device or NULL).
+ * amp, and the gain inside ext, are 1 + v zin as TWO fp32 operations (the product is rounded, then the sum: the bits of
+ * ssn_stimulus_hetero_f32 and of the torch expression `1 + vs[None, :] * zin`), so ext equals ssn_stimulus_amp_f32 of the
+ * returned amp and ssn_stimulus_hetero_f32 of the returned zin bit for bit (tests/test_device_inputs_gpu.py).
  */
 typedef struct ssn_gen_inputs {
     unsigned long long seed, off_z, off_zin;
@@ -662,7 +665,7 @@ typedef struct ssn_gen_inputs {
 int ssn_gen_inputs_philox_f32(const ssn_gen_inputs *a, void *stream);
 /* The heterogeneous-input SSN's noise from the same stream, in one launch (networks/ssn.py:679-720): zin[i] = +1 / -1
  * (u < 0.5; bernoulli != 0) or 2 u - 1, and amp[i] = 1 + v[i % M] * zin[i] (v: device [M], the input variability per
- * neuron); zin, amp: device [n]. */
+ * neuron; two operations of the type: the product is rounded before the sum); zin, amp: device [n]. */
 int ssn_philox_amp_f32(unsigned long long seed, unsigned long long offset, const float *v, float *zin, float *amp,
                        unsigned long long n, int M, int bernoulli, void *stream);
 int ssn_philox_amp_f64(unsigned long long seed, unsigned long long offset, const double *v, double *zin, double *amp,

@@ -360,9 +360,21 @@ hipError_t launch_build_w_philox(unsigned long long seed, unsigned long long off
 template hipError_t launch_build_w_philox<float>(unsigned long long, unsigned long long, const float*, float*, float*, int, int, hipStream_t);
 template hipError_t launch_build_w_philox<double>(unsigned long long, unsigned long long, const double*, double*, double*, int, int, hipStream_t);
 
+// 1 + v z of the heterogeneous-input models (networks/ssn.py:679-686) as the TWO roundings of the torch expression
+// `1 + vs[None, :] * zin`: the product is rounded before the addition, as in stimulus_hetero_kernel (left to itself the
+// compiler contracts it into one fma, which differs by an ulp for `dist_in = 'uniform'`).  The one place every kernel below
+// forms the number, so that the stored `amp`, the stimulus of the one-launch inputs and the materialised path hold the same bits.
+template <typename T>
+__device__ __forceinline__ T one_plus_vz(T v, T z) {
+    T t = v * z;
+    asm volatile("" : "+v"(t));
+    return (T)1 + t;
+}
+
 // The heterogeneous-input SSN's per-neuron input variability in one launch (networks/ssn.py:679-720): element i of the
 // draw gets z = +1 / -1 (u < 0.5, `dist_in = 'bernoulli'`) or 2 u - 1 ('uniform') from the same stream element u as
-// philox_uniform_kernel would give it, and amp = 1 + v[i % M] * z (v = the population's input variability per neuron).
+// philox_uniform_kernel would give it, and amp = 1 + v[i % M] * z (v = the population's input variability per neuron), the
+// product rounded before the sum (one_plus_vz).
 template <typename T>
 __global__ void __launch_bounds__(256) philox_amp_kernel(unsigned long long seed, unsigned long long offset, const T* __restrict__ v,
                                                          T* __restrict__ zin, T* __restrict__ amp, unsigned long long n, int M,
@@ -379,7 +391,7 @@ __global__ void __launch_bounds__(256) philox_amp_kernel(unsigned long long seed
                 const T u = (T)((float)(w[j] >> 8) * (1.0f / 16777216.0f));
                 const T z = bernoulli ? (u < (T)0.5 ? (T)1 : (T)-1) : u * (T)2 - (T)1;
                 zin[i] = z;
-                amp[i] = (T)1 + v[i % (unsigned long long)M] * z;
+                amp[i] = one_plus_vz<T>(v[i % (unsigned long long)M], z);
             }
         }
     }
@@ -400,7 +412,9 @@ template hipError_t launch_philox_amp<double>(unsigned long long, unsigned long 
 // cut in three ranges of workgroups that run the bodies of philox_amp_kernel (heterogeneous-input noise z and 1 + v z),
 // stimulus_kernel and build_w_philox_kernel.  The stimulus needs 1 + v z of its own (draw, neuron): it forms the number
 // again from the same stream element (ten Philox rounds per element, on a kernel of a few microseconds) instead of waiting
-// for the first range -- same expression, same bits as the stored `amp`.
+// for the first range -- through one_plus_vz, the helper the amp range and philox_amp_kernel use: v z rounded, then 1 + that,
+// the two roundings of stimulus_hetero_kernel and of the torch expression, so the same bits as the stored `amp` and as a forward
+// that materialises the noise first (tests/test_device_inputs_gpu.py).
 __global__ void __launch_bounds__(256) gen_inputs_kernel(GenInputsArgs a) {
     const long blk = blockIdx.x;
     const int M = 2 * a.N;
@@ -423,7 +437,7 @@ __global__ void __launch_bounds__(256) gen_inputs_kernel(GenInputsArgs a) {
             philox4x32_10((unsigned)(g >> 2), (unsigned)(g >> 34), 0u, 0u, (unsigned)a.seed, (unsigned)(a.seed >> 32), w);
             const float u = (float)(w[g & 3ull] >> 8) * (1.0f / 16777216.0f);
             const float z = a.bernoulli ? (u < 0.5f ? 1.f : -1.f) : u * 2.f - 1.f;
-            const float gain = 1.f + a.v[m] * z;
+            const float gain = one_plus_vz<float>(a.v[m], z);
             a.ext[e] = gain * a.con[bs] * s1 * s2;
         }
     } else {
@@ -440,7 +454,7 @@ __global__ void __launch_bounds__(256) gen_inputs_kernel(GenInputsArgs a) {
                     const float u = (float)(w[j] >> 8) * (1.0f / 16777216.0f);
                     const float z = a.bernoulli ? (u < 0.5f ? 1.f : -1.f) : u * 2.f - 1.f;
                     a.zin[i] = z;
-                    a.amp[i] = 1.f + a.v[i % (unsigned long long)M] * z;
+                    a.amp[i] = one_plus_vz<float>(a.v[i % (unsigned long long)M], z);
                 }
             }
         }
