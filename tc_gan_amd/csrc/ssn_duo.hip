@@ -294,7 +294,7 @@ __global__ void __launch_bounds__(512, 2) gen_forward_duo_kernel(GenFwdArgs<floa
 // ---------------------------------------------------------------------------------------------------------------
 // The fixed-point solver (ext/ssnode.c:64-187 semantics: Euler form r + (-r + f(u)) dt / tau, convergence and rate-bound
 // tests per step, every (draw, stimulus) pair stops at its own step) in the two-draw form, lock-step phases.
-// Stop protocol as solve_mfma_kernel / solve_wide_kernel: per draw three rotating flag words per stimulus in LDS (low
+// Stop protocol as solve_mfma_kernel / solve_split_kernel: per draw three rotating flag words per stimulus in LDS (low
 // half: some row not converged; high half: some row at the rate bound), written in the serial phase of step t, read by
 // all four waves of the draw at the start of its next chain phase (one barrier later), cleared one step ahead.  A draw
 // whose 8 stimuli are all frozen (or that reached max_iter) idles through the phases until the other draw of the
@@ -700,7 +700,7 @@ __device__ __forceinline__ void duo_backward_wave(const GenBwdArgs<float>& a, in
         }
     }
     {
-        const unsigned wm0 = duo_wave_max_bits(m0);
+        const unsigned wm0 = wave_max_bits(m0);
         if (lane == 0) __hip_atomic_fetch_max((__attribute__((address_space(3))) unsigned*)(dlds + SYNCB) + (T_ + 1 + 3) % 3, wm0,
                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
@@ -818,7 +818,7 @@ __device__ __forceinline__ void duo_backward_wave(const GenBwdArgs<float>& a, in
         }
         bused = bexp;
         // one LDS atomic per wave (64 lanes on one address serialise: 16.6 -> 9.x ms): wave maximum first, six DPP steps
-        const unsigned wm = duo_wave_max_bits(live ? dm : 0.f);
+        const unsigned wm = wave_max_bits(live ? dm : 0.f);
         if (lane == 0) __hip_atomic_fetch_max((__attribute__((address_space(3))) unsigned*)(dlds + SYNCB) + (tau + 3) % 3, wm,
                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };

@@ -119,24 +119,6 @@ __device__ __forceinline__ float duo_join(float lo, float hi, int is_hi) {
     return k + dpp_ror8(o);
 }
 
-// max over the wave of a non-negative float (bit patterns order like the values), the same value in every lane's SGPR copy
-__device__ __forceinline__ unsigned duo_wave_max_bits(float x) {
-    unsigned v = __builtin_bit_cast(unsigned, x);
-#define DUO_DPP_MAX(CTRL, ROWMASK)                                                                                   \
-    {                                                                                                                     \
-        const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWMASK, 0xf, false);                   \
-        v = o > v ? o : v;                                                                                                \
-    }
-    DUO_DPP_MAX(0xB1, 0xf)     // quad_perm [1,0,3,2]
-    DUO_DPP_MAX(0x4E, 0xf)     // quad_perm [2,3,0,1]
-    DUO_DPP_MAX(0x141, 0xf)    // row_half_mirror
-    DUO_DPP_MAX(0x140, 0xf)    // row_mirror: every lane = row max
-    DUO_DPP_MAX(0x142, 0xa)    // row_bcast15 -> rows 1, 3
-    DUO_DPP_MAX(0x143, 0xc)    // row_bcast31 -> rows 2, 3
-#undef DUO_DPP_MAX
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-
 // x 2^rshift = h + m by round to nearest, two values per call; returns the packed fp16 pairs
 // (plain fp32 instructions on purpose: beside a partner wave's MFMA stream a packed v_pk_*_f32 costs several times its
 // two scalar halves -- MI355X_MICROARCH.md, cycle constants; this file is built with -fno-slp-vectorize for the same reason)

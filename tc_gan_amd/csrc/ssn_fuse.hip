@@ -248,7 +248,7 @@ __device__ __forceinline__ void fuse_backward_wave(const GenBwdArgs<float>& a, f
         }
     }
     {
-        const unsigned wm0 = duo_wave_max_bits(m0);
+        const unsigned wm0 = wave_max_bits(m0);
         if (lane == 0) __hip_atomic_fetch_max((__attribute__((address_space(3))) unsigned*)(lds + FL::SLOTS) + (T_ + 1 + 3) % 3, wm0,
                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
@@ -407,7 +407,7 @@ __device__ __forceinline__ void fuse_backward_wave(const GenBwdArgs<float>& a, f
         }
         bused = bexp;
         update_slot(UPD, std::integral_constant<int, NSITE - 1>{});
-        const unsigned wm = duo_wave_max_bits(live ? dm : 0.f);
+        const unsigned wm = wave_max_bits(live ? dm : 0.f);
         if (lane == 0) __hip_atomic_fetch_max((__attribute__((address_space(3))) unsigned*)(lds + FL::SLOTS) + (tau + 3) % 3, wm,
                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         return snew;
@@ -489,7 +489,7 @@ __device__ __forceinline__ void fuse_backward_wave(const GenBwdArgs<float>& a, f
             for (int c = 0; c < CW; ++c) put(gwl[r][c], FT::NF + r, FT::C0 + c);
     }
     if (a.dmax) {                                   // max |delta| of the draw, NaN for a poisoned one (as gen_backward_duo_kernel)
-        const unsigned wm = duo_wave_max_bits(dmx);
+        const unsigned wm = wave_max_bits(dmx);
         if (lane == 0) atomicMax(a.dmax + b, wm);
         if (poisoned) atomicMax(a.dmax + b, 0x7fc00000u);
     }

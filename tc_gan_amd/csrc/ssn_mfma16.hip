@@ -28,22 +28,21 @@
 // Only the saturating I/O function (asym_tanh, the default of every driver) bounds the rates, hence the choice of the
 // r scale; the other two run the fp32 MFMA kernel.
 //
-// Three kernels share the matrix-wave code: gen_forward_split_kernel (this comment), gen_backward_split_kernel (adjoint
-// sweep: W^T, delta with a scale that follows max |delta| step by step; any I/O function) and solve_split_kernel (the
-// fixed-point solver with its stop protocol; scale from max(rate bound, max |r0|)).  Forward and solver also exist in a
-// WIDE form (gen_forward_wide_kernel, solve_wide_kernel: all 8 stimuli of a draw in one chain per step, the state as two
-// fp16 parts), which is what two-group launches run by default.
+// Three kernels share the pieces below (LDS layout, W prologue, chain, serial lane's addresses, state store):
+// gen_forward_split_kernel (this comment), gen_backward_split_kernel (adjoint sweep: W^T, delta with a scale that follows
+// max |delta| step by step; any I/O function) and solve_split_kernel (the fixed-point solver with its stop protocol; scale
+// from max(rate bound, max |r0|)).  Forward and solver take their FORM as a template parameter: the alternating one above,
+// or a WIDE one (all 8 stimuli of a draw in one chain per step, the state as two fp16 parts, or as three for the forward),
+// which is what two-group launches run by default.  What a form changes is an `if constexpr` in the kernel's own text.  The
+// four matrix-wave functions still repeat the W prologue and the chain, and each kernel its serial lane's addresses: these
+// kernels sit at 256 registers, and with those pieces behind a shared function or struct the compiler orders and allocates
+// them differently.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <type_traits>
 #include "ssn_device.h"
 #include "ssn_host.h"
 #include "ssn_mfma_io.h"
-
-#ifndef SSN_SPLIT_ABLATE
-#define SSN_SPLIT_ABLATE 0      // diagnostic builds: 1 = no serial part, 2 = no chains, 4 = sums not stored, 8 = one B tile
-                                // read seven times (wrong results, timing only)
-#endif
 
 #ifndef SSN_SPLIT_STAMP
 #define SSN_SPLIT_STAMP 0       // diagnostic build: cycle stamps of the adjoint's serial wave (ssn_debug_split_stamps)
@@ -73,21 +72,46 @@ __device__ __forceinline__ float split_u_scale(unsigned maxbits, int rshift) {
 }
 
 typedef float fv2 __attribute__((ext_vector_type(2)));
-// x * sc -> three fp16 parts by truncation (the masked values have 11 significant bits: their conversion is exact),
-// written to the lane's k slots of the B operand (part columns 64 bytes apart); packed fp32 arithmetic throughout
-__device__ __forceinline__ void split3_store(const float (&x)[4], fv2 sc01, fv2 sc23, unsigned bw) {
+// x * sc -> PARTS fp16 parts, written to the lane's k slots of the B operand: the high part at bw, the middle one at
+// bw + mid, the low one (PARTS = 3) at bw + low; packed fp32 arithmetic throughout.
+// Three parts: by truncation (the masked values have 11 significant bits: their conversion is exact).  EAGER stores each
+// part as soon as it exists -- the same values; the statement order alone decides how the compiler schedules the ten
+// instructions, and the three-part wide forward keeps the order it was built with.
+template <int PARTS, bool EAGER = false>
+__device__ __forceinline__ void split_store(const float (&x)[4], fv2 sc01, fv2 sc23, unsigned bw, unsigned mid, unsigned low) {
     using LdsU2 = __attribute__((address_space(3))) uv2*;
     const fv2 s01 = (fv2){x[0], x[1]} * sc01, s23 = (fv2){x[2], x[3]} * sc23;
-    auto top = [](fv2 v) { return __builtin_bit_cast(fv2, __builtin_bit_cast(uv2, v) & (uv2){0xffffe000u, 0xffffe000u}); };
-    auto pk = [](fv2 v) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v.x, v.y)); };
-    const fv2 h01 = top(s01), h23 = top(s23);
-    const fv2 d01 = s01 - h01, d23 = s23 - h23;
-    const fv2 m01 = top(d01), m23 = top(d23);
-    const fv2 l01 = d01 - m01, l23 = d23 - m23;
-    *(LdsU2)(size_t)bw = (uv2){pk(h01), pk(h23)};
-    *(LdsU2)(size_t)(bw + 64u) = (uv2){pk(m01), pk(m23)};
-    *(LdsU2)(size_t)(bw + 128u) = (uv2){pk(l01), pk(l23)};
+    if constexpr (PARTS == 3 && !EAGER) {
+        auto top = [](fv2 v) { return __builtin_bit_cast(fv2, __builtin_bit_cast(uv2, v) & (uv2){0xffffe000u, 0xffffe000u}); };
+        auto pk = [](fv2 v) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v.x, v.y)); };
+        const fv2 h01 = top(s01), h23 = top(s23);
+        const fv2 d01 = s01 - h01, d23 = s23 - h23;
+        const fv2 m01 = top(d01), m23 = top(d23);
+        const fv2 l01 = d01 - m01, l23 = d23 - m23;
+        *(LdsU2)(size_t)bw = (uv2){pk(h01), pk(h23)};
+        *(LdsU2)(size_t)(bw + mid) = (uv2){pk(m01), pk(m23)};
+        *(LdsU2)(size_t)(bw + low) = (uv2){pk(l01), pk(l23)};
+    } else if constexpr (PARTS == 3) {
+        auto top = [](fv2 v) { return __builtin_bit_cast(fv2, __builtin_bit_cast(uv2, v) & (uv2){0xffffe000u, 0xffffe000u}); };
+        auto pk = [](fv2 v) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v.x, v.y)); };
+        const fv2 h01 = top(s01), h23 = top(s23);
+        const fv2 d01 = s01 - h01, d23 = s23 - h23;
+        *(LdsU2)(size_t)bw = (uv2){pk(h01), pk(h23)};
+        const fv2 m01 = top(d01), m23 = top(d23);
+        *(LdsU2)(size_t)(bw + mid) = (uv2){pk(m01), pk(m23)};
+        *(LdsU2)(size_t)(bw + low) = (uv2){pk(d01 - m01), pk(d23 - m23)};
+    } else {
+        // two parts: both by ROUND TO NEAREST (h = rn(s), m = rn(s - h): |s - h - m| <= 2^-23 |s|, no bias; round 2
+        // truncated both, 2^-21 and biased toward zero)
+        typedef _Float16 hv2_ __attribute__((ext_vector_type(2)));
+        const hv2_ hn01 = __builtin_convertvector(s01, hv2_), hn23 = __builtin_convertvector(s23, hv2_);
+        const fv2 r01 = s01 - __builtin_convertvector(hn01, fv2), r23 = s23 - __builtin_convertvector(hn23, fv2);
+        *(LdsU2)(size_t)bw = (uv2){__builtin_bit_cast(unsigned, hn01), __builtin_bit_cast(unsigned, hn23)};
+        *(LdsU2)(size_t)(bw + mid) = (uv2){__builtin_bit_cast(unsigned, __builtin_convertvector(r01, hv2_)),
+                                           __builtin_bit_cast(unsigned, __builtin_convertvector(r23, hv2_))};
+    }
 }
+
 
 template <int MK>
 struct Split16 {
@@ -110,6 +134,14 @@ struct Split16 {
     static_assert(NRT * 16 <= 256, "serial lanes: 4 waves x 64 lanes x 4 rows");
     static_assert(start(1) >= NKT, "a row tile is shared by at most two waves");
 };
+
+
+// The forms of a two-group workgroup, numbered as GenFwdArgs::split_form.  The alternating form keeps one B operand and one
+// buffer of sums per group: 16 columns = 4 stimuli x [r_h, r_m, r_l, (unused)].  The wide forms use the first halves of
+// that layout for all 8 stimuli: column s = r_h, column 8 + s = r_m of stimulus s, and for three parts a second operand at
+// bbuf + BB whose columns s hold r_l.
+enum SplitForm { SPLIT_ALTERNATING = 0, SPLIT_WIDE2 = 2, SPLIT_WIDE3 = 3 };
+
 
 // One matrix wave: its slice of W (TRANSPOSED: of W^T, for the adjoint sweep) in registers for the whole launch, one
 // chain per phase p in [p0, p1) for group (p - p0) & 1, a barrier at the end of each of the `nphase` phases.
@@ -173,13 +205,13 @@ __device__ __forceinline__ void split_matrix_wave(const float* __restrict__ Wd, 
     const unsigned boff = (unsigned)(lg * S::ROW + li * 16), boff_b = (unsigned)(lg * S::BROW + li * 16);
     __syncthreads();                                                          // (B)
     for (int p = 0; p < nphase; ++p) {
-        if (p >= p0 && p < p1 && ((p - p0) & 1) < gpw && !(SSN_SPLIT_ABLATE & 2)) {
+        if (p >= p0 && p < p1 && ((p - p0) & 1) < gpw) {
             const int g = (p - p0) & 1;
             const unsigned bb = (unsigned)(size_t)(LdsH8)(bbuf + g * S::BB) + boff_b;
             hv8 bt[S::NKT];
 #pragma unroll
             for (int kt = 0; kt < S::NKT; ++kt)
-                bt[kt] = *(LdsH8)(size_t)(bb + (unsigned)(((SSN_SPLIT_ABLATE & 8) ? 0 : kt) * 4 * S::BROW));
+                bt[kt] = *(LdsH8)(size_t)(bb + (unsigned)(kt * 4 * S::BROW));
             mf4 acc[NT];
 #pragma unroll
             for (int t = 0; t < NT; ++t) acc[t] = (mf4){0.f, 0.f, 0.f, 0.f};
@@ -199,172 +231,12 @@ __device__ __forceinline__ void split_matrix_wave(const float* __restrict__ Wd, 
             for (int t = 0; t < NT; ++t) {
                 char* dst = (t == 0 && HEAD_SHARED) ? xbuf + g * S::XB + (WV - 1) * 4 * S::ROW
                                                     : abuf + g * S::AB + (RT0 + t) * 4 * S::ROW;
-                if (!(SSN_SPLIT_ABLATE & 4) || acc[t].x == 12345.f) *(LdsF4)(size_t)((unsigned)(size_t)(LdsF4)dst + boff) = acc[t];
+                *(LdsF4)(size_t)((unsigned)(size_t)(LdsF4)dst + boff) = acc[t];
             }
         }
         __syncthreads();
     }
 }
-
-template <int MK, bool SAVE>
-__global__ void __launch_bounds__(512, 2) gen_forward_split_kernel(GenFwdArgs<float> a, int rshift) {
-    using S = Split16<MK>;
-    __shared__ __align__(16) char lds[S::LDS];
-    char* const bbuf = lds;
-    char* const abuf = lds + 2 * S::BB;
-    char* const xbuf = abuf + 2 * S::AB;
-    char* const zrow = xbuf + 2 * S::XB;
-    unsigned* const wmax = reinterpret_cast<unsigned*>(zrow + S::ROW);
-    const int M = a.M, N = a.M / 2, T_ = a.seqlen;
-    const int gpw = a.mfma_groups;                // stimulus groups of 4 in this workgroup (2; 1: group 1 idle)
-    const int ngroups = (a.NB + 4 * gpw - 1) / (4 * gpw);
-    const int b = blockIdx.x / ngroups;
-    const int s0 = (blockIdx.x % ngroups) * 4 * gpw;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = threadIdx.x; c < S::LDS / 4; c += blockDim.x) reinterpret_cast<unsigned*>(lds)[c] = 0u;
-    __syncthreads();                              // (zeroed before any wave records max |W|)
-
-    if (wave < S::WM) {
-        const float* Wd = a.W + (size_t)b * M * M;
-        switch (wave) {       // phases 0 .. 2T: chains in 0 .. 2T - 1
-            case 0: split_matrix_wave<MK, 0, false>(Wd, M, lane, 0, 2 * T_, 2 * T_ + 1, gpw, bbuf, abuf, xbuf, wmax); break;
-            case 1: split_matrix_wave<MK, 1, false>(Wd, M, lane, 0, 2 * T_, 2 * T_ + 1, gpw, bbuf, abuf, xbuf, wmax); break;
-            case 2: split_matrix_wave<MK, 2, false>(Wd, M, lane, 0, 2 * T_, 2 * T_ + 1, gpw, bbuf, abuf, xbuf, wmax); break;
-            default: split_matrix_wave<MK, 3, false>(Wd, M, lane, 0, 2 * T_, 2 * T_ + 1, gpw, bbuf, abuf, xbuf, wmax); break;
-        }
-        return;
-    }
-
-    // ================================ serial wave ================================
-    const int sw = wave - S::WM;
-    const int blk = lane >> 2, j = lane & 3;
-    const int er = 64 * sw + 4 * blk;             // first of the 4 rows this lane finishes
-    const IoSelect io(a.io);
-    float eps[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) eps[v] = (er + v < N) ? a.eps_E : a.eps_I;
-    bool live[2];
-    float rc[2][4], ex[2][4], ta[2][4], dp[2][4], rpn[2][4];
-    int toff[2];                                  // byte offset of (my stimulus, step 0, row er) within this draw's block
-    const size_t blk_elems = (size_t)a.NB * T_ * M;
-    __amdgpu_buffer_rsrc_t rs_traj, rs_df;
-    if constexpr (SAVE) {
-        rs_traj = __builtin_amdgcn_make_buffer_rsrc(a.traj + (size_t)b * blk_elems, 0, (int)(blk_elems * 4), 0x00020000);
-        rs_df = __builtin_amdgcn_make_buffer_rsrc(a.df + (size_t)b * blk_elems, 0, (int)(blk_elems * 4), 0x00020000);
-    }
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        const int s = s0 + 4 * g + j;
-        live[g] = s < a.NB && g < gpw;
-        toff[g] = (live[g] && er < M) ? (int)(((size_t)s * T_ * M + er) * 4) : -1;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            rc[g][v] = ta[g][v] = dp[g][v] = rpn[g][v] = 0.f;
-            ex[g][v] = (live[g] && er + v < M) ? a.ext[((size_t)b * a.NB + s) * M + er + v] : 0.f;
-        }
-    }
-    // LDS addresses of this lane (bytes, relative to a group's buffer)
-    const int rt = er / 16 < S::NRT ? er / 16 : S::NRT - 1, rq = (er / 4) & 3;
-    const unsigned a_off = (unsigned)((rt * 4 + rq) * S::ROW + j * 16);       // column 4 part + j: + 64 part
-    int x_slot = -1;                                                          // extra slot of my row tile, if shared
-#pragma unroll
-    for (int w = 1; w < S::WM; ++w)
-        if (S::start(w) % S::NKT != 0 && S::start(w) / S::NKT == rt) x_slot = w - 1;
-    const unsigned x_off = (unsigned)((x_slot * 4 + rq) * S::ROW + j * 16);
-    const bool b_live = er < 32 * S::NKT;
-    const unsigned b_off = (unsigned)(((er / 32) * 4 + ((er & 31) >> 3)) * S::BROW + j * 16 + ((er & 7) >> 2) * 8);
-    const float rs = __builtin_bit_cast(float, (unsigned)(127 + rshift) << 23);          // 2^rshift
-    const fv2 rs01 = {er < M ? rs : 0.f, er + 1 < M ? rs : 0.f}, rs23 = {er + 2 < M ? rs : 0.f, er + 3 < M ? rs : 0.f};
-    using LdsF4 = const __attribute__((address_space(3))) mf4*;
-    using LdsU2 = __attribute__((address_space(3))) uv2*;
-
-    __syncthreads();                                                          // (A) max |W| of the draw is known
-    const float usc = split_u_scale(*wmax, rshift);                           // 2^-(a + rshift)
-
-    auto serial = [&](auto G, auto WIN, int it) {
-        constexpr int g = decltype(G)::value;
-        constexpr bool win_on = decltype(WIN)::value;
-        const unsigned ab = (unsigned)(size_t)(LdsF4)(abuf + g * S::AB) + a_off;
-        const unsigned xb = x_slot < 0 ? (unsigned)(size_t)(LdsF4)zrow + (unsigned)(j * 16)
-                                       : (unsigned)(size_t)(LdsF4)(xbuf + g * S::XB) + x_off;
-        const mf4 p0 = *(LdsF4)(size_t)ab, p1 = *(LdsF4)(size_t)(ab + 64u), p2 = *(LdsF4)(size_t)(ab + 128u);
-        const mf4 q0 = *(LdsF4)(size_t)xb, q1 = *(LdsF4)(size_t)(xb + 64u), q2 = *(LdsF4)(size_t)(xb + 128u);
-        const mf4 acc = ((p0 + q0) + (p1 + q1)) + (p2 + q2);
-        const float accs[4] = {acc.x, acc.y, acc.z, acc.w};
-        const float win2 = (it > a.skip) ? 1.f : 0.f;
-        float rnew[4], dfn[4] = {0.f, 0.f, 0.f, 0.f};
-        float uu[4], ff[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) uu[v] = fmaf(accs[v], usc, ex[g][v]);
-        io.template eval4<SAVE>(uu, ff, dfn);
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const float f = ff[v];
-            const float r1 = fmaf(eps[v], f - rc[g][v], rc[g][v]);             // (1 - eps) r + eps f(u)
-            const float dd = r1 - rc[g][v];
-            if constexpr (win_on) {
-                ta[g][v] += r1;
-                rpn[g][v] += fmaxf(r1 - a.theta, 0.f);
-                dp[g][v] = fmaf(win2 * dd, dd, dp[g][v]);
-            }
-            rc[g][v] = r1;
-            rnew[v] = r1;              // (rows >= M: never stored, and split with scale 0)
-        }
-        if constexpr (SAVE) {
-            if (er + 3 < M) {       // whole quad inside the matrix (always when M % 4 == 0)
-                const int off = toff[g] < 0 ? -1 : toff[g] + it * M * 4;
-                const mf4 rv = {rnew[0], rnew[1], rnew[2], rnew[3]}, dv = {dfn[0], dfn[1], dfn[2], dfn[3]};
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(
-                    unsigned __attribute__((ext_vector_type(4))), rv), rs_traj, off, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(
-                    unsigned __attribute__((ext_vector_type(4))), dv), rs_df, off, 0, 0);
-            } else {
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int off = (toff[g] < 0 || er + v >= M) ? -1 : toff[g] + (it * M + v) * 4;
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, rnew[v]), rs_traj, off, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dfn[v]), rs_df, off, 0, 0);
-                }
-            }
-        }
-        // new state -> three fp16 parts, written where the matrix lanes read their B operands (rows >= M: scale 0)
-        if (b_live) split3_store(rnew, rs01, rs23, (unsigned)(size_t)(LdsU2)(bbuf + g * S::BB) + b_off);
-    };
-    constexpr std::integral_constant<int, 0> G0{};
-    constexpr std::integral_constant<int, 1> G1{};
-    __syncthreads();                                  // (B)
-    __syncthreads();                                  // phase 0: nothing to finish yet
-    constexpr std::integral_constant<bool, false> W0{};
-    constexpr std::integral_constant<bool, true> W1{};
-    const int nskip = a.skip < T_ ? (a.skip > 0 ? a.skip : 0) : T_;
-    for (int it = 0; it < nskip; ++it) {
-        if (!(SSN_SPLIT_ABLATE & 1)) serial(G0, W0, it);     // phase 2 it + 1
-        __syncthreads();
-        if (!(SSN_SPLIT_ABLATE & 1) && gpw == 2) serial(G1, W0, it);     // phase 2 it + 2
-        __syncthreads();
-    }
-    for (int it = nskip; it < T_; ++it) {
-        if (!(SSN_SPLIT_ABLATE & 1)) serial(G0, W1, it);
-        __syncthreads();
-        if (!(SSN_SPLIT_ABLATE & 1) && gpw == 2) serial(G1, W1, it);
-        __syncthreads();
-    }
-
-    const float inv = 1.f / (float)(T_ - a.skip);
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        if (!live[g]) continue;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            if (er + v >= M) continue;
-            const size_t o = ((size_t)b * a.NB + s0 + 4 * g + j) * M + er + v;
-            a.time_avg[o] = ta[g][v] * inv;
-            a.dyn_row[o] = dp[g][v];
-            a.rate_row[o] = rpn[g][v];
-        }
-    }
-}
-
 
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -376,31 +248,6 @@ __global__ void __launch_bounds__(512, 2) gen_forward_split_kernel(GenFwdArgs<fl
 // of both groups] barrier, the matrix waves idle through the serial parts and vice versa -- fewer MFMAs against no
 // overlap.  Two groups per workgroup only (a.mfma_groups == 2).
 // ---------------------------------------------------------------------------------------------------------------
-template <int RP>
-__device__ __forceinline__ void wide_store(const float (&x)[4], fv2 sc01, fv2 sc23, unsigned bw, unsigned second) {
-    using LdsU2 = __attribute__((address_space(3))) uv2*;
-    const fv2 s01 = (fv2){x[0], x[1]} * sc01, s23 = (fv2){x[2], x[3]} * sc23;
-    auto top = [](fv2 v) { return __builtin_bit_cast(fv2, __builtin_bit_cast(uv2, v) & (uv2){0xffffe000u, 0xffffe000u}); };
-    auto pk = [](fv2 v) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v.x, v.y)); };
-    if constexpr (RP == 3) {
-        const fv2 h01 = top(s01), h23 = top(s23);
-        const fv2 d01 = s01 - h01, d23 = s23 - h23;
-        *(LdsU2)(size_t)bw = (uv2){pk(h01), pk(h23)};
-        const fv2 m01 = top(d01), m23 = top(d23);
-        *(LdsU2)(size_t)(bw + 128u) = (uv2){pk(m01), pk(m23)};
-        *(LdsU2)(size_t)(bw + second) = (uv2){pk(d01 - m01), pk(d23 - m23)};
-    } else {
-        // two parts: both by ROUND TO NEAREST (h = rn(s), m = rn(s - h): |s - h - m| <= 2^-23 |s|, no bias; round 2
-        // truncated both, 2^-21 and biased toward zero)
-        typedef _Float16 hv2_ __attribute__((ext_vector_type(2)));
-        const hv2_ hn01 = __builtin_convertvector(s01, hv2_), hn23 = __builtin_convertvector(s23, hv2_);
-        const fv2 r01 = s01 - __builtin_convertvector(hn01, fv2), r23 = s23 - __builtin_convertvector(hn23, fv2);
-        *(LdsU2)(size_t)bw = (uv2){__builtin_bit_cast(unsigned, hn01), __builtin_bit_cast(unsigned, hn23)};
-        *(LdsU2)(size_t)(bw + 128u) = (uv2){__builtin_bit_cast(unsigned, __builtin_convertvector(r01, hv2_)),
-                                            __builtin_bit_cast(unsigned, __builtin_convertvector(r23, hv2_))};
-    }
-}
-
 template <int MK, int WV, int RP>
 __device__ __forceinline__ void wide_matrix_wave(const float* __restrict__ Wd, int M, int lane, int T_, char* bbuf, char* abuf,
                                                  char* xbuf, unsigned* wmax) {
@@ -482,11 +329,46 @@ __device__ __forceinline__ void wide_matrix_wave(const float* __restrict__ Wd, i
     }
 }
 
-template <int MK, bool SAVE, int RP>
-__global__ void __launch_bounds__(512, 2) gen_forward_wide_kernel(GenFwdArgs<float> a, int rshift) {
+
+// (W . x)[er .. er + 3] of the serial lane's stimulus in group g, in the accumulator's scale: the part columns of the
+// group's sums (alternating: three, 64 B apart; wide: columns 4 g + j and 8 + 4 g + j of the one buffer) plus the extra slot's
+template <int MK, int FORM, int g>
+__device__ __forceinline__ mf4 split_sums(const char* abuf, const char* xbuf, const char* zrow, unsigned a_off, unsigned x_off,
+                                          int x_slot, int j) {
     using S = Split16<MK>;
-    __shared__ __align__(16) char lds[S::LDS];          // (laid out for two groups; this kernel uses the first halves)
-    char* const bbuf = lds;                               // B1: columns s (r_h) and 8 + s (r_m) of stimulus s; B2 = bbuf + BB: r_l
+    using LdsF4 = const __attribute__((address_space(3))) mf4*;
+    if constexpr (FORM == SPLIT_ALTERNATING) {
+        const unsigned ab = (unsigned)(size_t)(LdsF4)(abuf + g * S::AB) + a_off;
+        const unsigned xb = x_slot < 0 ? (unsigned)(size_t)(LdsF4)zrow + (unsigned)(j * 16)
+                                       : (unsigned)(size_t)(LdsF4)(xbuf + g * S::XB) + x_off;
+        const mf4 p0 = *(LdsF4)(size_t)ab, p1 = *(LdsF4)(size_t)(ab + 64u), p2 = *(LdsF4)(size_t)(ab + 128u);
+        const mf4 q0 = *(LdsF4)(size_t)xb, q1 = *(LdsF4)(size_t)(xb + 64u), q2 = *(LdsF4)(size_t)(xb + 128u);
+        return ((p0 + q0) + (p1 + q1)) + (p2 + q2);
+    } else {
+        const unsigned ab = (unsigned)(size_t)(LdsF4)abuf + a_off + (unsigned)(64 * g);
+        const unsigned xb = x_slot < 0 ? (unsigned)(size_t)(LdsF4)zrow + (unsigned)(j * 16)
+                                       : (unsigned)(size_t)(LdsF4)xbuf + x_off + (unsigned)(64 * g);
+        const mf4 p0 = *(LdsF4)(size_t)ab, p1 = *(LdsF4)(size_t)(ab + 128u);
+        const mf4 q0 = *(LdsF4)(size_t)xb, q1 = *(LdsF4)(size_t)(xb + 128u);
+        return (p0 + q0) + (p1 + q1);
+    }
+}
+// x * sc as fp16 parts to where the matrix lanes read the B operand of group g
+template <int MK, int FORM, int g>
+__device__ __forceinline__ void split_state_store(const float (&x)[4], fv2 sc01, fv2 sc23, char* bbuf, unsigned b_off) {
+    using S = Split16<MK>;
+    using LdsU2 = __attribute__((address_space(3))) uv2*;
+    if constexpr (FORM == SPLIT_ALTERNATING)
+        split_store<3>(x, sc01, sc23, (unsigned)(size_t)(LdsU2)(bbuf + g * S::BB) + b_off, 64u, 128u);
+    else
+        split_store<FORM, true>(x, sc01, sc23, (unsigned)(size_t)(LdsU2)bbuf + b_off + (unsigned)(64 * g), 128u, (unsigned)S::BB);
+}
+
+template <int MK, bool SAVE, int FORM>
+__global__ void __launch_bounds__(512, 2) gen_forward_split_kernel(GenFwdArgs<float> a, int rshift) {
+    using S = Split16<MK>;
+    __shared__ __align__(16) char lds[S::LDS];
+    char* const bbuf = lds;
     char* const abuf = lds + 2 * S::BB;
     char* const xbuf = abuf + 2 * S::AB;
     char* const zrow = xbuf + 2 * S::XB;
@@ -502,11 +384,20 @@ __global__ void __launch_bounds__(512, 2) gen_forward_wide_kernel(GenFwdArgs<flo
 
     if (wave < S::WM) {
         const float* Wd = a.W + (size_t)b * M * M;
-        switch (wave) {
-            case 0: wide_matrix_wave<MK, 0, RP>(Wd, M, lane, T_, bbuf, abuf, xbuf, wmax); break;
-            case 1: wide_matrix_wave<MK, 1, RP>(Wd, M, lane, T_, bbuf, abuf, xbuf, wmax); break;
-            case 2: wide_matrix_wave<MK, 2, RP>(Wd, M, lane, T_, bbuf, abuf, xbuf, wmax); break;
-            default: wide_matrix_wave<MK, 3, RP>(Wd, M, lane, T_, bbuf, abuf, xbuf, wmax); break;
+        if constexpr (FORM == SPLIT_ALTERNATING) {
+            switch (wave) {       // phases 0 .. 2T: chains in 0 .. 2T - 1
+                case 0: split_matrix_wave<MK, 0, false>(Wd, M, lane, 0, 2 * T_, 2 * T_ + 1, gpw, bbuf, abuf, xbuf, wmax); break;
+                case 1: split_matrix_wave<MK, 1, false>(Wd, M, lane, 0, 2 * T_, 2 * T_ + 1, gpw, bbuf, abuf, xbuf, wmax); break;
+                case 2: split_matrix_wave<MK, 2, false>(Wd, M, lane, 0, 2 * T_, 2 * T_ + 1, gpw, bbuf, abuf, xbuf, wmax); break;
+                default: split_matrix_wave<MK, 3, false>(Wd, M, lane, 0, 2 * T_, 2 * T_ + 1, gpw, bbuf, abuf, xbuf, wmax); break;
+            }
+        } else {
+            switch (wave) {
+                case 0: wide_matrix_wave<MK, 0, FORM>(Wd, M, lane, T_, bbuf, abuf, xbuf, wmax); break;
+                case 1: wide_matrix_wave<MK, 1, FORM>(Wd, M, lane, T_, bbuf, abuf, xbuf, wmax); break;
+                case 2: wide_matrix_wave<MK, 2, FORM>(Wd, M, lane, T_, bbuf, abuf, xbuf, wmax); break;
+                default: wide_matrix_wave<MK, 3, FORM>(Wd, M, lane, T_, bbuf, abuf, xbuf, wmax); break;
+            }
         }
         return;
     }
@@ -551,8 +442,6 @@ __global__ void __launch_bounds__(512, 2) gen_forward_wide_kernel(GenFwdArgs<flo
     const unsigned b_off = (unsigned)(((er / 32) * 4 + ((er & 31) >> 3)) * S::BROW + j * 16 + ((er & 7) >> 2) * 8);
     const float rs = __builtin_bit_cast(float, (unsigned)(127 + rshift) << 23);          // 2^rshift
     const fv2 rs01 = {er < M ? rs : 0.f, er + 1 < M ? rs : 0.f}, rs23 = {er + 2 < M ? rs : 0.f, er + 3 < M ? rs : 0.f};
-    using LdsF4 = const __attribute__((address_space(3))) mf4*;
-    using LdsU2 = __attribute__((address_space(3))) uv2*;
 
     __syncthreads();                                                          // (A) max |W| of the draw is known
     const float usc = split_u_scale(*wmax, rshift);                           // 2^-(a + rshift)
@@ -560,13 +449,7 @@ __global__ void __launch_bounds__(512, 2) gen_forward_wide_kernel(GenFwdArgs<flo
     auto serial = [&](auto G, auto WIN, int it) {
         constexpr int g = decltype(G)::value;
         constexpr bool win_on = decltype(WIN)::value;
-        // columns 4 g + j (W . r_h, and W_h . r_l on top when RP = 3) and 8 + 4 g + j (W . r_m) of the one sums buffer
-        const unsigned ab = (unsigned)(size_t)(LdsF4)abuf + a_off + (unsigned)(64 * g);
-        const unsigned xb = x_slot < 0 ? (unsigned)(size_t)(LdsF4)zrow + (unsigned)(j * 16)
-                                       : (unsigned)(size_t)(LdsF4)xbuf + x_off + (unsigned)(64 * g);
-        const mf4 p0 = *(LdsF4)(size_t)ab, p1 = *(LdsF4)(size_t)(ab + 128u);
-        const mf4 q0 = *(LdsF4)(size_t)xb, q1 = *(LdsF4)(size_t)(xb + 128u);
-        const mf4 acc = (p0 + q0) + (p1 + q1);
+        const mf4 acc = split_sums<MK, FORM, g>(abuf, xbuf, zrow, a_off, x_off, x_slot, j);
         const float accs[4] = {acc.x, acc.y, acc.z, acc.w};
         const float win2 = (it > a.skip) ? 1.f : 0.f;
         float rnew[4], dfn[4] = {0.f, 0.f, 0.f, 0.f};
@@ -604,27 +487,33 @@ __global__ void __launch_bounds__(512, 2) gen_forward_wide_kernel(GenFwdArgs<flo
                 }
             }
         }
-        // new state -> three fp16 parts, written where the matrix lanes read their B operands (rows >= M: scale 0)
-        if (b_live) wide_store<RP>(rnew, rs01, rs23, (unsigned)(size_t)(LdsU2)bbuf + b_off + (unsigned)(64 * g), (unsigned)S::BB);
+        // new state -> fp16 parts, written where the matrix lanes read their B operands (rows >= M: scale 0)
+        if (b_live) split_state_store<MK, FORM, g>(rnew, rs01, rs23, bbuf, b_off);
     };
     constexpr std::integral_constant<int, 0> G0{};
     constexpr std::integral_constant<int, 1> G1{};
     __syncthreads();                                  // (B)
+    if constexpr (FORM == SPLIT_ALTERNATING) __syncthreads();       // phase 0: nothing to finish yet
     constexpr std::integral_constant<bool, false> W0{};
     constexpr std::integral_constant<bool, true> W1{};
     const int nskip = a.skip < T_ ? (a.skip > 0 ? a.skip : 0) : T_;
-    for (int it = 0; it < nskip; ++it) {
-        __syncthreads();                              // the chain of step it is done
-        serial(G0, W0, it);
-        serial(G1, W0, it);
-        __syncthreads();
-    }
-    for (int it = nskip; it < T_; ++it) {
-        __syncthreads();
-        serial(G0, W1, it);
-        serial(G1, W1, it);
-        __syncthreads();
-    }
+    // a step of the alternating form: phases 2 it + 1 | 2 it + 2, each behind the other group's chain; of the wide forms:
+    // behind the chain of step it, both groups, then a barrier once the new state is stored
+    auto step = [&](auto WIN, int it) {
+        if constexpr (FORM == SPLIT_ALTERNATING) {
+            serial(G0, WIN, it);
+            __syncthreads();
+            if (gpw == 2) serial(G1, WIN, it);
+            __syncthreads();
+        } else {
+            __syncthreads();
+            serial(G0, WIN, it);
+            serial(G1, WIN, it);
+            __syncthreads();
+        }
+    };
+    for (int it = 0; it < nskip; ++it) step(W0, it);
+    for (int it = nskip; it < T_; ++it) step(W1, it);
 
     const float inv = 1.f / (float)(T_ - a.skip);
 #pragma unroll
@@ -641,24 +530,6 @@ __global__ void __launch_bounds__(512, 2) gen_forward_wide_kernel(GenFwdArgs<flo
     }
 }
 
-
-// max over the wave of a non-negative float (bit patterns order like the values), in every lane's SGPR copy
-__device__ __forceinline__ unsigned wave_max_bits(float x) {
-    unsigned v = __builtin_bit_cast(unsigned, x);
-    auto dpp_max = [&](auto CTRL, auto ROWMASK) {
-        const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, decltype(CTRL)::value, decltype(ROWMASK)::value, 0xf, false);
-        v = o > v ? o : v;
-    };
-    using I = std::integral_constant<int, 0>;
-    (void)sizeof(I);
-    dpp_max(std::integral_constant<int, 0xB1>{}, std::integral_constant<int, 0xf>{});    // quad_perm [1,0,3,2]
-    dpp_max(std::integral_constant<int, 0x4E>{}, std::integral_constant<int, 0xf>{});    // quad_perm [2,3,0,1]
-    dpp_max(std::integral_constant<int, 0x141>{}, std::integral_constant<int, 0xf>{});   // row_half_mirror
-    dpp_max(std::integral_constant<int, 0x140>{}, std::integral_constant<int, 0xf>{});   // row_mirror: every lane = row max
-    dpp_max(std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{});   // row_bcast15 -> rows 1, 3
-    dpp_max(std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{});   // row_bcast31 -> rows 2, 3
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
 
 // Reverse-time adjoint sweep with W^T delta on the fp16 matrix cores: the matrix waves hold W^T as two fp16 parts
 // (the forward's layout and scale), the serial waves own the adjoint state (the recurrence, HBM streams and the in-place
@@ -788,8 +659,6 @@ __global__ void __launch_bounds__(512, 2) gen_backward_split_kernel(GenBwdArgs<f
     const unsigned x_off = (unsigned)((x_slot * 4 + rq) * S::ROW + j * 16);
     const bool b_live = er < 32 * S::NKT;
     const unsigned b_off = (unsigned)(((er / 32) * 4 + ((er & 31) >> 3)) * S::BROW + j * 16 + ((er & 7) >> 2) * 8);
-    using LdsF4 = const __attribute__((address_space(3))) mf4*;
-    using LdsU2 = __attribute__((address_space(3))) uv2*;
 
     __syncthreads();                                                          // (A) max |W| and the first delta scale
     const int wexp = split_w_exp(*wmax);
@@ -812,12 +681,7 @@ __global__ void __launch_bounds__(512, 2) gen_backward_split_kernel(GenBwdArgs<f
         int bexp = 7 - ((int)((ref >> 23) & 0xffu) - 127);
         bexp = ref == 0u ? 0 : (bexp > 100 ? 100 : (bexp < -100 ? -100 : bexp));
         if (tau < T_) {
-            const unsigned ab = (unsigned)(size_t)(LdsF4)(abuf + g * S::AB) + a_off;
-            const unsigned xb = x_slot < 0 ? (unsigned)(size_t)(LdsF4)zrow + (unsigned)(j * 16)
-                                           : (unsigned)(size_t)(LdsF4)(xbuf + g * S::XB) + x_off;
-            const mf4 p0 = *(LdsF4)(size_t)ab, p1 = *(LdsF4)(size_t)(ab + 64u), p2 = *(LdsF4)(size_t)(ab + 128u);
-            const mf4 q0 = *(LdsF4)(size_t)xb, q1 = *(LdsF4)(size_t)(xb + 64u), q2 = *(LdsF4)(size_t)(xb + 128u);
-            const mf4 acc = ((p0 + q0) + (p1 + q1)) + (p2 + q2);                   // W^T delta_{tau+1} 2^(a + bused)
+            const mf4 acc = split_sums<MK, SPLIT_ALTERNATING, g>(abuf, xbuf, zrow, a_off, x_off, x_slot, j);   // W^T delta_{tau+1} 2^(a + bused)
             const float usc = __builtin_bit_cast(float, (unsigned)(127 - wexp - bused[g]) << 23);
             carry[g][0] = fmaf(acc.x, usc, carry[g][0]); carry[g][1] = fmaf(acc.y, usc, carry[g][1]);
             carry[g][2] = fmaf(acc.z, usc, carry[g][2]); carry[g][3] = fmaf(acc.w, usc, carry[g][3]);
@@ -848,7 +712,7 @@ __global__ void __launch_bounds__(512, 2) gen_backward_split_kernel(GenBwdArgs<f
                 delta[0] = __builtin_nanf("");
                 if (a.dmax) atomicMax(a.dmax + b, 0x7fc00000u);       // the draw's hand-over word says "poisoned" (NaN; host side counts them)
             }
-            if (b_live) split3_store(delta, (fv2){rs, rs}, (fv2){rs, rs}, (unsigned)(size_t)(LdsU2)(bbuf + g * S::BB) + b_off);
+            if (b_live) split_state_store<MK, SPLIT_ALTERNATING, g>(delta, (fv2){rs, rs}, (fv2){rs, rs}, bbuf, b_off);
         }
         bused[g] = bexp;
         const unsigned wm = wave_max_bits(live[g] ? dm : 0.f);
@@ -907,6 +771,7 @@ __global__ void __launch_bounds__(512, 2) gen_backward_split_kernel(GenBwdArgs<f
         }
     }
 }
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // Fixed-point solver (Euler loop of tc_gan/ext/ssnode.c:69-187; contract, stop protocol and phase structure of
@@ -1012,160 +877,10 @@ __device__ __forceinline__ void solve_split_matrix_wave(const SolveArgs<float>& 
     }
 }
 
-template <int MK>
-__global__ void __launch_bounds__(512, 2) solve_split_kernel(SolveArgs<float> a) {
-    using S = Split16<MK>;
-    __shared__ __align__(16) char lds[S::LDS + 128];
-    char* const bbuf = lds;
-    char* const abuf = lds + 2 * S::BB;
-    char* const xbuf = abuf + 2 * S::AB;
-    char* const zrow = xbuf + 2 * S::XB;
-    unsigned* const wmax = reinterpret_cast<unsigned*>(zrow + S::ROW);       // [0] max |W|, [1] max |r0|
-    int (*flags)[8] = reinterpret_cast<int (*)[8]>(zrow + S::ROW + 32);       // [3][8]
-    const int M = a.M, N = a.N, max_iter = a.st.max_iter;
-    const int ngroups = (a.NB + 7) / 8;
-    const int b = blockIdx.x / ngroups;
-    const int s0 = (blockIdx.x % ngroups) * 8;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = threadIdx.x; c < (S::LDS + 128) / 4; c += blockDim.x) reinterpret_cast<unsigned*>(lds)[c] = 0u;
-    __syncthreads();
-
-    if (wave < S::WM) {
-        switch (wave) {
-            case 0: solve_split_matrix_wave<MK, 0>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
-            case 1: solve_split_matrix_wave<MK, 1>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
-            case 2: solve_split_matrix_wave<MK, 2>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
-            default: solve_split_matrix_wave<MK, 3>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
-        }
-        return;
-    }
-
-    // ================================ serial wave ================================
-    const int sw = wave - S::WM;
-    const int blk = lane >> 2, j = lane & 3;
-    const int er = 64 * sw + 4 * blk;
-    int my_code = 1, my_steps = max_iter;
-    bool my_frozen = lane >= 8 || s0 + lane >= a.NB;
-    unsigned frozen = (unsigned)__builtin_amdgcn_ballot_w64(my_frozen) & 0xffu;
-    auto verdict = [&](int g, int it, int f) {
-        const bool fnc = (f & 0xffff) != 0, fhb = (f >> 16) != 0;
-        const bool stop = lane < 8 && (lane >> 2) == g && !my_frozen && (!fnc || fhb);
-        my_code = stop ? (fnc ? 2 : 0) : my_code;
-        my_steps = stop ? it + 1 : my_steps;
-        my_frozen = my_frozen || stop;
-        frozen = (unsigned)__builtin_amdgcn_ballot_w64(my_frozen) & 0xffu;
-    };
-    float eps[4], rc[2][4], rp[2][4], ex[2][4];
-    bool live[2], rowok[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) { eps[v] = (er + v < N) ? a.st.eps_E : a.st.eps_I; rowok[v] = er + v < M; }
-    float r0max = 0.f;
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        const int s = s0 + 4 * g + j;
-        live[g] = s < a.NB;
-        const size_t vec = ((size_t)b * a.NB + (live[g] ? s : 0)) * M;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const bool ok = live[g] && er + v < M;
-            rc[g][v] = rp[g][v] = ok ? a.r[vec + er + v] : 0.f;
-            ex[g][v] = ok ? a.ext[(a.ext_per_draw ? vec : (size_t)s * M) + er + v] : 0.f;
-            r0max = fmaxf(r0max, __builtin_fabsf(rc[g][v]));
-        }
-    }
-    {
-        const unsigned wm0 = wave_max_bits(r0max);
-        if (lane == 0) atomicMax(wmax + 1, wm0);
-    }
-    const IoSelect io(a.io);
-    const int rt = er / 16 < S::NRT ? er / 16 : S::NRT - 1, rq = (er / 4) & 3;
-    const unsigned a_off = (unsigned)((rt * 4 + rq) * S::ROW + j * 16);
-    int x_slot = -1;
-#pragma unroll
-    for (int w = 1; w < S::WM; ++w)
-        if (S::start(w) % S::NKT != 0 && S::start(w) / S::NKT == rt) x_slot = w - 1;
-    const unsigned x_off = (unsigned)((x_slot * 4 + rq) * S::ROW + j * 16);
-    const bool b_live = er < 32 * S::NKT;
-    const unsigned b_off = (unsigned)(((er / 32) * 4 + ((er & 31) >> 3)) * S::BROW + j * 16 + ((er & 7) >> 2) * 8);
-    using LdsF4 = const __attribute__((address_space(3))) mf4*;
-    using LdsU2 = __attribute__((address_space(3))) uv2*;
-    __syncthreads();                                                          // (A) max |W|, max |r0|
-    // state scale: bound 2^rshift < 2^14 for bound = max(rate_hard_bound, max |r0|)
-    const float bound = fmaxf(a.io.hard, __builtin_bit_cast(float, wmax[1]));
-    int rshift = 13 - ((int)((__builtin_bit_cast(unsigned, bound) >> 23) & 0xffu) - 127);
-    rshift = rshift > 100 ? 100 : (rshift < -100 ? -100 : rshift);
-    const float usc = split_u_scale(*wmax, rshift);
-    const float rs = __builtin_bit_cast(float, (unsigned)(127 + rshift) << 23);
-    const fv2 rs01 = {er < M ? rs : 0.f, er + 1 < M ? rs : 0.f}, rs23 = {er + 2 < M ? rs : 0.f, er + 3 < M ? rs : 0.f};
-#pragma unroll
-    for (int g = 0; g < 2; ++g)
-        if (b_live) split3_store(rc[g], rs01, rs23, (unsigned)(size_t)(LdsU2)(bbuf + g * S::BB) + b_off);
-    auto serial = [&](auto G, int it) {
-        constexpr int g = decltype(G)::value;
-        const unsigned ab = (unsigned)(size_t)(LdsF4)(abuf + g * S::AB) + a_off;
-        const unsigned xb = x_slot < 0 ? (unsigned)(size_t)(LdsF4)zrow + (unsigned)(j * 16)
-                                       : (unsigned)(size_t)(LdsF4)(xbuf + g * S::XB) + x_off;
-        const mf4 p0 = *(LdsF4)(size_t)ab, p1 = *(LdsF4)(size_t)(ab + 64u), p2 = *(LdsF4)(size_t)(ab + 128u);
-        const mf4 q0 = *(LdsF4)(size_t)xb, q1 = *(LdsF4)(size_t)(xb + 64u), q2 = *(LdsF4)(size_t)(xb + 128u);
-        const mf4 acc = ((p0 + q0) + (p1 + q1)) + (p2 + q2);
-        const float accs[4] = {acc.x, acc.y, acc.z, acc.w};
-        float uu[4], ff[4], dummy[4], r1[4], dabs[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) uu[v] = fmaf(accs[v], usc, ex[g][v]);
-        io.template eval4<false>(uu, ff, dummy);
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            r1[v] = rc[g][v] + (-rc[g][v] + ff[v]) * eps[v];                   // ssnode.c:64-67
-            dabs[v] = rowok[v] ? fabsf(r1[v] - rc[g][v]) : -1.f;
-        }
-        if (sw == 0 && lane < 4) flags[(it + 1) % 3][4 * g + lane] = 0;
-        if (live[g] && !((frozen >> (4 * g + j)) & 1u) && er < M) {
-            const float dmax = fmaxf(fmaxf(dabs[0], dabs[1]), fmaxf(dabs[2], dabs[3]));
-            const float rmax = fmaxf(fmaxf(r1[0], r1[1]), fmaxf(r1[2], r1[3]));
-            short* fw = reinterpret_cast<short*>(&flags[it % 3][4 * g + j]);
-            if (dmax >= a.st.atol) fw[0] = 1;
-            if (a.st.check_hard && rmax >= a.st.hard_stop) fw[1] = 1;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) { rp[g][v] = rc[g][v]; rc[g][v] = rowok[v] ? r1[v] : rc[g][v]; }
-            split3_store(rc[g], rs01, rs23, (unsigned)(size_t)(LdsU2)(bbuf + g * S::BB) + b_off);
-        }
-    };
-    constexpr std::integral_constant<int, 0> G0{};
-    constexpr std::integral_constant<int, 1> G1{};
-    __syncthreads();                                                          // (B)
-    for (int it = 0; it <= max_iter; ++it) {
-        int f4 = 0;
-        if (it >= 1) f4 = flags[(it - 1) % 3][lane & 7];                        // phase 2 it: serial part of (1, it - 1)
-        if (it >= 1) serial(G1, it - 1);
-        if (it >= 1) verdict(0, it - 1, f4);
-        if (frozen == 0xffu) break;
-        __syncthreads();
-        if (it >= 1) f4 = flags[(it - 1) % 3][lane & 7];                        // phase 2 it + 1: serial part of (0, it)
-        if (it < max_iter) serial(G0, it);
-        if (it >= 1) verdict(1, it - 1, f4);
-        if (frozen == 0xffu) break;
-        __syncthreads();
-    }
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        if (!live[g]) continue;
-        const size_t unit = (size_t)b * a.NB + s0 + 4 * g + j;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            if (er + v >= M) continue;
-            a.r[unit * M + er + v] = rc[g][v];
-            if (a.r_prev) a.r_prev[unit * M + er + v] = rp[g][v];
-        }
-    }
-    if (sw == 0 && lane < 8 && s0 + lane < a.NB) {
-        const size_t unit = (size_t)b * a.NB + s0 + lane;
-        a.codes[unit] = my_code;
-        if (a.steps) a.steps[unit] = my_steps;
-    }
-}
 
 
-// Wide form of the split solver (see gen_forward_wide_kernel): all 8 stimuli in one chain per step, the state as two fp16
+
+// Matrix wave of the wide form of the split solver (see wide_matrix_wave): all 8 stimuli in one chain per step, the state as two fp16
 // parts; a step is [chain] barrier [serial parts of both groups] barrier, the stop flags of a step are read by every
 // wave at the start of the next one.
 template <int MK, int WV>
@@ -1263,9 +978,11 @@ __device__ __forceinline__ void solve_wide_matrix_wave(const SolveArgs<float>& a
     }
 }
 
-template <int MK>
-__global__ void __launch_bounds__(512, 2) solve_wide_kernel(SolveArgs<float> a) {
+
+template <int MK, bool WIDE>
+__global__ void __launch_bounds__(512, 2) solve_split_kernel(SolveArgs<float> a) {
     using S = Split16<MK>;
+    constexpr int FORM = WIDE ? SPLIT_WIDE2 : SPLIT_ALTERNATING;
     __shared__ __align__(16) char lds[S::LDS + 128];
     char* const bbuf = lds;
     char* const abuf = lds + 2 * S::BB;
@@ -1282,11 +999,20 @@ __global__ void __launch_bounds__(512, 2) solve_wide_kernel(SolveArgs<float> a) 
     __syncthreads();
 
     if (wave < S::WM) {
-        switch (wave) {
-            case 0: solve_wide_matrix_wave<MK, 0>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
-            case 1: solve_wide_matrix_wave<MK, 1>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
-            case 2: solve_wide_matrix_wave<MK, 2>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
-            default: solve_wide_matrix_wave<MK, 3>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
+        if constexpr (WIDE) {
+            switch (wave) {
+                case 0: solve_wide_matrix_wave<MK, 0>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
+                case 1: solve_wide_matrix_wave<MK, 1>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
+                case 2: solve_wide_matrix_wave<MK, 2>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
+                default: solve_wide_matrix_wave<MK, 3>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
+            }
+        } else {
+            switch (wave) {
+                case 0: solve_split_matrix_wave<MK, 0>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
+                case 1: solve_split_matrix_wave<MK, 1>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
+                case 2: solve_split_matrix_wave<MK, 2>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
+                default: solve_split_matrix_wave<MK, 3>(a, b, lane, bbuf, abuf, xbuf, wmax, flags, s0); break;
+            }
         }
         return;
     }
@@ -1338,8 +1064,6 @@ __global__ void __launch_bounds__(512, 2) solve_wide_kernel(SolveArgs<float> a) 
     const unsigned x_off = (unsigned)((x_slot * 4 + rq) * S::ROW + j * 16);
     const bool b_live = er < 32 * S::NKT;
     const unsigned b_off = (unsigned)(((er / 32) * 4 + ((er & 31) >> 3)) * S::BROW + j * 16 + ((er & 7) >> 2) * 8);
-    using LdsF4 = const __attribute__((address_space(3))) mf4*;
-    using LdsU2 = __attribute__((address_space(3))) uv2*;
     __syncthreads();                                                          // (A) max |W|, max |r0|
     // state scale: bound 2^rshift < 2^14 for bound = max(rate_hard_bound, max |r0|)
     const float bound = fmaxf(a.io.hard, __builtin_bit_cast(float, wmax[1]));
@@ -1348,17 +1072,16 @@ __global__ void __launch_bounds__(512, 2) solve_wide_kernel(SolveArgs<float> a) 
     const float usc = split_u_scale(*wmax, rshift);
     const float rs = __builtin_bit_cast(float, (unsigned)(127 + rshift) << 23);
     const fv2 rs01 = {er < M ? rs : 0.f, er + 1 < M ? rs : 0.f}, rs23 = {er + 2 < M ? rs : 0.f, er + 3 < M ? rs : 0.f};
+    using LdsU2 = __attribute__((address_space(3))) uv2*;
 #pragma unroll
-    for (int g = 0; g < 2; ++g)
-        if (b_live) wide_store<2>(rc[g], rs01, rs23, (unsigned)(size_t)(LdsU2)bbuf + b_off + (unsigned)(64 * g), 0u);
+    for (int g = 0; g < 2; ++g)         // (split_state_store with g a loop variable)
+        if (b_live) {
+            if constexpr (WIDE) split_store<2>(rc[g], rs01, rs23, (unsigned)(size_t)(LdsU2)bbuf + b_off + (unsigned)(64 * g), 128u, 0u);
+            else split_store<3>(rc[g], rs01, rs23, (unsigned)(size_t)(LdsU2)(bbuf + g * S::BB) + b_off, 64u, 128u);
+        }
     auto serial = [&](auto G, int it) {
         constexpr int g = decltype(G)::value;
-        const unsigned ab = (unsigned)(size_t)(LdsF4)abuf + a_off + (unsigned)(64 * g);      // columns 4 g + j and 8 + 4 g + j
-        const unsigned xb = x_slot < 0 ? (unsigned)(size_t)(LdsF4)zrow + (unsigned)(j * 16)
-                                       : (unsigned)(size_t)(LdsF4)xbuf + x_off + (unsigned)(64 * g);
-        const mf4 p0 = *(LdsF4)(size_t)ab, p1 = *(LdsF4)(size_t)(ab + 128u);
-        const mf4 q0 = *(LdsF4)(size_t)xb, q1 = *(LdsF4)(size_t)(xb + 128u);
-        const mf4 acc = (p0 + q0) + (p1 + q1);
+        const mf4 acc = split_sums<MK, FORM, g>(abuf, xbuf, zrow, a_off, x_off, x_slot, j);
         const float accs[4] = {acc.x, acc.y, acc.z, acc.w};
         float uu[4], ff[4], dummy[4], r1[4], dabs[4];
 #pragma unroll
@@ -1378,22 +1101,38 @@ __global__ void __launch_bounds__(512, 2) solve_wide_kernel(SolveArgs<float> a) 
             if (a.st.check_hard && rmax >= a.st.hard_stop) fw[1] = 1;
 #pragma unroll
             for (int v = 0; v < 4; ++v) { rp[g][v] = rc[g][v]; rc[g][v] = rowok[v] ? r1[v] : rc[g][v]; }
-            wide_store<2>(rc[g], rs01, rs23, (unsigned)(size_t)(LdsU2)bbuf + b_off + (unsigned)(64 * g), 0u);
+            split_state_store<MK, FORM, g>(rc[g], rs01, rs23, bbuf, b_off);
         }
     };
     constexpr std::integral_constant<int, 0> G0{};
     constexpr std::integral_constant<int, 1> G1{};
     __syncthreads();                                                          // (B)
-    for (int it = 0; it <= max_iter; ++it) {
-        if (it >= 1) {
-            const int f4 = flags[(it - 1) % 3][lane & 7];
-            verdict(0, it - 1, f4);
-            verdict(1, it - 1, f4);
+    if constexpr (WIDE) {
+        for (int it = 0; it <= max_iter; ++it) {
+            if (it >= 1) {
+                const int f4 = flags[(it - 1) % 3][lane & 7];
+                verdict(0, it - 1, f4);
+                verdict(1, it - 1, f4);
+            }
+            if (frozen == 0xffu) break;
+            __syncthreads();                          // the chain of step it is done
+            if (it < max_iter) { serial(G0, it); serial(G1, it); }
+            __syncthreads();
         }
-        if (frozen == 0xffu) break;
-        __syncthreads();                              // the chain of step it is done
-        if (it < max_iter) { serial(G0, it); serial(G1, it); }
-        __syncthreads();
+    } else {
+        for (int it = 0; it <= max_iter; ++it) {
+            int f4 = 0;
+            if (it >= 1) f4 = flags[(it - 1) % 3][lane & 7];                    // phase 2 it: serial part of (1, it - 1)
+            if (it >= 1) serial(G1, it - 1);
+            if (it >= 1) verdict(0, it - 1, f4);
+            if (frozen == 0xffu) break;
+            __syncthreads();
+            if (it >= 1) f4 = flags[(it - 1) % 3][lane & 7];                    // phase 2 it + 1: serial part of (0, it)
+            if (it < max_iter) serial(G0, it);
+            if (it >= 1) verdict(1, it - 1, f4);
+            if (frozen == 0xffu) break;
+            __syncthreads();
+        }
     }
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
@@ -1413,10 +1152,21 @@ __global__ void __launch_bounds__(512, 2) solve_wide_kernel(SolveArgs<float> a) 
     }
 }
 
+
 static int split_pick_mk(int M) {
     const int ladder[] = {104, 152, 208};
     for (int mk : ladder) if (M <= mk) return mk;
     return 0;
+}
+// f(std::integral_constant<int, MK>) for the tile grid split_pick_mk names
+template <class F>
+static hipError_t split_with_mk(int M, F&& f) {
+    switch (split_pick_mk(M)) {
+        case 104: return f(std::integral_constant<int, 104>{});
+        case 152: return f(std::integral_constant<int, 152>{});
+        case 208: return f(std::integral_constant<int, 208>{});
+        default: return hipErrorInvalidValue;
+    }
 }
 
 // rshift: r 2^rshift stays below the fp16 range for every reachable rate (r <= rate_hard_bound with the saturating
@@ -1436,68 +1186,44 @@ int gen_split_wide_parts() {
     static const int rp = [] { const char* e = getenv("SSN_FWD_WIDE"); return (e && (e[0] == '0' || e[0] == '2' || e[0] == '3')) ? e[0] - '0' : 2; }();
     return rp;
 }
-template <int MK>
+template <int MK, bool SAVE>
 static hipError_t launch_split_mk(const GenFwdArgs<float>& a, int rshift, hipStream_t st) {
     const int ngroups = (a.NB + 4 * a.mfma_groups - 1) / (4 * a.mfma_groups);
-    if (a.mfma_groups == 2 && a.split_form) {
-        const bool three = a.split_form == 3;
-        if (a.traj) {
-            if (three) hipLaunchKernelGGL((gen_forward_wide_kernel<MK, true, 3>), dim3(a.B * ngroups), dim3(512), 0, st, a, rshift);
-            else hipLaunchKernelGGL((gen_forward_wide_kernel<MK, true, 2>), dim3(a.B * ngroups), dim3(512), 0, st, a, rshift);
-        } else {
-            if (three) hipLaunchKernelGGL((gen_forward_wide_kernel<MK, false, 3>), dim3(a.B * ngroups), dim3(512), 0, st, a, rshift);
-            else hipLaunchKernelGGL((gen_forward_wide_kernel<MK, false, 2>), dim3(a.B * ngroups), dim3(512), 0, st, a, rshift);
-        }
-        return hipGetLastError();
-    }
-    if (a.traj) hipLaunchKernelGGL((gen_forward_split_kernel<MK, true>), dim3(a.B * ngroups), dim3(512), 0, st, a, rshift);
-    else hipLaunchKernelGGL((gen_forward_split_kernel<MK, false>), dim3(a.B * ngroups), dim3(512), 0, st, a, rshift);
+    const int form = a.mfma_groups == 2 ? a.split_form : SPLIT_ALTERNATING;
+    const dim3 grid(a.B * ngroups), block(512);
+    if (form == SPLIT_WIDE3) hipLaunchKernelGGL((gen_forward_split_kernel<MK, SAVE, SPLIT_WIDE3>), grid, block, 0, st, a, rshift);
+    else if (form) hipLaunchKernelGGL((gen_forward_split_kernel<MK, SAVE, SPLIT_WIDE2>), grid, block, 0, st, a, rshift);
+    else hipLaunchKernelGGL((gen_forward_split_kernel<MK, SAVE, SPLIT_ALTERNATING>), grid, block, 0, st, a, rshift);
     return hipGetLastError();
 }
 hipError_t launch_gen_forward_split(const GenFwdArgs<float>& a, hipStream_t st) {
     const int rshift = gen_split_rshift(a);
     if (rshift < 0) return hipErrorInvalidValue;
-    switch (split_pick_mk(a.M)) {
-        case 104: return launch_split_mk<104>(a, rshift, st);
-        case 152: return launch_split_mk<152>(a, rshift, st);
-        case 208: return launch_split_mk<208>(a, rshift, st);
-        default: return hipErrorInvalidValue;
-    }
+    return split_with_mk(a.M, [&](auto MK) {
+        return a.traj ? launch_split_mk<decltype(MK)::value, true>(a, rshift, st) : launch_split_mk<decltype(MK)::value, false>(a, rshift, st);
+    });
 }
 
 bool solve_split_supported(const SolveArgs<float>& a) {
     return a.io.io_type == SSN_IO_TANH && a.io.hard > 0.f && a.io.hard < 3.0e4f && a.io.soft >= 0.f && a.st.eps_E > 0.f &&
            a.st.eps_E <= 1.f && a.st.eps_I > 0.f && a.st.eps_I <= 1.f && !(a.M & 1) && a.NB >= 4 && split_pick_mk(a.M) != 0;
 }
-template <int MK>
-static hipError_t launch_solve_split_mk(const SolveArgs<float>& a, hipStream_t st) {
-    if (a.split_form) hipLaunchKernelGGL((solve_wide_kernel<MK>), dim3(a.B * ((a.NB + 7) / 8)), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((solve_split_kernel<MK>), dim3(a.B * ((a.NB + 7) / 8)), dim3(512), 0, st, a);
-    return hipGetLastError();
-}
 hipError_t launch_solve_split(const SolveArgs<float>& a, hipStream_t st) {
     if (!solve_split_supported(a)) return hipErrorInvalidValue;
-    switch (split_pick_mk(a.M)) {
-        case 104: return launch_solve_split_mk<104>(a, st);
-        case 152: return launch_solve_split_mk<152>(a, st);
-        case 208: return launch_solve_split_mk<208>(a, st);
-        default: return hipErrorInvalidValue;
-    }
+    return split_with_mk(a.M, [&](auto MK) {
+        const dim3 grid(a.B * ((a.NB + 7) / 8)), block(512);
+        if (a.split_form) hipLaunchKernelGGL((solve_split_kernel<decltype(MK)::value, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((solve_split_kernel<decltype(MK)::value, false>), grid, block, 0, st, a);
+        return hipGetLastError();
+    });
 }
 
-template <int MK>
-static hipError_t launch_split_bwd_mk(const GenBwdArgs<float>& a, hipStream_t st) {
-    const int ngroups = (a.NB + 4 * a.mfma_groups - 1) / (4 * a.mfma_groups);
-    hipLaunchKernelGGL((gen_backward_split_kernel<MK>), dim3(a.B * ngroups), dim3(512), 0, st, a);
-    return hipGetLastError();
-}
 hipError_t launch_gen_backward_split(const GenBwdArgs<float>& a, hipStream_t st) {
-    switch (split_pick_mk(a.M)) {
-        case 104: return launch_split_bwd_mk<104>(a, st);
-        case 152: return launch_split_bwd_mk<152>(a, st);
-        case 208: return launch_split_bwd_mk<208>(a, st);
-        default: return hipErrorInvalidValue;
-    }
+    return split_with_mk(a.M, [&](auto MK) {
+        const int ngroups = (a.NB + 4 * a.mfma_groups - 1) / (4 * a.mfma_groups);
+        hipLaunchKernelGGL((gen_backward_split_kernel<decltype(MK)::value>), dim3(a.B * ngroups), dim3(512), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace ssn

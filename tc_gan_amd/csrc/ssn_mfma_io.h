@@ -109,4 +109,22 @@ struct IoSelect {
     }
 };
 
+// max over the wave of a non-negative float (bit patterns order like the values), the same value in every lane's SGPR copy
+__device__ __forceinline__ unsigned wave_max_bits(float x) {
+    unsigned v = __builtin_bit_cast(unsigned, x);
+#define SSN_DPP_MAX(CTRL, ROWMASK)                                                                                   \
+    {                                                                                                                     \
+        const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWMASK, 0xf, false);                   \
+        v = o > v ? o : v;                                                                                                \
+    }
+    SSN_DPP_MAX(0xB1, 0xf)     // quad_perm [1,0,3,2]
+    SSN_DPP_MAX(0x4E, 0xf)     // quad_perm [2,3,0,1]
+    SSN_DPP_MAX(0x141, 0xf)    // row_half_mirror
+    SSN_DPP_MAX(0x140, 0xf)    // row_mirror: every lane = row max
+    SSN_DPP_MAX(0x142, 0xa)    // row_bcast15 -> rows 1, 3
+    SSN_DPP_MAX(0x143, 0xc)    // row_bcast31 -> rows 2, 3
+#undef SSN_DPP_MAX
+    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+
 }  // namespace ssn

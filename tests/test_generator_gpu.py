@@ -677,6 +677,57 @@ def test_split_kernels_random_shapes_against_the_fp32_mfma_kernels():
                 np.testing.assert_allclose(got, want, rtol=2e-5, atol=3e-6 * scale + 1e-30, err_msg=tag)
 
 
+def test_three_part_wide_forward_against_the_fp32_mfma_kernel():
+    """`SSN_FWD_WIDE=3` turns kernel code 4 into forward variant 7: the wide form with the state as THREE fp16 parts (exact,
+    a third MFMA per tile), which no other test launches.  One shape per tile grid, each with 2N no multiple of 4 (partial
+    row quad, idle lanes) and 6 stimuli (ragged second group): time averages, trajectory, f' and the two penalties against
+    the fp32 MFMA kernel (2) within the bound `test_split_kernels_random_shapes_against_the_fp32_mfma_kernels` holds codes
+    4 / 5 / 6 / 8 to; the alternating form (6, state exact as well) on the same inputs to the same bound.  (The switch is
+    read once per process: subprocess.)"""
+    import os
+    import subprocess
+    import sys
+    import tempfile
+    from tc_gan_amd import stimuli, weight_gen
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sizes, B, NB, T, skip = (51, 75, 101), 2, 6, 12, 5
+    code = (
+        "import sys, numpy as np, torch; sys.path.insert(0, %r)\n"
+        "from tc_gan_amd import genops\n"
+        "inp = np.load(sys.argv[1]); res = {}\n"
+        "for N in %r:\n"
+        "    W, ext = torch.as_tensor(inp['W%%d' %% N]).cuda(), torch.as_tensor(inp['ext%%d' %% N]).cuda()\n"
+        "    for kernel in (4, 6, 2):\n"
+        "        gp = genops.make_gen_params(seqlen=%d, skip_steps=%d, rate_penalty_threshold=1.0, kernel=kernel, **%r)\n"
+        "        if kernel == 4:\n"
+        "            assert genops.forward_variant(%d, %d, 2 * N, gp, save=True) == 7\n"
+        "        out = genops.gen_forward(W, ext, gp, save=True)\n"
+        "        for key in ('time_avg', 'traj', 'df'):\n"
+        "            res['%%s_%%d_%%d' %% (key, kernel, N)] = out[key].cpu().numpy()\n"
+        "        res['pen_%%d_%%d' %% (kernel, N)] = np.array([float(out['dynamics_penalty']), float(out['rate_penalty'])])\n"
+        "np.savez(sys.argv[2], **res)\n" % (root, sizes, T, skip, GEN, B, NB))
+    inputs = {}
+    for N in sizes:
+        jds, z, bws, con = _problem(N, B, NB, 300 + N, T, skip, 1.0)
+        inputs['W%d' % N] = weight_gen.generate_weight_batch(N, jds['J'], jds['D'], jds['S'], z, dtype='float32').cpu().numpy()
+        inputs['ext%d' % N] = stimuli.stimulus_batch(bws, con, P['smoothness'], N, dtype='float32').cpu().numpy()
+    with tempfile.TemporaryDirectory() as tmp:
+        src, dst = os.path.join(tmp, 'in.npz'), os.path.join(tmp, 'out.npz')
+        np.savez(src, **inputs)
+        subprocess.run([sys.executable, '-c', code, src, dst], check=True, env=dict(os.environ, SSN_FWD_WIDE='3'), timeout=300)
+        res = dict(np.load(dst))
+    for N in sizes:
+        for kernel in (4, 6):
+            for key in ('time_avg', 'traj', 'df', 'pen'):
+                tag = '%s: kernel %d, N=%d' % (key, kernel, N)
+                got = res['%s_%d_%d' % (key, kernel, N)].astype('float64')
+                want = res['%s_2_%d' % (key, N)].astype('float64')
+                assert np.isfinite(got).all() and np.isfinite(want).all(), tag
+                for g, w in (zip(got, want) if key == 'pen' else [(got, want)]):      # the two penalties: each to its own size
+                    np.testing.assert_allclose(g, w, rtol=2e-5, atol=3e-6 * np.abs(w).max() + 1e-30, err_msg=tag)
+        assert res['time_avg_4_%d' % N].max() > 0.0
+
+
 def test_two_draw_kernel_half_real_tail_tile_one_value_per_lane_gives_the_same_bits():
     """2N = 194 ... 200: the 13th row tile holds at most 8 real rows and the wave that finishes it takes them one value per
     lane (`v_permlane32_swap`, 7 values per lane instead of 8); `SSN_DUO_HT=0` keeps the row-pair form.  Per value the same
