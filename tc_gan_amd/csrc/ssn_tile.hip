@@ -28,6 +28,7 @@
 // CU) is variant 4.  fp64: 7 rows x C <= 13 up to 2N = 104, 4 rows x C = 19 / 26
 // (one workgroup of 5-7 waves per CU) up to 2N = 208.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "ssn_device.h"
 #include "ssn_host.h"
 #include "ssn_tile_core.h"
@@ -38,6 +39,9 @@
 #endif
 
 namespace ssn {
+
+// LDS words of the stop protocol per stimulus: three rotating slots, or the two verdict words of the fp32 NB = 1 loop
+template <typename T, int NB> constexpr int tile_flag_words() { return (NB == 1 && sizeof(T) == 4 && !SSN_ABLATE) ? 2 : 3; }
 
 // The Euler loop of one wave: its RA x C tile of W (rows rowbase + a of row group rg), the step loop with ONE workgroup
 // barrier per step, the stop protocol and the final stores.  Every wave of a workgroup runs this with the same C, NB
@@ -71,8 +75,8 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     if constexpr (SPLIT) sw.template load<false>(a.W + (size_t)b * M * M, M, rowbase, colbase, wlds, threadIdx.x);
     else tile_load<T, RA, C, false>(a.W + (size_t)b * M * M, M, rowbase, colbase, w);
     // fp32, NB = 1: the step loop below without the NB-generic bookkeeping (FAST1: rotated by half a step so that one test of
-    // the verdict word ends it, rotating flag addresses, a toggled buffer offset) and without exec-mask regions around the
-    // state store, the flag stores and the flag clear (FLAT)
+    // the verdict word ends it, one scalar verdict byte per wave, unrolled by the parity of the state buffer) and without an
+    // exec-mask region around the state store (FLAT)
     constexpr bool FAST1 = NB == 1 && sizeof(T) == 4 && !SSN_ABLATE;
     constexpr bool FLAT = FAST1 && CP > C;      // (C = 4 has no pad float to absorb a dummy store)
     // the row this lane finishes each step (a = cg), its LDS slot, input and state
@@ -93,7 +97,8 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
         ex[s] = (fin && live[s]) ? a.ext[(a.ext_per_draw ? vec : (size_t)(s0 + s) * M) + myrow] : (T)0;
     }
     for (int c = threadIdx.x; c < 2 * NB * 8 * CP; c += blockDim.x) (&rbuf[0][0][0])[c] = (T)0;
-    if (threadIdx.x < 3 * NB) (&flags[0][0])[threadIdx.x] = 0;
+    // (FAST1: two verdict words; this is also what zeroes the bytes of waves that the workgroup does not have)
+    if (threadIdx.x < (FAST1 ? 2 : 3 * NB)) (&flags[0][0])[threadIdx.x] = 0;
     __syncthreads();
     if (fin) {
 #pragma unroll
@@ -116,19 +121,40 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     int step = 0;
     if constexpr (FAST1) {
         using LdsI = __attribute__((address_space(3))) int*;
-        using LdsS = __attribute__((address_space(3))) short*;
+        using LdsB = __attribute__((address_space(3))) unsigned char*;
+        using LdsF = __attribute__((address_space(3))) T*;
         using LdsV = const __attribute__((address_space(3))) void*;
         T* const rb0 = &rbuf[0][0][0];
         constexpr unsigned BUF = 8 * CP;                          // elements per state buffer
-        const unsigned fbase = (unsigned)(size_t)(LdsV)&flags[0][0];
-        // FLAT: lanes with nothing to report store their 1 to a fourth word that nobody reads
-        const unsigned fsink = fbase + 12;
-        // partial sums of one step from the state buffer at element offset boff
-        auto partial_sums = [&](unsigned boff, T (&acc)[1][8]) {
+        // Stop protocol of this loop: one verdict WORD per parity of the state buffer, one BYTE of it per wave.  In step t
+        // every wave ANDs its two compare masks with the mask of its finishing lanes and forms one scalar byte -- bit 0:
+        // some row of this wave is still moving, bit 1: some row hit the rate bound -- which all its lanes store, same
+        // address, same value, to byte `wave` of word t % 2.  A wave overwrites its own byte every step, so there is no
+        // clear, no sink word and no address select; the bytes of waves that do not exist are zeroed once in the prologue.
+        // Two words are enough: the word of step t is written before barrier t, read after barrier t (the load issued
+        // before the FMA block of step t + 1, consumed behind it, before barrier t + 1), and its next write, for step
+        // t + 2, comes after barrier t + 1.  Step t reads state buffer t % 2 and writes the other, so the word follows the
+        // parity of the buffer, and the loop below holds one body per parity: buffer, word and read address are immediate
+        // offsets on VGPRs that are computed here, once.
+        unsigned frd = (unsigned)(size_t)(LdsV)&flags[0][0];      // verdict word of parity 0 (parity 1: + 4)
+        unsigned fwr = frd + (threadIdx.x >> 6);                  // my wave's byte of it
+        asm volatile("" : "+v"(frd), "+v"(fwr));                  // (constants otherwise, moved into a VGPR every step)
+        const unsigned sst = (unsigned)(size_t)(LdsV)(rb0 + myslot);            // my state slot in buffer 0
+        unsigned xav = (unsigned)(size_t)(LdsV)(rb0 + cg * CP);                 // my column group's slab of buffer 0
+        unsigned wav = (unsigned)(size_t)(LdsV)(wlds + threadIdx.x * 4);        // my first LDS-resident W unit
+        // the lanes that finish a row, as a wave mask, and the same for the rate-bound test (none if it is off)
+        const unsigned long long finmask = __builtin_amdgcn_ballot_w64(fin);
+        const unsigned long long hardmask = a.st.check_hard ? finmask : 0ull;
+        // log2 k of the power law in a VGPR for the whole loop (v_fma takes one SGPR operand, and that is n)
+        IoConsts<T> io = a.io;
+        asm volatile("" : "+v"(io.log2k));
+        // partial sums of one step from state buffer PB
+        auto partial_sums = [&](auto pb, T (&acc)[1][8]) {
+            constexpr unsigned boff = decltype(pb)::value * BUF;
 #pragma unroll
             for (int r = 0; r < 8; ++r) acc[0][r] = (T)0;
             if constexpr (SPLIT) {
-                sw.template matvec<1, FMA_MODE>(wlds, threadIdx.x, rb0 + boff, cg, acc);
+                sw.template matvec_at<1, FMA_MODE, (int)boff>(xav, wav, acc);
             } else {
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) {
@@ -144,62 +170,57 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
                 }
             }
         };
-        // reduce, Euler update and stop tests of one step: the new state goes to the OTHER buffer, the tests to the flag
-        // word at byte address fcur, and the word at fnext is cleared for the next step
-        auto update = [&](T (&acc)[1][8], unsigned boff, unsigned fcur, unsigned fnext) {
-            const T u = reduce_rows_to_lane<RA, T, OPAIR>(acc[0], cg);
-            const T r1 = rc[0] + (-rc[0] + io_eval(u + ex[0], a.io)) * eps;
-            const bool moving = abs_t(r1 - rc[0]) >= a.st.atol;
-            const bool beyond = a.st.check_hard && r1 >= a.st.hard_stop;
-            if constexpr (FLAT) {
-                *(LdsS)(size_t)((fin && moving) ? fcur : fsink) = 1;
-                *(LdsS)(size_t)(((fin && beyond) ? fcur : fsink) + 2) = 1;
-                rc[0] = r1;
-                rb0[(boff ^ BUF) + myslot] = rc[0];
-                // Nothing reads slot (step + 1) % 3 between the barrier before this step and the barrier after it (it was
-                // read in step - 1, it is written in step + 1), so any lane may clear it now: all of them do, same address
-                *(LdsI)(size_t)fnext = 0;
-            } else {
-                if (fin) {
-                    if (moving) *(LdsS)(size_t)fcur = 1;
-                    if (beyond) *(LdsS)(size_t)(fcur + 2) = 1;
-                    rc[0] = r1;
-                    rb0[(boff ^ BUF) + myslot] = rc[0];
-                }
-                if (threadIdx.x < NB) *(LdsI)(size_t)fnext = 0;
-            }
-        };
-        // keeps the consumption of the flag word BELOW the FMA block (see the general loop)
+        // keeps the consumption of the verdict word BELOW the FMA block (see the general loop)
         auto verdict = [&](int fl, T (&acc)[1][8]) {
             asm volatile("" : "+v"(fl));
 #pragma unroll
             for (int r = 0; r < RA; ++r) asm volatile("" : "+v"(acc[0][r]));
             return __builtin_amdgcn_readfirstlane(fl);
         };
-        auto stops = [](int fu) { return !(fu & 0xffff) || (fu >> 16); };
+        // go on <=> some wave has a row that is still moving and no wave has a row at the rate bound
+        auto stops = [](int fu) { return !(fu & 0x01010101) || (fu & 0x02020202); };
         int stopword = 1;
-        // The loop rotated by half a step: [update of step k, barrier, flag word of step k, FMA block of step k + 1,
-        // verdict], so that ONE test at the bottom ends it -- on the verdict of the step just taken or at max_iter,
-        // where the FMA block of a step that is never taken is discarded just as after a stop.  The flag slots are
-        // three byte addresses that rotate and the state buffer is an offset that toggles: no step % 3, no multiply.
+        // One step of the loop rotated by half a step, for the parity PAR of the buffer that holds x_k = xc: [reduce, Euler
+        // update and stop tests of step k: the new state xn goes to the OTHER buffer, the wave's verdict to its byte of word
+        // PAR; barrier; verdict word of step k; FMA block of step k + 1; verdict].  Returns "the loop ends here": on the
+        // verdict of the step just taken or at max_iter, where the FMA block of a step that is never taken is discarded
+        // just as after a stop.
+        auto half_step = [&](auto par, const T xc, T& xn, T (&acc)[1][8]) {
+            constexpr unsigned PAR = decltype(par)::value;
+            const T u = reduce_rows_to_lane<RA, T, OPAIR>(acc[0], cg);
+            const T r1 = xc + (-xc + io_eval(u + ex[0], io)) * eps;
+            // the two compares as wave masks (a NaN row counts as not moving), ANDed with the masks of the lanes that report
+            const unsigned long long moving = __builtin_amdgcn_ballot_w64(abs_t(r1 - xc) >= a.st.atol);
+            const unsigned long long beyond = __builtin_amdgcn_ballot_w64(r1 >= a.st.hard_stop);
+            // (Lane counts, 0 .. 64, carried into bit 6: integer arithmetic on uniform values stays on the scalar unit, and
+            // the byte then costs the vector port the one v_mov that the store needs.  Written as two tests of the masks, the
+            // compiler forms it with a vector select and a vector or.)
+            const unsigned nm = __builtin_popcountll(moving & finmask), nb = __builtin_popcountll(beyond & hardmask);
+            const unsigned mine = ((nm + 63u) >> 6) | (((nb + 63u) >> 5) & 2u);
+            *(LdsB)(size_t)(fwr + 4 * PAR) = (unsigned char)mine;
+            if (FLAT || fin) *(LdsF)(size_t)(sst + (unsigned)sizeof(T) * ((PAR ^ 1) * BUF)) = r1;
+            xn = r1;
+            __syncthreads();
+            ++step;
+            const int fl = *(LdsI)(size_t)(frd + 4 * PAR);
+            partial_sums(std::integral_constant<unsigned, (PAR ^ 1)>{}, acc);
+            stopword = verdict(fl, acc);
+            return stops(stopword) || step >= a.st.max_iter;
+        };
+        // Unrolled by two, one body per parity; x_k alternates between two registers (no copy at the loop tail), and which
+        // body ended the loop says which buffer holds the newest state.  x_k and x_{k-1} are read back from the two buffers
+        // behind the loop (every lane reads what it stored itself), so neither body has to leave them in a common register.
         if (a.st.max_iter > 0) {
-            unsigned fcur = fbase, fnext = fbase + 4, fafter = fbase + 8, boff = 0;
             T acc[1][8];
-            partial_sums(boff, acc);
-            do {
-                update(acc, boff, fcur, fnext);
-                __syncthreads();
-                ++step;
-                boff ^= BUF;                                   // 0 <-> BUF
-                const int fl = *(LdsI)(size_t)fcur;
-                const unsigned t = fcur; fcur = fnext; fnext = fafter; fafter = t;
-                partial_sums(boff, acc);
-                stopword = verdict(fl, acc);
-            } while (!stops(stopword) && step < a.st.max_iter);
-            cur = boff != 0;
+            T xe = rc[0], xo;
+            partial_sums(std::integral_constant<unsigned, 0>{}, acc);
+            for (;;) {
+                if (half_step(std::integral_constant<unsigned, 0>{}, xe, xo, acc)) { cur = 1; break; }
+                if (half_step(std::integral_constant<unsigned, 1>{}, xo, xe, acc)) { cur = 0; break; }
+            }
         }
         // code and step count once, from the word that ended the loop
-        if (stops(stopword)) { code[0] = (stopword & 0xffff) ? 2 : 0; nsteps[0] = step; }
+        if (stops(stopword)) { code[0] = (stopword & 0x01010101) ? 2 : 0; nsteps[0] = step; }
     } else
     for (; step < a.st.max_iter; ++step) {
         int fl[NB];
@@ -289,6 +310,7 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     }
     // NB == 1: nothing runs after the stop, so the buffer that was read in the last update still holds x_{k-1}
     if constexpr (NB == 1) { if (step > 0 && fin) rp[0] = rbuf[cur ^ 1][0][myslot]; }
+    if constexpr (FAST1) { if (step > 0 && fin) rc[0] = rbuf[cur][0][myslot]; }
     // verdict of the last executed iteration (no extra step was taken, so no roll-back)
     if (!(SSN_ABLATE & 4) && !FAST1 && step == a.st.max_iter && step > 0) {
 #pragma unroll
@@ -325,7 +347,8 @@ __global__ void __launch_bounds__(MAXTHREADS, MINWAVES) solve_tile_kernel(SolveA
     __shared__ __align__(16) T rbuf[2][NB][8 * CP];
     // per slot and stimulus one 32-bit word: low half = "some row has not converged", high half = "some row hit
     // the rate bound"; written with 16-bit stores (no race between the two kinds), read and cleared as one word
-    __shared__ int flags[(NB == 1 && sizeof(T) == 4) ? 4 : 3][NB];      // (fourth word: sink of the NB = 1 loop)
+    // (the fp32 NB = 1 loop: two words of one verdict byte per wave, see tile_wave_body)
+    __shared__ int flags[tile_flag_words<T, NB>()][NB];
     if constexpr (RL > 0) set_rank_priority((blockIdx.x >> 8) % 3);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     tile_wave_body<T, RA, C, RL, NB, false>(a, wlds, rbuf, flags, (8 * wave + (lane >> 3)) * RA);
@@ -341,7 +364,7 @@ __global__ void __launch_bounds__(64 * NW, MINWAVES) solve_tile_mixed_kernel(Sol
     using Split = TileSplit<7, C, RL>;
     __shared__ __align__(16) T wlds[Split::lds_elems(64 * (NW - 1))];      // heavy waves only
     __shared__ __align__(16) T rbuf[2][NB][8 * CP];
-    __shared__ int flags[(NB == 1 && sizeof(T) == 4) ? 4 : 3][NB];
+    __shared__ int flags[tile_flag_words<T, NB>()][NB];
     set_rank_priority((blockIdx.x >> 8) % 3);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave < NW - 1) tile_wave_body<T, 7, C, RL, NB, false>(a, wlds, rbuf, flags, (8 * wave + (lane >> 3)) * 7);

@@ -450,6 +450,18 @@ template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
     __device__ __forceinline__ void matvec(const T* wl, int tid, const T* xs /* [NB][8*CP] */, int cg,
                                            T (&acc)[NB][8]) const {
         constexpr int CP = SlabPad<C>::value;
+        using LdsT = const __attribute__((address_space(3))) T*;
+        unsigned xa = (unsigned)(size_t)(LdsT)(xs + cg * CP);
+        unsigned wa = (unsigned)(size_t)(LdsT)(wl + tid * 4);
+        matvec_at<NB, MODE, 0>(xa, wa, acc);
+    }
+    // The same on the two LDS byte addresses themselves: xa = the lane's column-group slab of an x image, wa = the lane's
+    // first W unit; x is read at element offset XOFF from xa.  The stage boundaries below "redefine" both addresses, and
+    // they come back as redefined: a caller that keeps them as the state of a loop (the fp32 NB = 1 solver) pays no copy of
+    // a loop-invariant base per call, and selects one of several x images by XOFF, an immediate of the reads.
+    template <int NB, int MODE, int XOFF>
+    __device__ __forceinline__ void matvec_at(unsigned& xa, unsigned& wa, T (&acc)[NB][8]) const {
+        constexpr int CP = SlabPad<C>::value;
         constexpr int NQ = (C + 3) / 4;
         constexpr bool F32ASM = sizeof(T) == 4 && SSN_PK_ASM;
         constexpr bool BLK = F32ASM && (MODE & 1) && NP == 2;
@@ -462,9 +474,6 @@ template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
         // (~80 staging VGPRs).  The tied values are 32-bit LDS byte addresses: tying a generic pointer would
         // lose its address space and turn every ds_read into a flat_load.
         using LdsV4 = const __attribute__((address_space(3))) V4*;
-        using LdsT = const __attribute__((address_space(3))) T*;
-        unsigned xa = (unsigned)(size_t)(LdsT)(xs + cg * CP);
-        unsigned wa = (unsigned)(size_t)(LdsT)(wl + tid * 4);
         V2 a2[NB][NP > 0 ? NP : 1], al2[NB], ao2[NB];     // ao2 (OP): odd row, even columns in .x, odd columns in .y
         T ao[NB], al1[NB];
         if constexpr (!MUL0) {
@@ -478,12 +487,13 @@ template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
         }
         V4 rv[NQ][NB];
         V4 wu[S::NF4 > 0 ? S::NF4 : 1];
-        const V4 stub = {(T)cg, (T)(cg + 1), (T)(cg + 2), (T)(cg + 3)};     // diagnostic builds (SSN_ABLATE) only
+        const int cg = threadIdx.x & 7;
+        const V4 stub = {(T)cg,(T)(cg + 1), (T)(cg + 2), (T)(cg + 3)};     // diagnostic builds (SSN_ABLATE) only
         auto load_quad = [&](int q) {
 #pragma unroll
             for (int s = 0; s < NB; ++s) {
                 if constexpr (SSN_ABLATE & 8) rv[q][s] = stub;
-                else rv[q][s] = *(LdsV4)(size_t)(xa + (unsigned)sizeof(T) * (s * 8 * CP + 4 * q));
+                else rv[q][s] = *(LdsV4)(size_t)(xa + (unsigned)sizeof(T) * (XOFF + s * 8 * CP + 4 * q));
             }
         };
         load_quad(0);
