@@ -25,7 +25,8 @@
 // columns exact).  Default shape: split residency (RL = 2: five rows of every
 // lane's tile in VGPRs as packed pairs, two in LDS), 167 VGPRs, three workgroups
 // per CU; the all-register shape (175 W registers per lane, two workgroups per
-// CU) is variant 4.  fp64: 7 rows x C <= 13 up to 2N = 104, 4 rows x C = 19 / 26
+// CU) is variant 4.  fp32 with one stimulus per draw at 2N = 170..200: rows 56/48/48/48, one 7-row and three 6-row
+// waves (solve_tile_mixed6_kernel).  fp64: 7 rows x C <= 13 up to 2N = 104, 4 rows x C = 19 / 26
 // (one workgroup of 5-7 waves per CU) up to 2N = 208.
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -37,6 +38,10 @@
 #ifndef SSN_TILE_MIXED
 #define SSN_TILE_MIXED 1
 #endif
+// diagnostic switch: columns of a 6-row wave's third row pair that stay in VGPRs (0 = the whole pair in LDS; A/B builds)
+#ifndef SSN_TILE_KV
+#define SSN_TILE_KV 12
+#endif
 
 namespace ssn {
 
@@ -45,10 +50,12 @@ template <typename T, int NB> constexpr int tile_flag_words() { return (NB == 1 
 
 // The Euler loop of one wave: its RA x C tile of W (rows rowbase + a of row group rg), the step loop with ONE workgroup
 // barrier per step, the stop protocol and the final stores.  Every wave of a workgroup runs this with the same C, NB
-// and barrier sequence; RA / RL / PK (row pairs packed for v_pk_fma_f32) may differ between waves (mixed kernel below).
-template <typename T, int RA, int C, int RL, int NB, bool PK>
+// and barrier sequence; RA / RL / PK (row pairs packed for v_pk_fma_f32) may differ between waves (mixed kernels below).
+// wlds, wtid: the LDS image of the tile's LDS-resident rows and this thread's index in it (the workgroup's image and
+// threadIdx.x; with WSO = 64 the wave's own image and the lane).  KV, WSO: see SplitTile.
+template <typename T, int RA, int C, int RL, int NB, bool PK, int KV = -1, int WSO = 0>
 __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T (*rbuf)[NB][8 * SlabPad<C>::value],
-                                               int (*flags)[NB], const int rowbase) {
+                                               int (*flags)[NB], const int rowbase, const int wtid) {
     constexpr int CP = SlabPad<C>::value;
     constexpr int NQ = (C + 3) / 4;              // 16-B reads per lane per stimulus
     static_assert(RA <= 8, "a row group has 8 lanes to finish its rows");
@@ -68,11 +75,15 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     // LDS-resident rows.  They have one form: the odd row in column pairs inside the one-statement FMA block, and a
     // transpose-reduce of their 7 rows that forms no zero row 7.
     constexpr bool OPAIR = SSN_PK_ASM && sizeof(T) == 4 && NB == 1 && !PK && RA == 7 && RL == 2 && C % 4 == 1;
+    // SIXROW: the 6-row waves of solve_tile_mixed6_kernel: two packed row pairs and a third pair split between VGPRs and LDS,
+    // one-statement forms throughout and a transpose-reduce that forms no zero rows 6 and 7
+    constexpr bool SIXROW = KV >= 0;
+    static_assert(!SIXROW || (SSN_PK_ASM && sizeof(T) == 4 && NB == 1 && !PK && RA == 6 && RL == 2), "the 6-row wave is an fp32 NB = 1 form");
     // the FMA block of the solver (SplitTile::matvec's MODE): the first product of every chain is a multiply, and the light
     // wave of the mixed kernel (all rows packed, none in LDS) runs the one-statement form as well
-    constexpr int FMA_MODE = 2 | ((OPAIR || (PK && RL == 0)) ? 1 : 0);
-    SplitTile<T, RA, C, RL, OPAIR> sw;
-    if constexpr (SPLIT) sw.template load<false>(a.W + (size_t)b * M * M, M, rowbase, colbase, wlds, threadIdx.x);
+    constexpr int FMA_MODE = 2 | ((OPAIR || SIXROW || (PK && RL == 0)) ? 1 : 0);
+    SplitTile<T, RA, C, RL, OPAIR, KV, WSO> sw;
+    if constexpr (SPLIT) sw.template load<false>(a.W + (size_t)b * M * M, M, rowbase, colbase, wlds, wtid);
     else tile_load<T, RA, C, false>(a.W + (size_t)b * M * M, M, rowbase, colbase, w);
     // fp32, NB = 1: the step loop below without the NB-generic bookkeeping (FAST1: rotated by half a step so that one test of
     // the verdict word ends it, one scalar verdict byte per wave, unrolled by the parity of the state buffer) and without an
@@ -141,7 +152,7 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
         asm volatile("" : "+v"(frd), "+v"(fwr));                  // (constants otherwise, moved into a VGPR every step)
         const unsigned sst = (unsigned)(size_t)(LdsV)(rb0 + myslot);            // my state slot in buffer 0
         unsigned xav = (unsigned)(size_t)(LdsV)(rb0 + cg * CP);                 // my column group's slab of buffer 0
-        unsigned wav = (unsigned)(size_t)(LdsV)(wlds + threadIdx.x * 4);        // my first LDS-resident W unit
+        unsigned wav = (unsigned)(size_t)(LdsV)(wlds + wtid * 4);               // my first LDS-resident W unit
         // the lanes that finish a row, as a wave mask, and the same for the rate-bound test (none if it is off)
         const unsigned long long finmask = __builtin_amdgcn_ballot_w64(fin);
         const unsigned long long hardmask = a.st.check_hard ? finmask : 0ull;
@@ -187,7 +198,7 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
         // just as after a stop.
         auto half_step = [&](auto par, const T xc, T& xn, T (&acc)[1][8]) {
             constexpr unsigned PAR = decltype(par)::value;
-            const T u = reduce_rows_to_lane<RA, T, OPAIR>(acc[0], cg);
+            const T u = reduce_rows_to_lane<RA, T, OPAIR || SIXROW>(acc[0], cg);
             const T r1 = xc + (-xc + io_eval(u + ex[0], io)) * eps;
             // the two compares as wave masks (a NaN row counts as not moving), ANDed with the masks of the lanes that report
             const unsigned long long moving = __builtin_amdgcn_ballot_w64(abs_t(r1 - xc) >= a.st.atol);
@@ -235,7 +246,7 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
 #pragma unroll
             for (int r = 0; r < 8; ++r) acc[s][r] = (T)0;
         if constexpr (SPLIT) {
-            sw.template matvec<NB, FMA_MODE>(wlds, threadIdx.x, &rbuf[cur][0][0], cg, acc);
+            sw.template matvec<NB, FMA_MODE>(wlds, wtid, &rbuf[cur][0][0], cg, acc);
         } else {
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
@@ -351,13 +362,14 @@ __global__ void __launch_bounds__(MAXTHREADS, MINWAVES) solve_tile_kernel(SolveA
     __shared__ int flags[tile_flag_words<T, NB>()][NB];
     if constexpr (RL > 0) set_rank_priority((blockIdx.x >> 8) % 3);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    tile_wave_body<T, RA, C, RL, NB, false>(a, wlds, rbuf, flags, (8 * wave + (lane >> 3)) * RA);
+    tile_wave_body<T, RA, C, RL, NB, false>(a, wlds, rbuf, flags, (8 * wave + (lane >> 3)) * RA, threadIdx.x);
 }
 
 // Split shapes whose LAST wave is left with at most 40 rows (2N = 170..200 at C = 25: waves 0-2 own 56 rows each, 32 remain;
 // 2N = 114..152 at C = 19: 40 remain): that wave runs an LRA-row tile (LRA = 4 or 5), all in VGPRs as packed row pairs --
 // 50 (or 57) FMA instructions per step instead of 100 (76) on a 7-row tile that is mostly padding, and no LDS-resident
 // rows to re-read.  Same barriers, same stop protocol, same results.
+// (One stimulus per draw at C = 25 runs solve_tile_mixed6_kernel below; this kernel at C = 25 is left with NB > 1.)
 template <typename T, int C, int RL, int NW, int LRA, int NB, int MINWAVES>
 __global__ void __launch_bounds__(64 * NW, MINWAVES) solve_tile_mixed_kernel(SolveArgs<T> a) {
     constexpr int CP = SlabPad<C>::value;
@@ -367,8 +379,32 @@ __global__ void __launch_bounds__(64 * NW, MINWAVES) solve_tile_mixed_kernel(Sol
     __shared__ int flags[tile_flag_words<T, NB>()][NB];
     set_rank_priority((blockIdx.x >> 8) % 3);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (wave < NW - 1) tile_wave_body<T, 7, C, RL, NB, false>(a, wlds, rbuf, flags, (8 * wave + (lane >> 3)) * 7);
-    else tile_wave_body<T, LRA, C, 0, NB, true>(a, wlds, rbuf, flags, 56 * (NW - 1) + (lane >> 3) * LRA);
+    if (wave < NW - 1) tile_wave_body<T, 7, C, RL, NB, false>(a, wlds, rbuf, flags, (8 * wave + (lane >> 3)) * 7, threadIdx.x);
+    else tile_wave_body<T, LRA, C, 0, NB, true>(a, wlds, rbuf, flags, 56 * (NW - 1) + (lane >> 3) * LRA, threadIdx.x);
+}
+
+// 2N = 170..200 (C = 25, four waves): rows split 56/48/48/48.  Wave 0 runs the 7-row tile of the heavy waves above, waves 1-3 a
+// 6-row tile of three packed row pairs and no odd row; the third pair's columns 0 .. KV - 1 stay in VGPRs (a 6-row wave has the
+// registers: 100 + 2 KV against the 7-row wave's 125), the rest in LDS, so a 6-row wave re-reads 7 W units per step and not 13.
+// Every wave has an LDS image of its own (64 lanes per unit).  The hardware places a workgroup's waves on the SIMDs in the cyclic
+// order 0, 2, 1, 3 from a start that advances with every workgroup of the CU (tools/microbench/wave_placement.hip), so the
+// 7-row waves of the three workgroups that share a CU sit on three different SIMDs: the fullest SIMD carries one 7-row and two
+// 6-row waves, where 56/56/56/32 always leaves one SIMD with three 7-row waves.
+template <typename T, int C, int KV, int NB, int MINWAVES>
+__global__ void __launch_bounds__(256, MINWAVES) solve_tile_mixed6_kernel(SolveArgs<T> a) {
+    constexpr int CP = SlabPad<C>::value;
+    using Heavy = SplitTile<T, 7, C, 2, true, -1, 64>;
+    using Six = SplitTile<T, 6, C, 2, false, KV, 64>;
+    constexpr int HEAVY_ELEMS = Heavy::lds_elems(64), SIX_ELEMS = Six::lds_elems(64);
+    static_assert(HEAVY_ELEMS % 4 == 0 && SIX_ELEMS % 4 == 0, "16-byte units");
+    __shared__ __align__(16) T wlds[HEAVY_ELEMS + 3 * SIX_ELEMS];
+    __shared__ __align__(16) T rbuf[2][NB][8 * CP];
+    __shared__ int flags[tile_flag_words<T, NB>()][NB];
+    set_rank_priority((blockIdx.x >> 8) % 3);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wave == 0) tile_wave_body<T, 7, C, 2, NB, false, -1, 64>(a, wlds, rbuf, flags, (lane >> 3) * 7, lane);
+    else tile_wave_body<T, 6, C, 2, NB, false, KV, 64>(a, wlds + HEAVY_ELEMS + (wave - 1) * SIX_ELEMS, rbuf, flags,
+                                                       56 + 48 * (wave - 1) + (lane >> 3) * 6, lane);
 }
 
 // ---------------------------------------------------------------------------------
@@ -378,6 +414,8 @@ __global__ void __launch_bounds__(64 * NW, MINWAVES) solve_tile_mixed_kernel(Sol
 // "reg" = whole tile in VGPRs (2 waves/SIMD at C >= 19).  fp64: all-register only.
 // ---------------------------------------------------------------------------------
 static constexpr int TILE_RA = 7;
+// fp32, NB = 1, C = 25: the smallest 2N that runs rows 56/48/48/48 (solve_tile_mixed6_kernel): every size with four waves
+static constexpr int TILE_MIXED6_MIN_M = 170;
 
 static int tile_pick_c(int M, int elem_bytes) {
     const int need = (M + 7) / 8;
@@ -409,6 +447,10 @@ static hipError_t launch_tile_nb(const SolveArgs<T>& a, hipStream_t st, bool spl
         // split shapes; when the last wave is left with <= 40 rows it gets a lighter tile (mixed kernel)
         const int waves = (a.M + 55) / 56, last_rows = a.M - 56 * (waves - 1);
         if constexpr (C == 25) {                                                      // (C = 26 spills in the loop)
+            if (SSN_TILE_MIXED && split && a.NB == 1 && a.M >= TILE_MIXED6_MIN_M) {
+                hipLaunchKernelGGL((solve_tile_mixed6_kernel<T, C, SSN_TILE_KV, 1, 3>), dim3(a.B), dim3(256), 0, st, a);
+                return hipGetLastError();
+            }
             if (SSN_TILE_MIXED && split && waves == 4 && last_rows <= 32) {
                 hipLaunchKernelGGL((solve_tile_mixed_kernel<T, C, 2, 4, 4, 1, 3>), dim3(a.B * a.NB), dim3(256), 0, st, a);
                 return hipGetLastError();

@@ -89,21 +89,24 @@ __device__ __forceinline__ T reduce8_to_lane(const T (&acc)[8], int cg) {
 // fp32: the first exchange without selects.  Bit 2 of the lane index (= bit 2 of cg) is a DPP bank boundary, so the
 // two halves are formed by two v_add_f32_dpp, the second one writing only the lanes that keep rows 4..7
 // (bank_mask 0xa = lanes 4-7 and 12-15 of every row of 16): 8 instructions instead of 12 for this stage.
-// ROW7 = false: the tile has 7 rows and acc[7] is not read.  Lanes 4-7 then keep, in n4[3], the sum of their own and
+// ROWS = 7: the tile has 7 rows and acc[7] is not read.  Lanes 4-7 then keep, in n4[3], the sum of their own and
 // their mirror lane's partial sums of row 3 where row 7 would stand.  The second exchange sends it from lanes 4, 5 to
 // lanes 6, 7, which add it to their own as n2[1], and the third leaves lane 6 with n2[0] (row 6, from both) and lane 7
 // with n2[1]: lane cg = 7 of every row group is the only lane whose result has that value in it, and with 7 rows per
 // row group it finishes no row (fin = cg < RA).  Lanes 0-6 hold the same bits as with a zero row.
+// ROWS = 6: the same with two masked adds (rows 4 and 5).  Lanes 4-7 then keep sums of rows 2 and 3 where rows 6 and 7 would
+// stand; the second exchange leaves them in lanes 6 and 7 only, which finish no row: lanes 0-5 hold the bits of two zero rows.
 #ifndef SSN_REDUCE_PLAIN
-template <bool ROW7>
+template <int ROWS>
 __device__ __forceinline__ float reduce8_f32(const float (&acc)[8], int cg) {
+    static_assert(ROWS >= 6 && ROWS <= 8, "8 rows, or 7 or 6 rows without zero rows");
     const bool bB = cg & 2, bC = cg & 1;
     float n4[4], n2[2];
     // A DPP read of a VGPR needs two wait states after the VALU write of that VGPR and the hardware does not
     // interlock; the compiler inserts them for its own DPP instructions but cannot see into inline asm.  One s_nop
     // that "redefines" all eight inputs puts every producing FMA in front of it, and with it two wait states in front
     // of every DPP read below.
-    if constexpr (ROW7) {
+    if constexpr (ROWS == 8) {
         float a0 = acc[0], a1 = acc[1], a2 = acc[2], a3 = acc[3], a4 = acc[4], a5 = acc[5], a6 = acc[6], a7 = acc[7];
         asm volatile("s_nop 1" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7));
         const float lo[4] = {a0, a1, a2, a3}, hi[4] = {a4, a5, a6, a7};
@@ -120,10 +123,16 @@ __device__ __forceinline__ float reduce8_f32(const float (&acc)[8], int cg) {
         // put between two statements (they read rows 4-6, written long before, and only write n4).
 #define SSN_DPP_FULL(r, a) "v_add_f32_dpp %[" r "], %[" a "], %[" a "] row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
 #define SSN_DPP_HIGH(r, a) "v_add_f32_dpp %[" r "], %[" a "], %[" a "] row_half_mirror row_mask:0xf bank_mask:0xa\n"
+        if constexpr (ROWS == 7)
         asm("s_nop 1\n" SSN_DPP_FULL("r0", "a0") SSN_DPP_FULL("r1", "a1") SSN_DPP_FULL("r2", "a2") SSN_DPP_FULL("r3", "a3")
             SSN_DPP_HIGH("r0", "a4") SSN_DPP_HIGH("r1", "a5") SSN_DPP_HIGH("r2", "a6")
             : [r0] "=&v"(n4[0]), [r1] "=&v"(n4[1]), [r2] "=&v"(n4[2]), [r3] "=&v"(n4[3])
             : [a0] "v"(acc[0]), [a1] "v"(acc[1]), [a2] "v"(acc[2]), [a3] "v"(acc[3]), [a4] "v"(acc[4]), [a5] "v"(acc[5]), [a6] "v"(acc[6]));
+        else
+        asm("s_nop 1\n" SSN_DPP_FULL("r0", "a0") SSN_DPP_FULL("r1", "a1") SSN_DPP_FULL("r2", "a2") SSN_DPP_FULL("r3", "a3")
+            SSN_DPP_HIGH("r0", "a4") SSN_DPP_HIGH("r1", "a5")
+            : [r0] "=&v"(n4[0]), [r1] "=&v"(n4[1]), [r2] "=&v"(n4[2]), [r3] "=&v"(n4[3])
+            : [a0] "v"(acc[0]), [a1] "v"(acc[1]), [a2] "v"(acc[2]), [a3] "v"(acc[3]), [a4] "v"(acc[4]), [a5] "v"(acc[5]));
 #undef SSN_DPP_FULL
 #undef SSN_DPP_HIGH
     }
@@ -138,16 +147,16 @@ __device__ __forceinline__ float reduce8_f32(const float (&acc)[8], int cg) {
     return keep + dpp_get_f<0xB1>(send);                // quad_perm:[1,0,3,2]: lane i <-> i^1
 }
 template <>
-__device__ __forceinline__ float reduce8_to_lane<float>(const float (&acc)[8], int cg) { return reduce8_f32<true>(acc, cg); }
+__device__ __forceinline__ float reduce8_to_lane<float>(const float (&acc)[8], int cg) { return reduce8_f32<8>(acc, cg); }
 #endif
 
 // Tiles of at most 4 rows (acc[4..7] == 0): the first exchange only has to fold the two halves of the lane group
 // together -- four DPP adds, no second masked add, no zero inputs to materialise; lanes 0-3 end with rows 0-3.
-// TRIM (fp32 tiles of 7 rows): no zero row 7 is formed and folded in; lane cg = 7 ends with a value nobody may use.
+// TRIM (fp32 tiles of 7 or 6 rows): no zero rows are formed and folded in; lanes cg >= ROWS end with values nobody may use.
 template <int ROWS, typename T, bool TRIM = false>
 __device__ __forceinline__ T reduce_rows_to_lane(const T (&acc)[8], int cg) {
 #ifndef SSN_REDUCE_PLAIN
-    if constexpr (TRIM && ROWS == 7 && sizeof(T) == 4) return reduce8_f32<false>(acc, cg);
+    if constexpr (TRIM && (ROWS == 7 || ROWS == 6) && sizeof(T) == 4) return reduce8_f32<ROWS>(acc, cg);
 #endif
     if constexpr (ROWS > 4 || sizeof(T) != 4 || !SSN_REDUCE4) {
         return reduce8_to_lane(acc, cg);
@@ -281,15 +290,31 @@ template <int RA, int C, int RL> struct TileSplit {
 // OP (fp32 solver, C = 4k + 1): the odd row is held as PAIRS of columns, (o[c], o[c+1]) for even c, which is how the
 // 16-byte read leaves r: one plain v_pk_fma_f32 per two columns into a two-float accumulator (even columns in one half,
 // odd columns in the other), column C - 1 with one FMA into the low half, the row's partial sum = low + high.
-template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
+// KV >= 0 (fp32 solver, tiles of two register row pairs and one LDS-resident pair, 6 rows): the one-statement forms for a tile
+// without an odd row, and columns [0, KV) of the LDS-resident pair held in VGPRs as well (KV a multiple of 4: whole quads).
+// The LDS image then holds columns KV .. C - 1 only.
+// WSO: lanes per unit of the LDS image when it is not the TileSplit's (an image of one wave: 64, tid = the lane).
+template <typename T, int RA, int C, int RL, bool OP = false, int KV = -1, int WSO = 0> struct SplitTile {
     using S = TileSplit<RA, C, RL>;
     static constexpr int RR = S::RR, NP = RR / 2, ODD = RR % 2;
     static_assert(!OP || (sizeof(T) == 4 && ODD && NP == 2 && C % 4 == 1 && C >= 5), "odd row in column pairs: 5 register rows, whole quads + one column");
+    static constexpr bool SIX = KV >= 0;
+    static constexpr int KR = SIX ? KV : 0;                       // columns of the LDS-resident rows that stay in VGPRs
+    static_assert(!SIX || (sizeof(T) == 4 && !OP && !ODD && NP == 2 && RL == 2 && KV % 4 == 0 && KV < C), "two register row pairs + one split pair");
+    static constexpr int WS = WSO ? WSO : S::WS;
+    static constexpr int NLV = RL * (C - KR), NU = (NLV + 3) / 4; // values and units of the LDS image per lane
+    // KV = 0: a half-empty last unit is stored and read as 8 bytes, lanes 8 bytes apart (four whole images of 13 x 16 bytes
+    // per lane do not fit three workgroups per CU); it costs one more address VGPR, which the tile with KV = 12 does not have
+    static constexpr bool HALF = SIX && KV == 0 && NLV % 4 == 2;
+    static constexpr int NUF = NU - (HALF ? 1 : 0);
+    static constexpr int lds_elems(int wg) { return NU == 0 ? 4 : HALF ? NUF * WS * 4 + wg * 2 : ((NU - 1) * WS + wg) * 4; }
     using V2 = T __attribute__((ext_vector_type(2)));
     using V4 = T __attribute__((ext_vector_type(4)));
     V2 p[NP > 0 ? NP : 1][C];      // p[k][c] = (W[row 2k][c], W[row 2k+1][c])
     T o[ODD && !OP ? C : 1];       // last register row when RR is odd (OP: its last column only)
     V2 oc[OP ? C / 2 : 1];         // OP: oc[j] = (W[odd row][2j], W[odd row][2j+1])
+    V2 pv[KR > 0 ? KR : 1];        // KV: pv[c] = (W[row RR][c], W[row RR+1][c]), c < KV
+    unsigned wh;                   // HALF: LDS byte address of the image + 8 * tid (the 8-byte units lie 8 bytes apart)
 
     template <bool TRANSPOSED>
     __device__ __forceinline__ void load(const T* A, int M, int rowbase, int colbase, T* wl, int tid) {
@@ -322,21 +347,32 @@ template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
 #pragma unroll
             for (int c = 0; c < C; ++c) t[c] = (row < M && c < ncol) ? t[c] : (T)0;
         };
+        using LdsT = const __attribute__((address_space(3))) T*;
+        if constexpr (HALF) wh = (unsigned)(size_t)(LdsT)(wl + tid * 2);
         // LDS rows first, fenced off from the register rows (fewer values in flight at once)
-        if (RL > 0 && tid < S::WS) {
+        if (RL > 0 && tid < WS) {
             T t[RL > 0 ? RL : 1][C];
 #pragma unroll
             for (int rl = 0; rl < RL; ++rl) fetch_row(rowbase + RR + rl, t[rl]);
 #pragma unroll
-            for (int k = 0; k < S::NF4; ++k) {
+            for (int k = 0; k < NU; ++k) {
                 T v[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const int j = 4 * k + e, c = j / (RL > 0 ? RL : 1), rl = j % (RL > 0 ? RL : 1);
-                    v[e] = (j < S::NL) ? t[rl][c] : (T)0;
+                    const int j = 4 * k + e, c = KR + j / (RL > 0 ? RL : 1), rl = j % (RL > 0 ? RL : 1);
+                    v[e] = (j < NLV) ? t[rl][c] : (T)0;
                 }
-                V4 q; q.x = v[0]; q.y = v[1]; q.z = v[2]; q.w = v[3];
-                *reinterpret_cast<V4*>(&wl[((size_t)k * S::WS + tid) * 4]) = q;
+                if (HALF && k == NU - 1) {
+                    V2 q; q.x = v[0]; q.y = v[1];
+                    *reinterpret_cast<V2*>(&wl[(size_t)NUF * WS * 4 + tid * 2]) = q;
+                } else {
+                    V4 q; q.x = v[0]; q.y = v[1]; q.z = v[2]; q.w = v[3];
+                    *reinterpret_cast<V4*>(&wl[((size_t)k * WS + tid) * 4]) = q;
+                }
+            }
+            if constexpr (KR > 0) {        // (tid < WS holds for every lane of an image with columns in VGPRs)
+#pragma unroll
+                for (int c = 0; c < KR; ++c) { pv[c].x = t[0][c]; pv[c].y = t[1][c]; }
             }
         }
         asm volatile("" ::: "memory");
@@ -432,6 +468,19 @@ template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
             asm(SSN_PK_LO("a0", "u0", "rl") SSN_PK_HI("a0", "u1", "rl") SSN_PK_LO("a0", "u2", "rh") SSN_PK_HI("a0", "u3", "rh")
                 : [a0] "+v"(al) : [rl] "v"(rlo), [rh] "v"(rhi), [u0] "v"(u0), [u1] "v"(u1), [u2] "v"(u2), [u3] "v"(u3));
     }
+    // KV: one whole quad of columns of all three row pairs from VGPRs, as one statement: three chains, no two consecutive
+    // instructions on one accumulator.
+    template <bool MUL>
+    static __device__ __forceinline__ void pk3_block(V2& a0, V2& a1, V2& a2, const V2* w0, const V2* w1, const V2* w2,
+                                                     const V2& rlo, const V2& rhi) {
+#define SSN_PK3_TAIL SSN_PK_COL1 SSN_PK_HI("a2", "x1", "rl") SSN_PK_COL2 SSN_PK_LO("a2", "x2", "rh") SSN_PK_COL3 SSN_PK_HI("a2", "x3", "rh")
+#define SSN_PK3_IN [rl] "v"(rlo), [rh] "v"(rhi), [u0] "v"(w0[0]), [u1] "v"(w0[1]), [u2] "v"(w0[2]), [u3] "v"(w0[3]), [v0] "v"(w1[0]), \
+                   [v1] "v"(w1[1]), [v2] "v"(w1[2]), [v3] "v"(w1[3]), [x0] "v"(w2[0]), [x1] "v"(w2[1]), [x2] "v"(w2[2]), [x3] "v"(w2[3])
+        if constexpr (MUL) asm(SSN_PK_COL0M SSN_PK_MUL("a2", "x0", "rl") SSN_PK3_TAIL : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2) : SSN_PK3_IN);
+        else asm(SSN_PK_COL0 SSN_PK_LO("a2", "x0", "rl") SSN_PK3_TAIL : [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2) : SSN_PK3_IN);
+#undef SSN_PK3_IN
+#undef SSN_PK3_TAIL
+    }
 #undef SSN_PK_STMT_ODD
 #undef SSN_PK_STMT
 #undef SSN_PK_IN
@@ -467,6 +516,9 @@ template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
         constexpr bool BLK = F32ASM && (MODE & 1) && NP == 2;
         constexpr bool MUL0 = F32ASM && (MODE & 2);
         static_assert(!OP || BLK, "the odd row in column pairs lives in the one-statement block");
+        static_assert(!SIX || (BLK && NB == 1), "the 6-row forms are the fp32 NB = 1 solver's");
+        using LdsV2 = const __attribute__((address_space(3))) V2*;
+        constexpr int QV = KR / 4;                            // quads of the split pair that come from VGPRs
         // Stage boundaries are enforced with data dependencies (an empty asm that "redefines" the LDS
         // addresses and the accumulators): the reads of stage q+1 cannot be hoisted above it, the FMAs of
         // stage q cannot sink below it.  __builtin_amdgcn_sched_barrier alone is not enough -- instruction
@@ -486,7 +538,7 @@ template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
             }
         }
         V4 rv[NQ][NB];
-        V4 wu[S::NF4 > 0 ? S::NF4 : 1];
+        V4 wu[NU > 0 ? NU : 1];
         const int cg = threadIdx.x & 7;
         const V4 stub = {(T)cg,(T)(cg + 1), (T)(cg + 2), (T)(cg + 3)};     // diagnostic builds (SSN_ABLATE) only
         auto load_quad = [&](int q) {
@@ -501,11 +553,15 @@ template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
         for (int q = 0; q < NQ; ++q) {
             if (q + 1 < NQ) load_quad(q + 1);
 #pragma unroll
-            for (int uu = 0; uu < RL; ++uu) {                         // values 4*q*RL .. 4*(q+1)*RL - 1
-                const int k = q * RL + uu;
-                if (k < S::NF4) {
+            for (int uu = 0; uu < RL; ++uu) {                         // values 4*q*RL .. 4*(q+1)*RL - 1 (KV: of the image)
+                const int k = (q - QV) * RL + uu;
+                if (k >= 0 && k < NU) {
                     if constexpr (SSN_ABLATE & 32) wu[k] = stub;
-                    else wu[k] = *(LdsV4)(size_t)(wa + (unsigned)sizeof(T) * (k * S::WS * 4));
+                    else if (HALF && k == NU - 1) {
+                        // the 8-byte unit, behind the 16-byte ones
+                        const V2 h = *(LdsV2)(size_t)(wh + (unsigned)sizeof(T) * (NUF * WS * 4));
+                        wu[k].x = h.x; wu[k].y = h.y;
+                    } else wu[k] = *(LdsV4)(size_t)(wa + (unsigned)sizeof(T) * (k * WS * 4));
                 }
             }
 #pragma unroll
@@ -530,7 +586,28 @@ template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
                         acc = __builtin_elementwise_fma(w2, (V2){rr[e], rr[e]}, acc);
                     }
                 };
-                if constexpr (BLK) {
+                if constexpr (SIX) {
+                    // whole quads below KV: three register chains; then the two register pairs with the split pair's
+                    // accumulator tied behind them, and the split pair from its two W units (the last column: from the half-filled one)
+                    const int nc = C - 4 * q < 4 ? C - 4 * q : 4;
+                    const V2 *w0 = &p[0][4 * q], *w1 = &p[1][4 * q];
+                    V2 &x0 = a2[s][0], &x1 = a2[s][1], &xo = ao2[s], &t = al2[s];
+                    const bool first = MUL0 && q == 0;
+                    if (q < QV) {
+                        if (first) pk3_block<true>(x0, x1, t, w0, w1, &pv[KR > 0 ? 4 * q : 0], rlo, rhi);
+                        else pk3_block<false>(x0, x1, t, w0, w1, &pv[KR > 0 ? 4 * q : 0], rlo, rhi);
+                    } else {
+                        const int k = (q - QV) * 2;
+                        if (nc == 4) {
+                            if (first) { pk_block<4, true, false>(x0, x1, xo, t, w0, w1, w0, rlo, rhi); lds_block<true>(t, wu[k], wu[k + 1], rlo, rhi); }
+                            else { pk_block<4, false, true>(x0, x1, xo, t, w0, w1, w0, rlo, rhi); lds_block<false>(t, wu[k], wu[k + 1], rlo, rhi); }
+                        } else {
+                            static_assert(C % 4 == 1 && 4 * QV + 4 <= C, "whole quads and one last column, behind at least one quad from LDS");
+                            pk_block<1, false, true>(x0, x1, xo, t, w0, w1, w0, rlo, rhi);
+                            pk_bcast(t, (V2){wu[k].x, wu[k].y}, 0);
+                        }
+                    }
+                } else if constexpr (BLK) {
                     // (q is a constant once the loop is unrolled; the other branches fold away.  In the first quad
                     // under MUL0 the accumulator of the LDS-resident rows does not exist yet: no tie there.)
                     const int nc = C - 4 * q < 4 ? C - 4 * q : 4;
@@ -571,7 +648,7 @@ template <typename T, int RA, int C, int RL, bool OP = false> struct SplitTile {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int c = 4 * q + e;
-                    if (c < C && !(OP && RL == 2 && C - 4 * q >= 4)) {
+                    if (c < C && !SIX && !(OP && RL == 2 && C - 4 * q >= 4)) {
                         if constexpr (RL == 2) {
                             const int j = c * 2;
                             const V2 wp = {wu[j / 4][j % 4], wu[j / 4][j % 4 + 1]};

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """HIP-event timing of the fp32 fixed-point solver kernels at the C2 shape with 8 stimuli per draw (2N = 200, 4096 draws,
-2000 steps, atol = 0) for a list of variants.  usage: tools/time_solver.py [variant ...] [--draws B]"""
+2000 steps, atol = 0) for a list of variants.  usage: tools/time_solver.py [variant ...] [--draws B] [--size 2N] [--nb NB]"""
 import os
 import sys
 
@@ -13,9 +13,11 @@ from tc_gan_amd import ssnode  # noqa: E402
 
 def main():
     args = sys.argv[1:]
-    B = int(args[args.index('--draws') + 1]) if '--draws' in args else 4096
-    variants = [int(a) for i, a in enumerate(args) if a.isdigit() and (i == 0 or args[i - 1] != '--draws')] or [6, 8]
-    NB, M, T = 8, 200, 2000
+    def opt(name, default):
+        return int(args[args.index(name) + 1]) if name in args else default
+
+    B, M, NB, T = opt('--draws', 4096), opt('--size', 200), opt('--nb', 8), 2000
+    variants = [int(a) for i, a in enumerate(args) if a.isdigit() and (i == 0 or not args[i - 1].startswith('--'))] or [6, 8]
     g = torch.Generator(device='cuda'); g.manual_seed(1)
     W = (torch.rand((B, M, M), device='cuda', generator=g) - 0.6) * 0.02
     ext = torch.rand((NB, M), device='cuda', generator=g) * 20
