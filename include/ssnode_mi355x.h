@@ -469,7 +469,9 @@ typedef struct ssn_ff_params {
 } ssn_ff_params;
 /* out[nsam][ni][nhid] = relu(sum_g e w / sum_g e - thr).  RF_w [nsam][G], FF_con/FF_str [nsam][nhid][G],
  * TH_sam [nsam][nhid], stim [ni][3] (ni <= 32), all device fp32.  q, den [nsam][ni][nhid] optional (NULL):
- * pre-threshold drive and sum_g e, kept for the backward. */
+ * pre-threshold drive and sum_g e, kept for the backward.  When box^3 % 4 == 0 the kernels read RF_w, FF_con and FF_str with
+ * 16-byte loads: the three pointers must then be 16-byte aligned, and the call is refused with the invalid-argument status
+ * (nothing is launched) when one is not.  The connection-list entry points below take any 4-byte aligned pointers. */
 int ssn_ff_forward_f32(const float *RF_w, const float *FF_con, const float *FF_str, const float *TH_sam,
                        const float *stim, float *out, float *q, float *den, const ssn_ff_params *p, void *stream);
 /* The same outputs from the model's own data structure: a unit has box^3 / 100 connections (FF_lalazar_model.py:154-167), so
@@ -484,7 +486,8 @@ int ssn_ff_backward_sparse_f32(const float *RF_w, const int *conn_idx, const flo
                                const float *q, const float *den, const float *gq, float *dsig, const ssn_ff_params *p,
                                void *stream);
 /* dsig[nsam][nhid][2] = per-sample partial derivatives of L w.r.t. RF_l and RF_d, given gq[nsam][ni][nhid] =
- * dL/d(drive) (upstream gradient times [out > 0]) and the forward's q, den. */
+ * dL/d(drive) (upstream gradient times [out > 0]) and the forward's q, den.  RF_w, FF_con, FF_str: the alignment contract of
+ * ssn_ff_forward_f32 (16-byte aligned when box^3 % 4 == 0, refused otherwise). */
 int ssn_ff_backward_f32(const float *RF_w, const float *FF_con, const float *FF_str, const float *stim,
                         const float *q, const float *den, const float *gq, float *dsig,
                         const ssn_ff_params *p, void *stream);

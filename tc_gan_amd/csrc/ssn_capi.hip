@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -980,6 +981,12 @@ static bool ff_lattice(const float* stim, int ni, ssn::FFLattice& lat, void* str
         lattice = hs[i][0] == lat.x[i / 9] && hs[i][1] == lat.y[(i / 3) % 3] && hs[i][2] == lat.z[i % 3];
     return lattice;
 }
+// The dense kernels read RF_w, FF_con, FF_str with 16-byte loads whenever box^3 % 4 == 0 (a sample's and a unit's rows then
+// start at multiples of 16 bytes from the base): the bases must be 16-byte aligned.  Decided on the host, before any launch.
+static bool ff_dense_aligned(const ssn_ff_params& p, const float* RF_w, const float* FF_con, const float* FF_str) {
+    if (((long long)p.box * p.box * p.box) % 4 != 0) return true;
+    return (((uintptr_t)RF_w | (uintptr_t)FF_con | (uintptr_t)FF_str) % 16) == 0;
+}
 int ssn_ff_forward_sparse_f32(const float* RF_w, const int* conn_idx, const float* conn_str, int ncon, const float* TH_sam,
                               const float* stim, float* out, float* q, float* den, const ssn_ff_params* p, void* stream) {
     if (!p || p->nsam < 0 || p->nhid < 1 || p->ni < 1 || p->ni > 32 || p->box < 1 || ncon < 0 || (q == nullptr) != (den == nullptr) ||
@@ -1012,6 +1019,10 @@ int ssn_ff_forward_f32(const float* RF_w, const float* FF_con, const float* FF_s
         g_last_error = "ssn_ff_forward: invalid argument";
         return SSN_ERR_BASE + (int)hipErrorInvalidValue;
     }
+    if (!ff_dense_aligned(*p, RF_w, FF_con, FF_str)) {
+        g_last_error = "ssn_ff_forward: RF_w, FF_con, FF_str must be 16-byte aligned when box^3 % 4 == 0";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
     ssn::FFArgs a = ff_args(*p);
     a.RF_w = RF_w; a.FF_con = FF_con; a.FF_str = FF_str; a.TH_sam = TH_sam; a.stim = stim; a.out = out; a.q = q; a.den = den;
     ssn::FFLattice lat;
@@ -1023,6 +1034,10 @@ int ssn_ff_backward_f32(const float* RF_w, const float* FF_con, const float* FF_
                         const float* den, const float* gq, float* dsig, const ssn_ff_params* p, void* stream) {
     if (!p || p->nsam < 0 || p->nhid < 1 || p->ni < 1 || p->ni > 32 || p->box < 1 || !q || !den || !gq || !dsig) {
         g_last_error = "ssn_ff_backward: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if (!ff_dense_aligned(*p, RF_w, FF_con, FF_str)) {      // (the same contract as the forward whose tensors it takes)
+        g_last_error = "ssn_ff_backward: RF_w, FF_con, FF_str must be 16-byte aligned when box^3 % 4 == 0";
         return SSN_ERR_BASE + (int)hipErrorInvalidValue;
     }
     ssn::FFArgs a = ff_args(*p);

@@ -38,7 +38,10 @@ def generate_samples(rng, nsam, box_width, nhid=1, device=None):
 
 
 def _f32(t):
-    return torch.as_tensor(t).to('cuda', torch.float32).contiguous()
+    """Contiguous float32 on the device, in 16-byte aligned storage (the dense kernels load 16 bytes at a time; a view into
+    a larger tensor may start anywhere, a fresh allocation is aligned)."""
+    t = torch.as_tensor(t).to('cuda', torch.float32).contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
 
 
 def _params(p, nsam, nhid, ni, box):
