@@ -955,11 +955,6 @@ static bool duo_half_tail_on() {
     static const bool on = [] { const char* e = getenv("SSN_DUO_HT"); return !(e && e[0] == '0'); }();
     return on;
 }
-static int duo_pick_mk(int M) {
-    const int ladder[] = {104, 152, 208};
-    for (int mk : ladder) if (M <= mk) return mk;
-    return 0;
-}
 
 template <int MK, bool HT>
 static hipError_t launch_duo_fwd_ht(const GenFwdArgs<float>& a, int rshift, hipStream_t st) {
@@ -974,58 +969,39 @@ static hipError_t launch_duo_fwd_ht(const GenFwdArgs<float>& a, int rshift, hipS
     }
     return hipGetLastError();
 }
-template <int MK>
-static hipError_t launch_duo_fwd_mk(const GenFwdArgs<float>& a, int rshift, hipStream_t st) {
-    if constexpr (MK == 208) {
-        if (duo_half_tail(MK, a.M) && duo_half_tail_on()) return launch_duo_fwd_ht<MK, true>(a, rshift, st);
-    }
-    return launch_duo_fwd_ht<MK, false>(a, rshift, st);
-}
 // rshift from gen_split_rshift (ssn_mfma16.hip): the same applicability rules as the other fp16-split forms
 hipError_t launch_gen_forward_duo(const GenFwdArgs<float>& a, hipStream_t st) {
     const int rshift = gen_split_rshift(a);
     if (rshift < 0) return hipErrorInvalidValue;
-    switch (duo_pick_mk(a.M)) {
-        case 104: return launch_duo_fwd_mk<104>(a, rshift, st);
-        case 152: return launch_duo_fwd_mk<152>(a, rshift, st);
-        case 208: return launch_duo_fwd_mk<208>(a, rshift, st);
-        default: return hipErrorInvalidValue;
-    }
+    return Fp16Ladder::with(a.M, [&](auto MKC) {
+        constexpr int MK = decltype(MKC)::value;
+        if constexpr (MK == 208) {
+            if (duo_half_tail(MK, a.M) && duo_half_tail_on()) return launch_duo_fwd_ht<MK, true>(a, rshift, st);
+        }
+        return launch_duo_fwd_ht<MK, false>(a, rshift, st);
+    });
 }
 
-template <int MK>
-static hipError_t launch_duo_solve_mk(const SolveArgs<float>& a, hipStream_t st) {
-    const long nunits = (long)a.B * ((a.NB + 7) / 8);
-    hipLaunchKernelGGL((solve_duo_kernel<MK>), dim3((unsigned)((nunits + 1) / 2)), dim3(512), 0, st, a);
-    return hipGetLastError();
-}
 // applicability: solve_split_supported (ssn_mfma16.hip)
 hipError_t launch_solve_duo(const SolveArgs<float>& a, hipStream_t st) {
     if (!solve_split_supported(a)) return hipErrorInvalidValue;
-    switch (duo_pick_mk(a.M)) {
-        case 104: return launch_duo_solve_mk<104>(a, st);
-        case 152: return launch_duo_solve_mk<152>(a, st);
-        case 208: return launch_duo_solve_mk<208>(a, st);
-        default: return hipErrorInvalidValue;
-    }
+    return Fp16Ladder::with(a.M, [&](auto MKC) {
+        const long nunits = (long)a.B * ((a.NB + 7) / 8);
+        hipLaunchKernelGGL((solve_duo_kernel<decltype(MKC)::value>), dim3((unsigned)((nunits + 1) / 2)), dim3(512), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
-template <int MK>
-static hipError_t launch_duo_bwd_mk(const GenBwdArgs<float>& a, hipStream_t st) {
-    const long nunits = (long)a.B * ((a.NB + 7) / 8);
-    const dim3 grid((unsigned)((nunits + 1) / 2));
-    if (a.g_ext) hipLaunchKernelGGL((gen_backward_duo_kernel<MK, true>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((gen_backward_duo_kernel<MK, false>), grid, dim3(512), 0, st, a);
-    return hipGetLastError();
-}
 // applicability: gen_mfma_supported (any I/O function: the scale follows the data)
 hipError_t launch_gen_backward_duo(const GenBwdArgs<float>& a, hipStream_t st) {
-    switch (duo_pick_mk(a.M)) {
-        case 104: return launch_duo_bwd_mk<104>(a, st);
-        case 152: return launch_duo_bwd_mk<152>(a, st);
-        case 208: return launch_duo_bwd_mk<208>(a, st);
-        default: return hipErrorInvalidValue;
-    }
+    return Fp16Ladder::with(a.M, [&](auto MKC) {
+        constexpr int MK = decltype(MKC)::value;
+        const long nunits = (long)a.B * ((a.NB + 7) / 8);
+        const dim3 grid((unsigned)((nunits + 1) / 2));
+        if (a.g_ext) hipLaunchKernelGGL((gen_backward_duo_kernel<MK, true>), grid, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((gen_backward_duo_kernel<MK, false>), grid, dim3(512), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace ssn

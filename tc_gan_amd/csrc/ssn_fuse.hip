@@ -520,20 +520,9 @@ __global__ void __launch_bounds__(256) gen_backward_fused_kernel(GenBwdArgs<floa
     }
 }
 
-static int fuse_pick_mk(int M) {
-    const int ladder[] = {104, 152, 208};
-    for (int mk : ladder) if (M <= mk) return mk;
-    return 0;
-}
 bool gen_backward_fused_supported(const GenBwdArgs<float>& a, float xmax) {
-    return a.B > 0 && a.NB >= 1 && a.NB <= 8 && a.M >= 2 && (a.M & 1) == 0 && fuse_pick_mk(a.M) != 0 && a.seqlen >= 1 &&
+    return a.B > 0 && a.NB >= 1 && a.NB <= 8 && a.M >= 2 && (a.M & 1) == 0 && Fp16Ladder::pick(a.M) != 0 && a.seqlen >= 1 &&
            xmax > 0.f && xmax < __builtin_inff();
-}
-template <int MK>
-static hipError_t launch_fused_mk(const GenBwdArgs<float>& a, float* gW, int xexp, hipStream_t st) {
-    if (a.g_ext) hipLaunchKernelGGL((gen_backward_fused_kernel<MK, true>), dim3(a.B), dim3(256), 0, st, a, gW, xexp);
-    else hipLaunchKernelGGL((gen_backward_fused_kernel<MK, false>), dim3(a.B), dim3(256), 0, st, a, gW, xexp);
-    return hipGetLastError();
 }
 // a.delta = f'(u) [B][NB][T][M] (read only here), a.traj the trajectory; gW [B][M][M] out; xmax >= every |traj| element
 hipError_t launch_gen_backward_fused(const GenBwdArgs<float>& a, float* gW, float xmax, hipStream_t st) {
@@ -542,12 +531,12 @@ hipError_t launch_gen_backward_fused(const GenBwdArgs<float>& a, float* gW, floa
     const int e = (int)((__builtin_bit_cast(unsigned, xmax) >> 23) & 0xffu) - 127;          // floor(log2 xmax)
     int xexp = 14 - e - 1;
     xexp = xexp > 100 ? 100 : (xexp < -100 ? -100 : xexp);
-    switch (fuse_pick_mk(a.M)) {
-        case 104: return launch_fused_mk<104>(a, gW, xexp, st);
-        case 152: return launch_fused_mk<152>(a, gW, xexp, st);
-        case 208: return launch_fused_mk<208>(a, gW, xexp, st);
-        default: return hipErrorInvalidValue;
-    }
+    return Fp16Ladder::with(a.M, [&](auto MKC) {
+        constexpr int MK = decltype(MKC)::value;
+        if (a.g_ext) hipLaunchKernelGGL((gen_backward_fused_kernel<MK, true>), dim3(a.B), dim3(256), 0, st, a, gW, xexp);
+        else hipLaunchKernelGGL((gen_backward_fused_kernel<MK, false>), dim3(a.B), dim3(256), 0, st, a, gW, xexp);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace ssn

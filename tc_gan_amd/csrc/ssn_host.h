@@ -1,6 +1,8 @@
 // Host-side declarations shared between the kernel translation units and the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
+#include <type_traits>
 #include "ssn_device.h"
 
 namespace ssn {
@@ -146,6 +148,26 @@ template <typename T> hipError_t launch_ss_system(const T* R, const T* W, const 
                                                   const IoConsts<T>& io, int nz, int nb, int M, T* A, T* rhs, hipStream_t st);
 
 template <typename T> hipError_t launch_lu_solve(T* A, T* rhs, int* info, int nsys, int M, int nrhs, hipStream_t st);
+
+// Size ladder of the matrix-core kernels: a kernel is built per ladder size MK and serves every 2N = M up to it.
+// pick: the first ladder size >= M, 0 beyond the ladder; with: f(std::integral_constant<int, MK>{}) for that size
+// (hipErrorInvalidValue beyond the ladder; a braced list, so that f is instantiated in ladder order).
+template <int... MKS>
+struct MkLadder {
+    static int pick(int M) {
+        for (int mk : {MKS...}) if (M <= mk) return mk;
+        return 0;
+    }
+    template <class F>
+    static hipError_t with(int M, F&& f) {
+        const int mk = pick(M);
+        hipError_t err = hipErrorInvalidValue;
+        for (bool hit : {(mk == MKS && (err = f(std::integral_constant<int, MKS>{}), true))...}) (void)hit;
+        return err;
+    }
+};
+using Fp32Ladder = MkLadder<104, 152, 200, 208>;     // ssn_mfma.hip
+using Fp16Ladder = MkLadder<104, 152, 208>;          // ssn_mfma16.hip, ssn_duo.hip, ssn_fuse.hip
 
 // ssn_mfma.hip (fp32, NB >= 4)
 bool gen_mfma_supported(int M, int NB);

@@ -31,22 +31,7 @@
 #include "ssn_host.h"
 #include "ssn_mfma_io.h"
 
-#ifndef SSN_MFMA_ABLATE
-#define SSN_MFMA_ABLATE 0      // diagnostic builds: 1 = no serial part (wrong results, timing only)
-#endif
-
 namespace ssn {
-
-
-// f(v) and f'(v) of ssn_gen.hip (kept in sync: ssnode.c:25-53 / ssnode.py:129-149)
-__device__ __forceinline__ void mfma_io_eval_grad(float v, const IoConsts<float>& c, float& f, float& df) {
-    if (!(v > 0.f)) { f = (v != v) ? v : 0.f; df = 0.f; return; }
-    if (c.io_type == SSN_IO_POWER || v <= c.v0) { f = pow_rate(v, c.k, c.n); df = c.n * f / v; return; }
-    if (c.io_type == SSN_IO_LINEAR) { f = c.soft + c.lin_slope * (v - c.v0); df = c.lin_slope; return; }
-    const float th = tanh_pos(c.tanh_gain * (v - c.v0));
-    f = c.soft + c.span * th;
-    df = c.span_gain * (1.f - th * th);
-}
 
 // the wave's 64-row slab of the row-major M x M matrix A (TRANSPOSED: of its transpose): wr[k] = slab[lane][k]
 template <int MK, bool TRANSPOSED>
@@ -209,58 +194,95 @@ __device__ __forceinline__ mf4 ksplit_gather(const mf4* ab /* [SLOTS][4] of one 
     return acc;
 }
 
-template <int MK, bool SAVE>
-__global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 512, KSplit<MK>::enabled ? 3 : 2) gen_forward_mfma_kernel(GenFwdArgs<float> a) {
+// ---- one matrix wave, in whichever operand layout KSplit<MK>::enabled selects ----------------------------------
+// MfmaShape: the sizes the three kernels and their launchers share, and the serial lanes' read of the hand-off.
+template <int MK>
+struct MfmaShape {
     using KS = KSplit<MK>;
-    constexpr bool KSP = KS::enabled;
-    constexpr int RS = KSP ? KS::RS : MK + 4;     // LDS row stride: the 4 stimuli of a group on disjoint banks
+    static constexpr bool KSP = KS::enabled;
+    static constexpr int RS = KSP ? KS::RS : MK + 4;          // LDS row stride of the state: the 4 stimuli of a group on disjoint banks
+    // accumulator hand-off of one group, in mf4: slab form [matrix wave][lane], K-split form [slot][stimulus]
+    static constexpr int AB = KSP ? KS::SLOTS * 4 : 4 * 64;
+    // __launch_bounds__: three (K-split), respectively two, waves per SIMD of the 512-register file
+    static constexpr int MAX_THREADS = KSP ? KS::THREADS : 512, WAVES_PER_SIMD = KSP ? 3 : 2;
+    // slab form: one matrix and one serial wave per 64 rows of M; K-split form: fixed by MK
+    static int threads(int M) { return KSP ? KS::THREADS : 128 * ((M + 63) / 64); }
+    __device__ static __forceinline__ int matrix_waves() { return KSP ? KS::WM : (int)(blockDim.x >> 7); }
+    // serial lane `lane` of serial wave sw: the complete sums of its 4 rows for its stimulus
+    __device__ static __forceinline__ mf4 gather(const mf4* ab, int sw, int lane) {
+        if constexpr (KSP) return ksplit_gather<MK>(ab, 16 * sw + (lane >> 2), lane & 3);
+        else return ab[sw * 64 + lane];
+    }
+};
+// The W operand in registers (TRANSPOSED: W^T) and the chains of one phase.
+template <int MK, bool TRANSPOSED>
+struct MatrixWave : MfmaShape<MK> {
+    using KS = KSplit<MK>;
+    using MfmaShape<MK>::KSP;
+    using MfmaShape<MK>::RS;
+    std::conditional_t<KSP, float[KS::CH][KS::KP], float[MK]> wr;
+    unsigned xoff[KS::CH];        // K-split: byte offset of (my stimulus row, first column of chain c's part)
+
+    __device__ __forceinline__ void load(const float* A, int M, int wave, int lane) {
+        if constexpr (KSP) {
+            ksplit_load<MK, TRANSPOSED>(A, M, wave, lane, wr);
+#pragma unroll
+            for (int c = 0; c < KS::CH; ++c)
+                xoff[c] = (unsigned)(((lane & 3) * RS + (KS::slot(wave, c, lane >> 2) / KS::NQ) * KS::KP) * 4);
+        } else {
+            slab_load<MK, TRANSPOSED>(A, M, 64 * wave + lane, wr);
+        }
+    }
+    // rows: the first LDS state row (rows RS apart), row: index of the group's first stimulus, ab: the group's hand-off block
+    __device__ __forceinline__ void chain(const float* rows, int row, mf4* ab, int wave, int lane) const {
+        const int blk = lane >> 2, j = lane & 3;
+        if constexpr (KSP) {
+            static_assert(KS::CH == 2, "operand lists below are written out for two chains per wave");
+            using LdsF = const __attribute__((address_space(3))) float*;
+            const unsigned base = (unsigned)(size_t)(LdsF)rows + (unsigned)((row * RS) * 4);
+            unsigned xa[2] = {base + xoff[0], base + xoff[1]};
+            mf4* const out[2] = {&ab[KS::slot(wave, 0, blk) * 4 + j], &ab[KS::slot(wave, 1, blk) * 4 + j]};
+            ksplit_chain<MK>(wr, xa, out);
+        } else {
+            ab[wave * 64 + lane] = slab_chain<MK>(wr, rows + row * RS + j * RS);
+        }
+    }
+};
+
+// template arguments of the serial lambdas: stimulus group, and whether the step lies inside the averaging window
+constexpr std::integral_constant<int, 0> G0{};
+constexpr std::integral_constant<int, 1> G1{};
+constexpr std::integral_constant<bool, false> W0{};
+constexpr std::integral_constant<bool, true> W1{};
+
+template <int MK, bool SAVE>
+__global__ void __launch_bounds__(MfmaShape<MK>::MAX_THREADS, MfmaShape<MK>::WAVES_PER_SIMD) gen_forward_mfma_kernel(GenFwdArgs<float> a) {
+    using MW = MatrixWave<MK, false>;
+    constexpr int RS = MW::RS;
     __shared__ __align__(16) float rbuf[2][8][RS];
-    // accumulator hand-off: slab form [group][matrix wave][lane], K-split form [group][slot][stimulus]
-    __shared__ __align__(16) mf4 abuf[2][KSP ? KS::SLOTS * 4 : 4 * 64];
+    __shared__ __align__(16) mf4 abuf[2][MW::AB];        // accumulator hand-off per group
     const int M = a.M, N = a.M / 2, T_ = a.seqlen;
     const int gpw = a.mfma_groups;                // stimulus groups of 4 in this workgroup (2; 1: group 1 idle)
     const int ngroups = (a.NB + 4 * gpw - 1) / (4 * gpw);
     const int b = blockIdx.x / ngroups;
     const int s0 = (blockIdx.x % ngroups) * 4 * gpw;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = KSplit<MK>::enabled ? KSplit<MK>::WM : (int)(blockDim.x >> 7);     // matrix waves
+    const int wm = MW::matrix_waves();
     const int blk = lane >> 2, j = lane & 3;
     const int nphase = 2 * T_ + 1;
     for (int c = threadIdx.x; c < 2 * 8 * RS; c += blockDim.x) (&rbuf[0][0][0])[c] = 0.f;
 
     if (wave < wm) {
         // ================================ matrix wave ================================
-        if constexpr (KSP) {
-            float wr[KS::CH][KS::KP];
-            ksplit_load<MK, false>(a.W + (size_t)b * M * M, M, wave, lane, wr);
-            using LdsF = const __attribute__((address_space(3))) float*;
-            const unsigned rb0 = (unsigned)(size_t)(LdsF)&rbuf[0][0][0];
-            unsigned xoff[KS::CH];                // byte offset of (my stimulus row, first column of chain c's part)
-#pragma unroll
-            for (int c = 0; c < KS::CH; ++c) xoff[c] = (unsigned)((j * RS + (KS::slot(wave, c, blk) / KS::NQ) * KS::KP) * 4);
-            __syncthreads();
-            for (int p = 0; p < nphase; ++p) {
-                if (p < 2 * T_ && (p & 1) < gpw && !(SSN_MFMA_ABLATE & 2)) {
-                    const int g = p & 1, it = p >> 1;
-                    const unsigned base = rb0 + (unsigned)((((it & 1) * 8 + 4 * g) * RS) * 4);
-                    static_assert(KS::CH == 2, "operand lists below are written out for two chains per wave");
-                    unsigned xa[2] = {base + xoff[0], base + xoff[1]};
-                    mf4* const out[2] = {&abuf[g][KS::slot(wave, 0, blk) * 4 + j], &abuf[g][KS::slot(wave, 1, blk) * 4 + j]};
-                    ksplit_chain<MK>(wr, xa, out);
-                }
-                __syncthreads();
+        MW mw;
+        mw.load(a.W + (size_t)b * M * M, M, wave, lane);
+        __syncthreads();
+        for (int p = 0; p < nphase; ++p) {
+            if (p < 2 * T_ && (p & 1) < gpw) {
+                const int g = p & 1, it = p >> 1;
+                mw.chain(&rbuf[0][0][0], (it & 1) * 8 + 4 * g, &abuf[g][0], wave, lane);
             }
-        } else {
-            float wr[MK];
-            slab_load<MK, false>(a.W + (size_t)b * M * M, M, 64 * wave + lane, wr);
             __syncthreads();
-            for (int p = 0; p < nphase; ++p) {
-                if (p < 2 * T_ && (p & 1) < gpw && !(SSN_MFMA_ABLATE & 2)) {
-                    const int g = p & 1, it = p >> 1;
-                    abuf[g][wave * 64 + lane] = slab_chain<MK>(wr, &rbuf[it & 1][4 * g + j][0]);
-                }
-                __syncthreads();
-            }
         }
         return;
     }
@@ -299,16 +321,14 @@ __global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 51
     auto serial = [&](auto G, auto WIN, int it) {
         constexpr int g = decltype(G)::value;
         constexpr bool win_on = decltype(WIN)::value;
-        mf4 acc;
-        if constexpr (KSP) acc = ksplit_gather<MK>(&abuf[g][0], 16 * sw + blk, j);
-        else acc = abuf[g][sw * 64 + lane];
+        const mf4 acc = MW::gather(&abuf[g][0], sw, lane);
         const float accs[4] = {acc.x, acc.y, acc.z, acc.w};
         const float win2 = (it > a.skip) ? 1.f : 0.f;
         float rnew[4], dfn[4] = {0.f, 0.f, 0.f, 0.f};   // scalars: see the bit_cast note in ssn_tile_core.h
         float uu[4], ff[4];
 #pragma unroll
         for (int v = 0; v < 4; ++v) uu[v] = accs[v] + ex[g][v];
-        if (SSN_MFMA_ABLATE & 4) { for (int v = 0; v < 4; ++v) ff[v] = uu[v] * 0.5f; } else io.template eval4<SAVE>(uu, ff, dfn);
+        io.template eval4<SAVE>(uu, ff, dfn);
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             const float f = ff[v];
@@ -341,23 +361,19 @@ __global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 51
         }
         if (er < M) *reinterpret_cast<mf4*>(&rbuf[(it + 1) & 1][4 * g + j][er]) = (mf4){rnew[0], rnew[1], rnew[2], rnew[3]};
     };
-    constexpr std::integral_constant<int, 0> G0{};
-    constexpr std::integral_constant<int, 1> G1{};
     __syncthreads();
     __syncthreads();                                  // phase 0: nothing to finish yet
-    constexpr std::integral_constant<bool, false> W0{};
-    constexpr std::integral_constant<bool, true> W1{};
     const int nskip = a.skip < T_ ? (a.skip > 0 ? a.skip : 0) : T_;
     for (int it = 0; it < nskip; ++it) {
-        if (!(SSN_MFMA_ABLATE & 1)) serial(G0, W0, it);     // phase 2 it + 1
+        serial(G0, W0, it);                           // phase 2 it + 1
         __syncthreads();
-        if (!(SSN_MFMA_ABLATE & 1) && gpw == 2) serial(G1, W0, it);     // phase 2 it + 2
+        if (gpw == 2) serial(G1, W0, it);             // phase 2 it + 2
         __syncthreads();
     }
     for (int it = nskip; it < T_; ++it) {
-        if (!(SSN_MFMA_ABLATE & 1)) serial(G0, W1, it);
+        serial(G0, W1, it);
         __syncthreads();
-        if (!(SSN_MFMA_ABLATE & 1) && gpw == 2) serial(G1, W1, it);
+        if (gpw == 2) serial(G1, W1, it);
         __syncthreads();
     }
 
@@ -382,55 +398,32 @@ __global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 51
 // serial(tau - 1) [carry = (1 - eps) a_tau + W^T delta_tau] ...; group 0 serial phases are the even ones, group 1 the
 // odd ones, the matrix waves serve the other group in every phase.
 template <int MK>
-__global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 512, KSplit<MK>::enabled ? 3 : 2) gen_backward_mfma_kernel(GenBwdArgs<float> a) {
-    using KS = KSplit<MK>;
-    constexpr bool KSP = KS::enabled;
-    constexpr int RS = KSP ? KS::RS : MK + 4;
+__global__ void __launch_bounds__(MfmaShape<MK>::MAX_THREADS, MfmaShape<MK>::WAVES_PER_SIMD) gen_backward_mfma_kernel(GenBwdArgs<float> a) {
+    using MW = MatrixWave<MK, true>;
+    constexpr int RS = MW::RS;
     __shared__ __align__(16) float dbuf[8][RS];          // delta_tau per stimulus, contiguous in the neuron index
-    __shared__ __align__(16) mf4 abuf[2][KSP ? KS::SLOTS * 4 : 4 * 64];    // hand-off, as in the forward kernel
+    __shared__ __align__(16) mf4 abuf[2][MW::AB];        // hand-off, as in the forward kernel
     const int M = a.M, N = a.M / 2, T_ = a.seqlen;
     const int gpw = a.mfma_groups;
     const int ngroups = (a.NB + 4 * gpw - 1) / (4 * gpw);
     const int b = blockIdx.x / ngroups;
     const int s0 = (blockIdx.x % ngroups) * 4 * gpw;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = KSplit<MK>::enabled ? KSplit<MK>::WM : (int)(blockDim.x >> 7);
+    const int wm = MW::matrix_waves();
     const int blk = lane >> 2, j = lane & 3;
     const int nphase = 2 * T_;
     for (int c = threadIdx.x; c < 8 * RS; c += blockDim.x) (&dbuf[0][0])[c] = 0.f;
 
     if (wave < wm) {
-        if constexpr (KSP) {
-            float wr[KS::CH][KS::KP];
-            ksplit_load<MK, true>(a.W + (size_t)b * M * M, M, wave, lane, wr);
-            using LdsF = const __attribute__((address_space(3))) float*;
-            const unsigned db0 = (unsigned)(size_t)(LdsF)&dbuf[0][0];
-            unsigned xoff[KS::CH];
-#pragma unroll
-            for (int c = 0; c < KS::CH; ++c) xoff[c] = (unsigned)((j * RS + (KS::slot(wave, c, blk) / KS::NQ) * KS::KP) * 4);
-            __syncthreads();
-            for (int p = 0; p < nphase; ++p) {
-                if (p >= 1 && ((p - 1) & 1) < gpw) {
-                    const int g = (p - 1) & 1;
-                    const unsigned base = db0 + (unsigned)(4 * g * RS * 4);
-                    static_assert(KS::CH == 2, "operand lists below are written out for two chains per wave");
-                    unsigned xa[2] = {base + xoff[0], base + xoff[1]};
-                    mf4* const out[2] = {&abuf[g][KS::slot(wave, 0, blk) * 4 + j], &abuf[g][KS::slot(wave, 1, blk) * 4 + j]};
-                    ksplit_chain<MK>(wr, xa, out);
-                }
-                __syncthreads();
+        MW mw;
+        mw.load(a.W + (size_t)b * M * M, M, wave, lane);
+        __syncthreads();
+        for (int p = 0; p < nphase; ++p) {
+            if (p >= 1 && ((p - 1) & 1) < gpw) {
+                const int g = (p - 1) & 1;
+                mw.chain(&dbuf[0][0], 4 * g, &abuf[g][0], wave, lane);
             }
-        } else {
-            float wr[MK];
-            slab_load<MK, true>(a.W + (size_t)b * M * M, M, 64 * wave + lane, wr);
             __syncthreads();
-            for (int p = 0; p < nphase; ++p) {
-                if (p >= 1 && ((p - 1) & 1) < gpw) {
-                    const int g = (p - 1) & 1;
-                    abuf[g][wave * 64 + lane] = slab_chain<MK>(wr, &dbuf[4 * g + j][0]);
-                }
-                __syncthreads();
-            }
         }
         return;
     }
@@ -507,9 +500,7 @@ __global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 51
         }
         if (tau >= 3) load4(rs_dlt, at_step(g, tau - 3), ndf);
         if (tau < T_) {
-            mf4 acc;                                                                  // W^T delta_{tau+1}
-            if constexpr (KSP) acc = ksplit_gather<MK>(&abuf[g][0], 16 * sw + blk, j);
-            else acc = abuf[g][sw * 64 + lane];
+            const mf4 acc = MW::gather(&abuf[g][0], sw, lane);                        // W^T delta_{tau+1}
             carry[g][0] += acc.x; carry[g][1] += acc.y; carry[g][2] += acc.z; carry[g][3] += acc.w;
         }
         float delta[4];
@@ -534,10 +525,6 @@ __global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 51
         if (live[g] && er < M) *reinterpret_cast<mf4*>(&dbuf[4 * g + j][er]) = (mf4){delta[0], delta[1], delta[2], delta[3]};
         if (tau >= 2) store4(rs_dlt, at_step(g, tau - 2), delta);                      // shifted: pairs with x_{tau-1}
     };
-    constexpr std::integral_constant<int, 0> G0{};
-    constexpr std::integral_constant<int, 1> G1{};
-    constexpr std::integral_constant<bool, false> W0{};
-    constexpr std::integral_constant<bool, true> W1{};
     __syncthreads();
     int tau = T_;
     for (; tau >= a.skip + 1 && tau >= 1; --tau) {    // window steps first (time runs backwards)
@@ -570,19 +557,18 @@ __global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 51
 // phase in which serial(g, it) ran; in the NEXT phase EVERY wave reads them and updates the same frozen mask / codes /
 // step counts, so matrix and serial waves leave the loop in the same phase.
 template <int MK>
-__global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 512, KSplit<MK>::enabled ? 3 : 2) solve_mfma_kernel(SolveArgs<float> a) {
-    using KS = KSplit<MK>;
-    constexpr bool KSP = KS::enabled;
-    constexpr int RS = KSP ? KS::RS : MK + 4;
+__global__ void __launch_bounds__(MfmaShape<MK>::MAX_THREADS, MfmaShape<MK>::WAVES_PER_SIMD) solve_mfma_kernel(SolveArgs<float> a) {
+    using MW = MatrixWave<MK, false>;
+    constexpr int RS = MW::RS;
     __shared__ __align__(16) float rbuf[2][8][RS];
-    __shared__ __align__(16) mf4 abuf[2][KSP ? KS::SLOTS * 4 : 4 * 64];    // hand-off, as in the generator kernels
+    __shared__ __align__(16) mf4 abuf[2][MW::AB];        // hand-off, as in the generator kernels
     __shared__ __align__(16) int flags[3][8];
     const int M = a.M, N = a.N, max_iter = a.st.max_iter;
     const int ngroups = (a.NB + 7) / 8;
     const int b = blockIdx.x / ngroups;
     const int s0 = (blockIdx.x % ngroups) * 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = KSplit<MK>::enabled ? KSplit<MK>::WM : (int)(blockDim.x >> 7);
+    const int wm = MW::matrix_waves();
     const int blk = lane >> 2, j = lane & 3;
     const bool matrix = wave < wm;
     const int sw = wave - wm;
@@ -610,58 +596,25 @@ __global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 51
         my_frozen = my_frozen || stop;
         frozen = (unsigned)__builtin_amdgcn_ballot_w64(my_frozen) & 0xffu;
     };
-    constexpr std::integral_constant<int, 0> G0{};
-    constexpr std::integral_constant<int, 1> G1{};
 
     // The two roles run the SAME phase structure (same barriers, same exits) in separate loops, so that the
     // registers of one role (200 for the slab) are not live in the other.
     if (matrix) {
-        if constexpr (KSP) {
-            float wr[KS::CH][KS::KP];
-            ksplit_load<MK, false>(a.W + (size_t)b * M * M, M, wave, lane, wr);
-            using LdsF = const __attribute__((address_space(3))) float*;
-            const unsigned rb0 = (unsigned)(size_t)(LdsF)&rbuf[0][0][0];
-            unsigned xoff[KS::CH];
-#pragma unroll
-            for (int c = 0; c < KS::CH; ++c) xoff[c] = (unsigned)((j * RS + (KS::slot(wave, c, blk) / KS::NQ) * KS::KP) * 4);
-            auto chain = [&](int g, int it) {
-                const unsigned base = rb0 + (unsigned)((((it & 1) * 8 + 4 * g) * RS) * 4);
-                static_assert(KS::CH == 2, "operand lists below are written out for two chains per wave");
-                unsigned xa[2] = {base + xoff[0], base + xoff[1]};
-                mf4* const out[2] = {&abuf[g][KS::slot(wave, 0, blk) * 4 + j], &abuf[g][KS::slot(wave, 1, blk) * 4 + j]};
-                ksplit_chain<MK>(wr, xa, out);
-            };
+        MW mw;
+        mw.load(a.W + (size_t)b * M * M, M, wave, lane);
+        __syncthreads();
+        for (int it = 0; it <= max_iter; ++it) {
+            int f4 = 0;
+            if (it >= 1) f4 = flags_read(G0, it - 1);                           // phase 2 it
+            if (it < max_iter) mw.chain(&rbuf[0][0][0], (it & 1) * 8, &abuf[0][0], wave, lane);
+            if (it >= 1) verdict(G0, it - 1, f4);
+            if (frozen == 0xffu) break;
             __syncthreads();
-            for (int it = 0; it <= max_iter; ++it) {
-                int f4 = 0;
-                if (it >= 1) f4 = flags_read(G0, it - 1);                       // phase 2 it
-                if (it < max_iter) chain(0, it);
-                if (it >= 1) verdict(G0, it - 1, f4);
-                if (frozen == 0xffu) break;
-                __syncthreads();
-                if (it >= 1) f4 = flags_read(G1, it - 1);                       // phase 2 it + 1
-                if (it < max_iter) chain(1, it);
-                if (it >= 1) verdict(G1, it - 1, f4);
-                if (frozen == 0xffu) break;
-                __syncthreads();
-            }
-        } else {
-            float wr[MK];
-            slab_load<MK, false>(a.W + (size_t)b * M * M, M, 64 * wave + lane, wr);
+            if (it >= 1) f4 = flags_read(G1, it - 1);                           // phase 2 it + 1
+            if (it < max_iter) mw.chain(&rbuf[0][0][0], (it & 1) * 8 + 4, &abuf[1][0], wave, lane);
+            if (it >= 1) verdict(G1, it - 1, f4);
+            if (frozen == 0xffu) break;
             __syncthreads();
-            for (int it = 0; it <= max_iter; ++it) {
-                int f4 = 0;
-                if (it >= 1) f4 = flags_read(G0, it - 1);                       // phase 2 it
-                if (it < max_iter) abuf[0][wave * 64 + lane] = slab_chain<MK>(wr, &rbuf[it & 1][j][0]);
-                if (it >= 1) verdict(G0, it - 1, f4);
-                if (frozen == 0xffu) break;
-                __syncthreads();
-                if (it >= 1) f4 = flags_read(G1, it - 1);                       // phase 2 it + 1
-                if (it < max_iter) abuf[1][wave * 64 + lane] = slab_chain<MK>(wr, &rbuf[it & 1][4 + j][0]);
-                if (it >= 1) verdict(G1, it - 1, f4);
-                if (frozen == 0xffu) break;
-                __syncthreads();
-            }
         }
         return;
     }
@@ -690,9 +643,7 @@ __global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 51
     for (int v = 0; v < 4; ++v) rowok[v] = er + v < M;
     auto serial = [&](auto G, int it) {            // serial part of (group G, step it)
         constexpr int g = decltype(G)::value;
-        mf4 acc;
-        if constexpr (KSP) acc = ksplit_gather<MK>(&abuf[g][0], 16 * sw + blk, j);
-        else acc = abuf[g][sw * 64 + lane];
+        const mf4 acc = MW::gather(&abuf[g][0], sw, lane);
         const float accs[4] = {acc.x, acc.y, acc.z, acc.w};
         float uu[4], ff[4], dummy[4], r1[4], dabs[4];
 #pragma unroll
@@ -749,63 +700,34 @@ __global__ void __launch_bounds__(KSplit<MK>::enabled ? KSplit<MK>::THREADS : 51
     }
 }
 
-static int mfma_pick_mk(int M) {
-    const int ladder[] = {104, 152, 200, 208};
-    for (int mk : ladder) if (M <= mk) return mk;
-    return 0;
-}
-bool gen_mfma_supported(int M, int NB) { return (M % 2 == 0) && NB >= 4 && mfma_pick_mk(M) != 0; }
+bool gen_mfma_supported(int M, int NB) { return (M % 2 == 0) && NB >= 4 && Fp32Ladder::pick(M) != 0; }
 
-template <int MK>
-static hipError_t launch_fwd_mk(const GenFwdArgs<float>& a, hipStream_t st) {
-    const int threads = KSplit<MK>::enabled ? KSplit<MK>::THREADS : 128 * ((a.M + 63) / 64);
-    const int ngroups = (a.NB + 4 * a.mfma_groups - 1) / (4 * a.mfma_groups);
-    if (a.traj) hipLaunchKernelGGL((gen_forward_mfma_kernel<MK, true>), dim3(a.B * ngroups), dim3(threads), 0, st, a);
-    else hipLaunchKernelGGL((gen_forward_mfma_kernel<MK, false>), dim3(a.B * ngroups), dim3(threads), 0, st, a);
-    return hipGetLastError();
-}
 hipError_t launch_gen_forward_mfma(const GenFwdArgs<float>& a, hipStream_t st) {
-    switch (mfma_pick_mk(a.M)) {
-        case 104: return launch_fwd_mk<104>(a, st);
-        case 152: return launch_fwd_mk<152>(a, st);
-        case 200: return launch_fwd_mk<200>(a, st);
-        case 208: return launch_fwd_mk<208>(a, st);
-        default: return hipErrorInvalidValue;
-    }
+    return Fp32Ladder::with(a.M, [&](auto MKC) {
+        constexpr int MK = decltype(MKC)::value;
+        const int ngroups = (a.NB + 4 * a.mfma_groups - 1) / (4 * a.mfma_groups);
+        const dim3 grid(a.B * ngroups), block(MfmaShape<MK>::threads(a.M));
+        if (a.traj) hipLaunchKernelGGL((gen_forward_mfma_kernel<MK, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((gen_forward_mfma_kernel<MK, false>), grid, block, 0, st, a);
+        return hipGetLastError();
+    });
 }
 
-template <int MK>
-static hipError_t launch_bwd_mk(const GenBwdArgs<float>& a, hipStream_t st) {
-    const int threads = KSplit<MK>::enabled ? KSplit<MK>::THREADS : 128 * ((a.M + 63) / 64);
-    const int ngroups = (a.NB + 4 * a.mfma_groups - 1) / (4 * a.mfma_groups);
-    hipLaunchKernelGGL((gen_backward_mfma_kernel<MK>), dim3(a.B * ngroups), dim3(threads), 0, st, a);
-    return hipGetLastError();
-}
 hipError_t launch_gen_backward_mfma(const GenBwdArgs<float>& a, hipStream_t st) {
-    switch (mfma_pick_mk(a.M)) {
-        case 104: return launch_bwd_mk<104>(a, st);
-        case 152: return launch_bwd_mk<152>(a, st);
-        case 200: return launch_bwd_mk<200>(a, st);
-        case 208: return launch_bwd_mk<208>(a, st);
-        default: return hipErrorInvalidValue;
-    }
+    return Fp32Ladder::with(a.M, [&](auto MKC) {
+        constexpr int MK = decltype(MKC)::value;
+        const int ngroups = (a.NB + 4 * a.mfma_groups - 1) / (4 * a.mfma_groups);
+        hipLaunchKernelGGL((gen_backward_mfma_kernel<MK>), dim3(a.B * ngroups), dim3(MfmaShape<MK>::threads(a.M)), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
-template <int MK>
-static hipError_t launch_solve_mk(const SolveArgs<float>& a, hipStream_t st) {
-    const int threads = KSplit<MK>::enabled ? KSplit<MK>::THREADS : 128 * ((a.M + 63) / 64);
-    const int ngroups = (a.NB + 7) / 8;
-    hipLaunchKernelGGL((solve_mfma_kernel<MK>), dim3(a.B * ngroups), dim3(threads), 0, st, a);
-    return hipGetLastError();
-}
 hipError_t launch_solve_mfma(const SolveArgs<float>& a, hipStream_t st) {
-    switch (mfma_pick_mk(a.M)) {
-        case 104: return launch_solve_mk<104>(a, st);
-        case 152: return launch_solve_mk<152>(a, st);
-        case 200: return launch_solve_mk<200>(a, st);
-        case 208: return launch_solve_mk<208>(a, st);
-        default: return hipErrorInvalidValue;
-    }
+    return Fp32Ladder::with(a.M, [&](auto MKC) {
+        constexpr int MK = decltype(MKC)::value;
+        hipLaunchKernelGGL((solve_mfma_kernel<MK>), dim3(a.B * ((a.NB + 7) / 8)), dim3(MfmaShape<MK>::threads(a.M)), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace ssn

@@ -1153,28 +1153,12 @@ __global__ void __launch_bounds__(512, 2) solve_split_kernel(SolveArgs<float> a)
 }
 
 
-static int split_pick_mk(int M) {
-    const int ladder[] = {104, 152, 208};
-    for (int mk : ladder) if (M <= mk) return mk;
-    return 0;
-}
-// f(std::integral_constant<int, MK>) for the tile grid split_pick_mk names
-template <class F>
-static hipError_t split_with_mk(int M, F&& f) {
-    switch (split_pick_mk(M)) {
-        case 104: return f(std::integral_constant<int, 104>{});
-        case 152: return f(std::integral_constant<int, 152>{});
-        case 208: return f(std::integral_constant<int, 208>{});
-        default: return hipErrorInvalidValue;
-    }
-}
-
 // rshift: r 2^rshift stays below the fp16 range for every reachable rate (r <= rate_hard_bound with the saturating
 // I/O function and Euler factors <= 1); -1: the split kernel does not apply
 int gen_split_rshift(const GenFwdArgs<float>& a) {
     if (a.io.io_type != SSN_IO_TANH || !(a.io.hard > 0.f) || !(a.io.hard < 3.0e4f) || !(a.io.soft >= 0.f)) return -1;
     if (!(a.eps_E > 0.f && a.eps_E <= 1.f && a.eps_I > 0.f && a.eps_I <= 1.f)) return -1;
-    if ((a.M & 1) || a.NB < 4 || split_pick_mk(a.M) == 0) return -1;
+    if ((a.M & 1) || a.NB < 4 || Fp16Ladder::pick(a.M) == 0) return -1;
     int sh = 0;
     while (sh < 14 && a.io.hard * (float)(2 << sh) <= 32768.f) ++sh;
     return sh;
@@ -1199,18 +1183,18 @@ static hipError_t launch_split_mk(const GenFwdArgs<float>& a, int rshift, hipStr
 hipError_t launch_gen_forward_split(const GenFwdArgs<float>& a, hipStream_t st) {
     const int rshift = gen_split_rshift(a);
     if (rshift < 0) return hipErrorInvalidValue;
-    return split_with_mk(a.M, [&](auto MK) {
+    return Fp16Ladder::with(a.M, [&](auto MK) {
         return a.traj ? launch_split_mk<decltype(MK)::value, true>(a, rshift, st) : launch_split_mk<decltype(MK)::value, false>(a, rshift, st);
     });
 }
 
 bool solve_split_supported(const SolveArgs<float>& a) {
     return a.io.io_type == SSN_IO_TANH && a.io.hard > 0.f && a.io.hard < 3.0e4f && a.io.soft >= 0.f && a.st.eps_E > 0.f &&
-           a.st.eps_E <= 1.f && a.st.eps_I > 0.f && a.st.eps_I <= 1.f && !(a.M & 1) && a.NB >= 4 && split_pick_mk(a.M) != 0;
+           a.st.eps_E <= 1.f && a.st.eps_I > 0.f && a.st.eps_I <= 1.f && !(a.M & 1) && a.NB >= 4 && Fp16Ladder::pick(a.M) != 0;
 }
 hipError_t launch_solve_split(const SolveArgs<float>& a, hipStream_t st) {
     if (!solve_split_supported(a)) return hipErrorInvalidValue;
-    return split_with_mk(a.M, [&](auto MK) {
+    return Fp16Ladder::with(a.M, [&](auto MK) {
         const dim3 grid(a.B * ((a.NB + 7) / 8)), block(512);
         if (a.split_form) hipLaunchKernelGGL((solve_split_kernel<decltype(MK)::value, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((solve_split_kernel<decltype(MK)::value, false>), grid, block, 0, st, a);
@@ -1219,7 +1203,7 @@ hipError_t launch_solve_split(const SolveArgs<float>& a, hipStream_t st) {
 }
 
 hipError_t launch_gen_backward_split(const GenBwdArgs<float>& a, hipStream_t st) {
-    return split_with_mk(a.M, [&](auto MK) {
+    return Fp16Ladder::with(a.M, [&](auto MK) {
         const int ngroups = (a.NB + 4 * a.mfma_groups - 1) / (4 * a.mfma_groups);
         hipLaunchKernelGGL((gen_backward_split_kernel<decltype(MK)::value>), dim3(a.B * ngroups), dim3(512), 0, st, a);
         return hipGetLastError();

@@ -1,9 +1,11 @@
+"""HIP-event timing of the adjoint sweep, alone and with dL/dW, at the C3 shape (1024 draws x 8 stimuli x 1200 steps, 2N = 200).
+usage: tools/time_adj.py [kernel] [paper]     kernel: a code of clib.GEN_KERNELS, default 8 (2: the fp32 matrix-core sweep)"""
 import os, sys, torch
-sys.path.insert(0, '/root/repo' if os.path.exists('/root/repo/tc_gan_amd') else os.getcwd())
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tc_gan_amd import genops
 B, NB, M, T, skip = 1024, 8, 200, 1200, 1000
-KERNEL, GEN = 8, {}
-if len(sys.argv) > 1 and sys.argv[1] == 'paper':       # the paper's run: 128 draws, 2N = 202, 240 / 200 steps, tau_E = 2, the library's own choice
+KERNEL, GEN = next((int(a) for a in sys.argv[1:] if a.isdigit()), 8), {}
+if 'paper' in sys.argv[1:]:       # the paper's run: 128 draws, 2N = 202, 240 / 200 steps, tau_E = 2, the library's own choice
     B, NB, M, T, skip, KERNEL, GEN = 128, 8, 202, 240, 200, 0, dict(tau_E=2.0)
 g = torch.Generator(device='cuda'); g.manual_seed(1)
 W = (torch.rand((B, M, M), device='cuda', generator=g) - 0.6) * 0.02
@@ -17,7 +19,7 @@ bwd(); e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_ti
 e0.record()
 for _ in range(3): bwd()
 e1.record(); torch.cuda.synchronize()
-print('adjoint (in place, repeated) %.3f ms' % (e0.elapsed_time(e1) / 3))
+print('kernel %d: adjoint (in place, repeated) %.3f ms' % (KERNEL, e0.elapsed_time(e1) / 3), flush=True)
 if hasattr(genops.libssnode, 'ssn_debug_duo_stamps'):       # diagnostic build (-DSSN_DUO_STAMP=1): the steps after the window
     import ctypes
     buf = (ctypes.c_ulonglong * 64)()
