@@ -26,8 +26,9 @@
 // lane's tile in VGPRs as packed pairs, two in LDS), 167 VGPRs, three workgroups
 // per CU; the all-register shape (175 W registers per lane, two workgroups per
 // CU) is variant 4.  fp32 with one stimulus per draw at 2N = 170..200: rows 56/48/48/48, one 7-row and three 6-row
-// waves (solve_tile_mixed6_kernel).  fp64: 7 rows x C <= 13 up to 2N = 104, 4 rows x C = 19 / 26
-// (one workgroup of 5-7 waves per CU) up to 2N = 208.
+// waves (solve_tile_mixed6_kernel), whose lane grid puts the column-group bits on lane bits 2, 3 and 0 so that two of the three
+// exchanges of the transpose-reduce choose with DPP bank masks (reduce_bank_f32, ssn_tile_core.h).  fp64: 7 rows x C <= 13 up
+// to 2N = 104, 4 rows x C = 19 / 26 (one workgroup of 5-7 waves per CU) up to 2N = 208.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "ssn_device.h"
@@ -48,12 +49,23 @@ namespace ssn {
 // LDS words of the stop protocol per stimulus: three rotating slots, or the two verdict words of the fp32 NB = 1 loop
 template <typename T, int NB> constexpr int tile_flag_words() { return (NB == 1 && sizeof(T) == 4 && !SSN_ABLATE) ? 2 : 3; }
 
+// The fp32 NB = 1 loop exists twice in its kernels, with and without the test of the rate bound, which is uniform per launch:
+// the kernel picks the whole wave body once, so that the loop of a launch without the test holds no compare against hard_stop.
+// (Two loops behind one prologue do not fit the mixed kernels' 168 VGPRs.)  The mixed kernels do this.  TIGHT:
+// solve_tile_mixed_kernel at C = 25 spills a register with two bodies and keeps the one with the test, as solve_tile_kernel does
+// in all its shapes: several of them sit right at a register step (128 VGPRs at C = 13: a fourth wave per SIMD; 168 at C = 19
+// and C = 25), which the second body crosses.
+template <typename T, int NB, bool TIGHT = false> constexpr bool tile_hard_split() { return NB == 1 && sizeof(T) == 4 && !SSN_ABLATE && !TIGHT; }
+
 // The Euler loop of one wave: its RA x C tile of W (rows rowbase + a of row group rg), the step loop with ONE workgroup
 // barrier per step, the stop protocol and the final stores.  Every wave of a workgroup runs this with the same C, NB
 // and barrier sequence; RA / RL / PK (row pairs packed for v_pk_fma_f32) may differ between waves (mixed kernels below).
 // wlds, wtid: the LDS image of the tile's LDS-resident rows and this thread's index in it (the workgroup's image and
 // threadIdx.x; with WSO = 64 the wave's own image and the lane).  KV, WSO: see SplitTile.
-template <typename T, int RA, int C, int RL, int NB, bool PK, int KV = -1, int WSO = 0>
+// BANK (the fp32 NB = 1 waves of solve_tile_mixed6_kernel): the column-group bits on lane bits 2, 3 and 0, so that two of the three
+// exchanges of the transpose-reduce choose with DPP bank masks (reduce_bank_f32): the lane owns the columns of group
+// bank_col_group(lane) and finishes row bank_row(lane) of its row group; rowbase is that of row group bank_row_group(lane).
+template <typename T, int RA, int C, int RL, int NB, bool PK, int KV = -1, int WSO = 0, bool BANK = false, bool HARD = true>
 __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T (*rbuf)[NB][8 * SlabPad<C>::value],
                                                int (*flags)[NB], const int rowbase, const int wtid) {
     constexpr int CP = SlabPad<C>::value;
@@ -65,7 +77,9 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     const int b = blockIdx.x / ngroups;
     const int s0 = (blockIdx.x % ngroups) * NB;
     const int lane = threadIdx.x & 63;
-    const int cg = lane & 7;
+    // cg: the column group whose columns this lane owns; fr: the row of its row group that it finishes (>= RA: none)
+    const int cg = BANK ? bank_col_group(lane) : lane & 7;
+    const int fr = BANK ? bank_row(lane) : cg;
     const int colbase = cg * C;
 
     // ---- prologue: my RA x C tile of W -> registers (and LDS for the last RL rows) -----------------
@@ -79,6 +93,7 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     // one-statement forms throughout and a transpose-reduce that forms no zero rows 6 and 7
     constexpr bool SIXROW = KV >= 0;
     static_assert(!SIXROW || (SSN_PK_ASM && sizeof(T) == 4 && NB == 1 && !PK && RA == 6 && RL == 2), "the 6-row wave is an fp32 NB = 1 form");
+    static_assert(!BANK || OPAIR || SIXROW, "the bank-mask reduce is the 7- and 6-row fp32 NB = 1 waves'");
     // the FMA block of the solver (SplitTile::matvec's MODE): the first product of every chain is a multiply, and the light
     // wave of the mixed kernel (all rows packed, none in LDS) runs the one-statement form as well
     constexpr int FMA_MODE = 2 | ((OPAIR || SIXROW || (PK && RL == 0)) ? 1 : 0);
@@ -90,9 +105,9 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     // exec-mask region around the state store (FLAT)
     constexpr bool FAST1 = NB == 1 && sizeof(T) == 4 && !SSN_ABLATE;
     constexpr bool FLAT = FAST1 && CP > C;      // (C = 4 has no pad float to absorb a dummy store)
-    // the row this lane finishes each step (a = cg), its LDS slot, input and state
-    const int myrow = rowbase + cg;
-    const bool fin = (cg < RA) && (myrow < M);
+    // the row this lane finishes each step (a = fr: cg, or with BANK bank_row(lane)), its LDS slot, input and state
+    const int myrow = rowbase + fr;
+    const bool fin = (fr < RA) && (myrow < M);
     // FLAT: a lane that finishes no row stores its (meaningless) state every step all the same, to the last pad float of
     // its column group's slab: column CP - 1 >= C, which no FMA consumes -- never to a column c < C of a ragged last
     // group: those meet masked-zero W, and 0 * Inf = NaN
@@ -130,6 +145,7 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
     // slot (i+1)%3 is cleared for iteration i+1.  The FMAs of the extra iteration are discarded.
     int cur = 0;
     int step = 0;
+    int outrow = myrow;                  // the row of the final stores
     if constexpr (FAST1) {
         using LdsI = __attribute__((address_space(3))) int*;
         using LdsB = __attribute__((address_space(3))) unsigned char*;
@@ -140,8 +156,11 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
         // Stop protocol of this loop: one verdict WORD per parity of the state buffer, one BYTE of it per wave.  In step t
         // every wave ANDs its two compare masks with the mask of its finishing lanes and forms one scalar byte -- bit 0:
         // some row of this wave is still moving, bit 1: some row hit the rate bound -- which all its lanes store, same
-        // address, same value, to byte `wave` of word t % 2.  A wave overwrites its own byte every step, so there is no
-        // clear, no sink word and no address select; the bytes of waves that do not exist are zeroed once in the prologue.
+        // address, same value, to byte `wave` of word t % 2.  Only the wave itself ever writes that byte, so it keeps the
+        // value it stored last per parity in a scalar register (0 behind the prologue's clear) and stores under a scalar
+        // branch, only when the byte changes: there is no clear, no sink word and no address select, and a step whose
+        // verdict is that of two steps before costs the vector port and the LDS nothing for it.  The bytes of waves that
+        // do not exist are zeroed once in the prologue.
         // Two words are enough: the word of step t is written before barrier t, read after barrier t (the load issued
         // before the FMA block of step t + 1, consumed behind it, before barrier t + 1), and its next write, for step
         // t + 2, comes after barrier t + 1.  Step t reads state buffer t % 2 and writes the other, so the word follows the
@@ -153,9 +172,10 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
         const unsigned sst = (unsigned)(size_t)(LdsV)(rb0 + myslot);            // my state slot in buffer 0
         unsigned xav = (unsigned)(size_t)(LdsV)(rb0 + cg * CP);                 // my column group's slab of buffer 0
         unsigned wav = (unsigned)(size_t)(LdsV)(wlds + wtid * 4);               // my first LDS-resident W unit
-        // the lanes that finish a row, as a wave mask, and the same for the rate-bound test (none if it is off)
+        // the lanes that finish a row, as a wave mask, and the same for the rate-bound test (none if it is off: a kernel that
+        // holds one wave body runs the one with the test for every launch)
         const unsigned long long finmask = __builtin_amdgcn_ballot_w64(fin);
-        const unsigned long long hardmask = a.st.check_hard ? finmask : 0ull;
+        const unsigned long long hardmask = (HARD && a.st.check_hard) ? finmask : 0ull;
         // log2 k of the power law in a VGPR for the whole loop (v_fma takes one SGPR operand, and that is n)
         IoConsts<T> io = a.io;
         asm volatile("" : "+v"(io.log2k));
@@ -180,35 +200,51 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
                     }
                 }
             }
+            // BANK: the transpose-reduce stands right behind the FMA block, in front of the verdict and the loop's branch, so
+            // that the loop carries the lane's row total (in acc[0][0]) and not the accumulators; the one of a step that is
+            // never taken is discarded with its FMA block
+            if constexpr (BANK) acc[0][0] = reduce_bank_f32<RA>(acc[0], lane);
         };
         // keeps the consumption of the verdict word BELOW the FMA block (see the general loop)
         auto verdict = [&](int fl, T (&acc)[1][8]) {
             asm volatile("" : "+v"(fl));
 #pragma unroll
-            for (int r = 0; r < RA; ++r) asm volatile("" : "+v"(acc[0][r]));
+            for (int r = 0; r < (BANK ? 1 : RA); ++r) asm volatile("" : "+v"(acc[0][r]));
             return __builtin_amdgcn_readfirstlane(fl);
         };
         // go on <=> some wave has a row that is still moving and no wave has a row at the rate bound
         auto stops = [](int fu) { return !(fu & 0x01010101) || (fu & 0x02020202); };
         int stopword = 1;
+        unsigned last0 = 0, last1 = 0;          // the verdict byte this wave stored last, per parity
         // One step of the loop rotated by half a step, for the parity PAR of the buffer that holds x_k = xc: [reduce, Euler
         // update and stop tests of step k: the new state xn goes to the OTHER buffer, the wave's verdict to its byte of word
         // PAR; barrier; verdict word of step k; FMA block of step k + 1; verdict].  Returns "the loop ends here": on the
         // verdict of the step just taken or at max_iter, where the FMA block of a step that is never taken is discarded
-        // just as after a stop.
+        // just as after a stop.  HARD: the launch tests the rate bound (without it the body holds no compare against hard_stop,
+        // and bit 1 of the byte is never set).
         auto half_step = [&](auto par, const T xc, T& xn, T (&acc)[1][8]) {
             constexpr unsigned PAR = decltype(par)::value;
-            const T u = reduce_rows_to_lane<RA, T, OPAIR || SIXROW>(acc[0], cg);
+            T u;
+            if constexpr (BANK) u = acc[0][0];
+            else u = reduce_rows_to_lane<RA, T, OPAIR || SIXROW>(acc[0], cg);
             const T r1 = xc + (-xc + io_eval(u + ex[0], io)) * eps;
             // the two compares as wave masks (a NaN row counts as not moving), ANDed with the masks of the lanes that report
             const unsigned long long moving = __builtin_amdgcn_ballot_w64(abs_t(r1 - xc) >= a.st.atol);
-            const unsigned long long beyond = __builtin_amdgcn_ballot_w64(r1 >= a.st.hard_stop);
             // (Lane counts, 0 .. 64, carried into bit 6: integer arithmetic on uniform values stays on the scalar unit, and
             // the byte then costs the vector port the one v_mov that the store needs.  Written as two tests of the masks, the
             // compiler forms it with a vector select and a vector or.)
-            const unsigned nm = __builtin_popcountll(moving & finmask), nb = __builtin_popcountll(beyond & hardmask);
-            const unsigned mine = ((nm + 63u) >> 6) | (((nb + 63u) >> 5) & 2u);
-            *(LdsB)(size_t)(fwr + 4 * PAR) = (unsigned char)mine;
+            const unsigned nm = __builtin_popcountll(moving & finmask);
+            unsigned mine = (nm + 63u) >> 6;
+            if constexpr (HARD) {
+                const unsigned long long beyond = __builtin_amdgcn_ballot_w64(r1 >= a.st.hard_stop);
+                const unsigned nb = __builtin_popcountll(beyond & hardmask);
+                mine |= ((nb + 63u) >> 5) & 2u;
+            }
+            unsigned& last = PAR ? last1 : last0;
+            if (__builtin_expect(mine != last, 0)) {
+                *(LdsB)(size_t)(fwr + 4 * PAR) = (unsigned char)mine;
+                last = mine;
+            }
             if (FLAT || fin) *(LdsF)(size_t)(sst + (unsigned)sizeof(T) * ((PAR ^ 1) * BUF)) = r1;
             xn = r1;
             __syncthreads();
@@ -229,6 +265,14 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
                 if (half_step(std::integral_constant<unsigned, 0>{}, xe, xo, acc)) { cur = 1; break; }
                 if (half_step(std::integral_constant<unsigned, 1>{}, xo, xe, acc)) { cur = 0; break; }
             }
+        }
+        // BANK: the final stores take their row from the LDS address of the lane's state slot, which the loop keeps anyway
+        // (slot = (row / C) CP + row % C in the lanes that finish a row, the only ones that store): the 64-bit element index
+        // of the prologue's load is then not kept across the loop, which has no register for it.
+        if constexpr (BANK) {
+            unsigned slot = (sst - (unsigned)(size_t)(LdsV)rb0) / (unsigned)sizeof(T);
+            asm volatile("" : "+v"(slot));
+            outrow = (int)((slot / CP) * C + slot % CP);
         }
         // code and step count once, from the word that ended the loop
         if (stops(stopword)) { code[0] = (stopword & 0x01010101) ? 2 : 0; nsteps[0] = step; }
@@ -340,8 +384,8 @@ __device__ __forceinline__ void tile_wave_body(const SolveArgs<T>& a, T* wlds, T
         if (!live[s]) continue;
         const size_t vec = ((size_t)b * a.NB + s0 + s) * M;
         if (fin) {
-            a.r[vec + myrow] = rc[s];
-            if (a.r_prev) a.r_prev[vec + myrow] = rp[s];
+            a.r[vec + outrow] = rc[s];
+            if (a.r_prev) a.r_prev[vec + outrow] = rp[s];
         }
         if (threadIdx.x == 0) {
             a.codes[(size_t)b * a.NB + s0 + s] = code[s];
@@ -379,8 +423,15 @@ __global__ void __launch_bounds__(64 * NW, MINWAVES) solve_tile_mixed_kernel(Sol
     __shared__ int flags[tile_flag_words<T, NB>()][NB];
     set_rank_priority((blockIdx.x >> 8) % 3);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (wave < NW - 1) tile_wave_body<T, 7, C, RL, NB, false>(a, wlds, rbuf, flags, (8 * wave + (lane >> 3)) * 7, threadIdx.x);
-    else tile_wave_body<T, LRA, C, 0, NB, true>(a, wlds, rbuf, flags, 56 * (NW - 1) + (lane >> 3) * LRA, threadIdx.x);
+    auto body = [&](auto hard) {
+        constexpr bool HARD = decltype(hard)::value;
+        if (wave < NW - 1)
+            tile_wave_body<T, 7, C, RL, NB, false, -1, 0, false, HARD>(a, wlds, rbuf, flags, (8 * wave + (lane >> 3)) * 7, threadIdx.x);
+        else
+            tile_wave_body<T, LRA, C, 0, NB, true, -1, 0, false, HARD>(a, wlds, rbuf, flags, 56 * (NW - 1) + (lane >> 3) * LRA, threadIdx.x);
+    };
+    if (tile_hard_split<T, NB, C == 25 && RL == 2>() && !a.st.check_hard) body(std::false_type{});
+    else body(std::true_type{});
 }
 
 // 2N = 170..200 (C = 25, four waves): rows split 56/48/48/48.  Wave 0 runs the 7-row tile of the heavy waves above, waves 1-3 a
@@ -402,9 +453,16 @@ __global__ void __launch_bounds__(256, MINWAVES) solve_tile_mixed6_kernel(SolveA
     __shared__ int flags[tile_flag_words<T, NB>()][NB];
     set_rank_priority((blockIdx.x >> 8) % 3);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (wave == 0) tile_wave_body<T, 7, C, 2, NB, false, -1, 64>(a, wlds, rbuf, flags, (lane >> 3) * 7, lane);
-    else tile_wave_body<T, 6, C, 2, NB, false, KV, 64>(a, wlds + HEAVY_ELEMS + (wave - 1) * SIX_ELEMS, rbuf, flags,
-                                                       56 + 48 * (wave - 1) + (lane >> 3) * 6, lane);
+    constexpr bool BANK = NB == 1 && sizeof(T) == 4 && !SSN_ABLATE;      // (the general loop keeps lane = 8*rg + cg)
+    const int rg = BANK ? bank_row_group(lane) : lane >> 3;
+    auto body = [&](auto hard) {
+        constexpr bool HARD = decltype(hard)::value;
+        if (wave == 0) tile_wave_body<T, 7, C, 2, NB, false, -1, 64, BANK, HARD>(a, wlds, rbuf, flags, rg * 7, lane);
+        else tile_wave_body<T, 6, C, 2, NB, false, KV, 64, BANK, HARD>(a, wlds + HEAVY_ELEMS + (wave - 1) * SIX_ELEMS, rbuf, flags,
+                                                                     56 + 48 * (wave - 1) + rg * 6, lane);
+    };
+    if (tile_hard_split<T, NB>() && !a.st.check_hard) body(std::false_type{});
+    else body(std::true_type{});
 }
 
 // ---------------------------------------------------------------------------------

@@ -150,6 +150,54 @@ template <>
 __device__ __forceinline__ float reduce8_to_lane<float>(const float (&acc)[8], int cg) { return reduce8_f32<8>(acc, cg); }
 #endif
 
+// fp32 tiles of 7 or 6 rows with the column-group bits on lane bits 2, 3 and 0 (the waves of solve_tile_mixed6_kernel): lane l
+// with bits b5 .. b0 is row group b1 | b4 << 1 | b5 << 2 and owns the columns of group bank_col_group(l) =
+// ((b3 << 1) | b0) ^ (b2 ? 7 : 0).  Bits 2 and 3 of the lane index are both DPP bank bits (a bank is four lanes of a row of 16),
+// so the first two exchanges make their keep / send choice with bank masks and need no selects:
+//   over bit 2, per pair of rows (k, k + 4), v_add_f32_dpp row_shl:4 under bank_mask 0x5 (lanes with b2 = 0 keep row k: own +
+//   lane l + 4) and row_shr:4 under bank_mask 0xa (lanes with b2 = 1 keep row k + 4: own + lane l - 4).  (row_half_mirror would
+//   flip bit 1 as well, which belongs to the row group now.)
+//   over bit 3, row_ror:8: one full add (row k) and one under bank_mask 0xc (lanes with b3 = 1: row k + 2).
+// The third, over bit 0, keeps its two selects.  7 + 4 + 3 = 14 instructions for 7 rows and 6 + 4 + 3 = 13 for 6, where
+// reduce8_f32 has 16 and 15.  The bit-2 partner owns group 7 - c, the bit-3 partner c ^ 2, the bit-0 partner c ^ 1: every row
+// total is the tree of the same fp32 pairs as in reduce8_f32, ((c, 7 - c), then ^ 2, then ^ 1), bit for bit.
+// Lane l ends with the total of row bank_row(l) = 4 b2 + 2 b3 + b0 of its row group; with a value nobody may use where the
+// tile has no such row (the rows that are not formed: 7, or 6 and 7, and in the lanes with b2 = 1 what stands in for them).
+// The first two exchanges are one statement: its s_nop gives the first DPP reads their two wait states behind the producing
+// FMAs, and the order of the adds puts two instructions between every write and the DPP read of it.
+__device__ __forceinline__ int bank_col_group(int l) { return (((l >> 2) & 2) | (l & 1)) ^ ((l & 4) ? 7 : 0); }
+__device__ __forceinline__ int bank_row_group(int l) { return ((l >> 1) & 1) | ((l >> 3) & 6); }
+__device__ __forceinline__ int bank_row(int l) { return (l & 4) | ((l >> 2) & 2) | (l & 1); }
+template <int ROWS>
+__device__ __forceinline__ float reduce_bank_f32(const float (&acc)[8], int lane) {
+    static_assert(ROWS == 7 || ROWS == 6, "the 7- and 6-row waves");
+    // In place: a masked add leaves the lanes it does not write as they are, and those are the lanes its partner add reads.
+    float a0 = acc[0], a1 = acc[1], a2 = acc[2], a3 = acc[3];
+#define SSN_DPP_LO(a) "v_add_f32_dpp %[" a "], %[" a "], %[" a "] row_shl:4 row_mask:0xf bank_mask:0x5\n"
+#define SSN_DPP_HI(r, a) "v_add_f32_dpp %[" r "], %[" a "], %[" a "] row_shr:4 row_mask:0xf bank_mask:0xa\n"
+#define SSN_DPP_ALL(a) "v_add_f32_dpp %[" a "], %[" a "], %[" a "] row_ror:8 row_mask:0xf bank_mask:0xf\n"
+#define SSN_DPP_UP(r, a) "v_add_f32_dpp %[" r "], %[" a "], %[" a "] row_ror:8 row_mask:0xf bank_mask:0xc\n"
+#define SSN_DPP_BIT3 SSN_DPP_ALL("a0") SSN_DPP_ALL("a1") SSN_DPP_UP("a0", "a2") SSN_DPP_UP("a1", "a3")
+    if constexpr (ROWS == 7)
+    asm("s_nop 1\n" SSN_DPP_LO("a3") SSN_DPP_LO("a2") SSN_DPP_LO("a0") SSN_DPP_LO("a1")
+        SSN_DPP_HI("a0", "a4") SSN_DPP_HI("a1", "a5") SSN_DPP_HI("a2", "a6") SSN_DPP_BIT3
+        : [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2), [a3] "+v"(a3) : [a4] "v"(acc[4]), [a5] "v"(acc[5]), [a6] "v"(acc[6]));
+    else
+    asm("s_nop 1\n" SSN_DPP_LO("a0") SSN_DPP_LO("a1") SSN_DPP_HI("a0", "a4") SSN_DPP_HI("a1", "a5")
+        SSN_DPP_LO("a2") SSN_DPP_LO("a3") SSN_DPP_BIT3
+        : [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2), [a3] "+v"(a3) : [a4] "v"(acc[4]), [a5] "v"(acc[5]));
+#undef SSN_DPP_BIT3
+#undef SSN_DPP_UP
+#undef SSN_DPP_ALL
+#undef SSN_DPP_HI
+#undef SSN_DPP_LO
+    const float n2[2] = {a0, a1};
+    const bool b0 = lane & 1;
+    const float keep = b0 ? n2[1] : n2[0];
+    const float send = b0 ? n2[0] : n2[1];
+    return keep + dpp_get_f<0xB1>(send);                // quad_perm:[1,0,3,2]: lane i <-> i^1
+}
+
 // Tiles of at most 4 rows (acc[4..7] == 0): the first exchange only has to fold the two halves of the lane group
 // together -- four DPP adds, no second masked add, no zero inputs to materialise; lanes 0-3 end with rows 0-3.
 // TRIM (fp32 tiles of 7 or 6 rows): no zero rows are formed and folded in; lanes cg >= ROWS end with values nobody may use.
