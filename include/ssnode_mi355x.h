@@ -114,8 +114,8 @@ int ssn_solve_batch_f64(const double *W, const double *ext, int ext_per_draw,
                         int B, int NB, int M, const ssn_solver_params *p, void *stream);
 /* Force a kernel variant (testing / A-B benchmarking): 0 = generic streaming
  * kernel, 1 = register-stationary DPP kernel, 2 = register-stationary tile kernel
- * (shape chosen by the library), 3 = tile kernel with split VGPR/LDS residency,
- * 4 = tile kernel with the whole tile in VGPRs, 5 = fp32 MFMA kernel (NB >= 4), 6 = fp16-split MFMA kernel
+ * (shape chosen by the library), 3 = tile kernel with split VGPR/LDS residency where that is instantiated (what the
+ * library chooses for 2 as well: the two are the same launch), 4 = tile kernel with the whole tile in VGPRs, 5 = fp32 MFMA kernel (NB >= 4), 6 = fp16-split MFMA kernel
  * (NB >= 4, asym_tanh, dt <= tau: W and the state carried as two fp16 parts each, exact products, all 8 stimuli in one
  * chain per step), 7 = the same in the alternating two-group form (state as three parts, exact), 8 = fp16-split kernel
  * with two draws per workgroup (csrc/ssn_duo.hip; what the automatic choice takes for more than 256 (draw, 8 stimuli)

@@ -117,10 +117,10 @@ def grouping(NB):
 def kernel_of(c, variant):
     """(family, grid, shape) of the kernel a supported (case, variant) launches -- the launchers restated:
     ssn_capi.hip::solve_batch_impl, ssn_tile.hip::launch_tile_nb, ssn_solver.hip::launch_regw_nb, ssn_mfma*.hip, ssn_duo.hip.
-    family: 'stream', 'regw', 'tile split', 'tile mixed', 'tile all-register', 'mfma', 'wide', 'alternating', 'duo' (fp64:
-    'fp64 stream', 'fp64 regw', 'fp64 tile'); grid: the step of the family's size ladder; shape: the stimuli per workgroup
-    the template is instantiated for (tile, register-stationary), the rows per lane of the last wave (mixed) or the grouping
-    of the stimuli (variants 5-8)."""
+    family: 'stream', 'regw', 'tile split', 'tile mixed', 'tile mixed6', 'tile all-register', 'mfma', 'wide', 'alternating',
+    'duo' (fp64: 'fp64 stream', 'fp64 regw', 'fp64 tile'); grid: the step of the family's size ladder; shape: the stimuli per
+    workgroup the template is instantiated for (tile, register-stationary), the rows per lane of the last wave (mixed), the
+    rows of the four waves (mixed6) or the grouping of the stimuli (variants 5-8)."""
     assert supported(c, variant)
     fp32 = c.dtype == 'float32'
     if variant is None:                    # B = 3 is far from filling the chip: tile, register-stationary, streaming
@@ -137,7 +137,9 @@ def kernel_of(c, variant):
             return 'fp64 tile', C, 1
         waves = (c.M + 55) // 56
         last_rows = c.M - 56 * (waves - 1)
-        if variant != 4 and C in (19, 25):
+        if variant != 4 and C in (19, 25):               # variants 2 and 3 are the same choice: split where instantiated
+            if C == 25 and c.NB == 1 and c.M >= 170:     # (ssn_tile.hip: TILE_MIXED6_MIN_M)
+                return 'tile mixed6', C, 'rows 56/48/48/48'
             if (C == 25 and waves == 4 and last_rows <= 32) or (C == 19 and waves == 3 and last_rows <= 40):
                 return 'tile mixed', C, 'last wave %d rows per lane' % (4 if last_rows <= 32 else 5)
             return 'tile split', C, 1
@@ -170,7 +172,8 @@ def coverage():
     need += [('fp64 regw', k, nbt) for k in KCH64 for nbt in ((1, 2) if k < 7 else (1,))]
     need += [('tile all-register', C, nbt) for C in C32 for nbt in ((1, 2, 4) if C <= 19 else (1, 2))]
     need += [('tile split', 19, 1), ('tile split', 25, 1), ('tile mixed', 19, 'last wave 4 rows per lane'),
-             ('tile mixed', 19, 'last wave 5 rows per lane'), ('tile mixed', 25, 'last wave 4 rows per lane')]
+             ('tile mixed', 19, 'last wave 5 rows per lane'), ('tile mixed', 25, 'last wave 4 rows per lane'),
+             ('tile mixed6', 25, 'rows 56/48/48/48')]
     need += [('fp64 tile', C, 1) for C in C64]
     need += [('mfma', mk, g) for mk in (104, 152, 200, 208) for g in GROUPINGS]
     need += [(f, mk, g) for f in ('wide', 'alternating', 'duo') for mk in (104, 152, 208) for g in GROUPINGS]

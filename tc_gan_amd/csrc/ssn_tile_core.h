@@ -4,18 +4,9 @@
 #include <hip/hip_runtime.h>
 #include "ssn_device.h"
 
-// Diagnostic builds only (tools/microbench/tile_ablate.hip): bit mask of loop phases to stub out so that
-// their cost can be measured.  The product library is always built with SSN_ABLATE == 0.
-#ifndef SSN_ABLATE
-#define SSN_ABLATE 0
-#endif
 // diagnostic switch: 0 no wave priorities, 2 static priority per workgroup rank (product setting)
 #ifndef SSN_PRIO_MODE
 #define SSN_PRIO_MODE 2
-#endif
-// diagnostic switch: 0 = leave the packed FMAs of the split tile to the compiler (A/B builds), 1 = asm with op_sel broadcast
-#ifndef SSN_PK_ASM
-#define SSN_PK_ASM 1
 #endif
 #ifndef SSN_REDUCE4
 #define SSN_REDUCE4 1            // diagnostic: 0 = 8-row transpose-reduce also for tiles of <= 4 rows
@@ -23,31 +14,7 @@
 
 namespace ssn {
 
-// x + (x from the lane selected by a DPP control); folds to v_add_f32_dpp.
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x) {
-    const float y = __builtin_bit_cast(
-        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
-    return x + y;
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp_add(double x) {
-    const long long b = __builtin_bit_cast(long long, x);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, true);
-    return x + __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-// Sum over the 8 adjacent lanes {8k .. 8k+7}; every lane ends with the total.
-template <typename T>
-__device__ __forceinline__ T sum8(T x) {
-    x = dpp_add<0xB1>(x);    // quad_perm:[1,0,3,2]
-    x = dpp_add<0x4E>(x);    // quad_perm:[2,3,0,1]
-    x = dpp_add<0x141>(x);   // row_half_mirror
-    return x;
-}
-
-template <int CTRL, typename T>
-__device__ __forceinline__ T dpp_get(T x);
+// x from the lane selected by a DPP control
 template <int CTRL>
 __device__ __forceinline__ float dpp_get_f(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
@@ -96,7 +63,6 @@ __device__ __forceinline__ T reduce8_to_lane(const T (&acc)[8], int cg) {
 // row group it finishes no row (fin = cg < RA).  Lanes 0-6 hold the same bits as with a zero row.
 // ROWS = 6: the same with two masked adds (rows 4 and 5).  Lanes 4-7 then keep sums of rows 2 and 3 where rows 6 and 7 would
 // stand; the second exchange leaves them in lanes 6 and 7 only, which finish no row: lanes 0-5 hold the bits of two zero rows.
-#ifndef SSN_REDUCE_PLAIN
 template <int ROWS>
 __device__ __forceinline__ float reduce8_f32(const float (&acc)[8], int cg) {
     static_assert(ROWS >= 6 && ROWS <= 8, "8 rows, or 7 or 6 rows without zero rows");
@@ -148,7 +114,6 @@ __device__ __forceinline__ float reduce8_f32(const float (&acc)[8], int cg) {
 }
 template <>
 __device__ __forceinline__ float reduce8_to_lane<float>(const float (&acc)[8], int cg) { return reduce8_f32<8>(acc, cg); }
-#endif
 
 // fp32 tiles of 7 or 6 rows with the column-group bits on lane bits 2, 3 and 0 (the waves of solve_tile_mixed6_kernel): lane l
 // with bits b5 .. b0 is row group b1 | b4 << 1 | b5 << 2 and owns the columns of group bank_col_group(l) =
@@ -203,9 +168,7 @@ __device__ __forceinline__ float reduce_bank_f32(const float (&acc)[8], int lane
 // TRIM (fp32 tiles of 7 or 6 rows): no zero rows are formed and folded in; lanes cg >= ROWS end with values nobody may use.
 template <int ROWS, typename T, bool TRIM = false>
 __device__ __forceinline__ T reduce_rows_to_lane(const T (&acc)[8], int cg) {
-#ifndef SSN_REDUCE_PLAIN
     if constexpr (TRIM && (ROWS == 7 || ROWS == 6) && sizeof(T) == 4) return reduce8_f32<ROWS>(acc, cg);
-#endif
     if constexpr (ROWS > 4 || sizeof(T) != 4 || !SSN_REDUCE4) {
         return reduce8_to_lane(acc, cg);
     } else {
@@ -338,31 +301,29 @@ template <int RA, int C, int RL> struct TileSplit {
 // OP (fp32 solver, C = 4k + 1): the odd row is held as PAIRS of columns, (o[c], o[c+1]) for even c, which is how the
 // 16-byte read leaves r: one plain v_pk_fma_f32 per two columns into a two-float accumulator (even columns in one half,
 // odd columns in the other), column C - 1 with one FMA into the low half, the row's partial sum = low + high.
-// KV >= 0 (fp32 solver, tiles of two register row pairs and one LDS-resident pair, 6 rows): the one-statement forms for a tile
+// KV > 0 (fp32 solver, tiles of two register row pairs and one LDS-resident pair, 6 rows): the one-statement forms for a tile
 // without an odd row, and columns [0, KV) of the LDS-resident pair held in VGPRs as well (KV a multiple of 4: whole quads).
 // The LDS image then holds columns KV .. C - 1 only.
 // WSO: lanes per unit of the LDS image when it is not the TileSplit's (an image of one wave: 64, tid = the lane).
-template <typename T, int RA, int C, int RL, bool OP = false, int KV = -1, int WSO = 0> struct SplitTile {
+// The solver's waves take OP and KV from their TileWave (ssn_tile.hip); the generator kernels use the plain form.
+template <typename T, int RA, int C, int RL, bool OP = false, int KV = 0, int WSO = 0> struct SplitTile {
     using S = TileSplit<RA, C, RL>;
     static constexpr int RR = S::RR, NP = RR / 2, ODD = RR % 2;
-    static_assert(!OP || (sizeof(T) == 4 && ODD && NP == 2 && C % 4 == 1 && C >= 5), "odd row in column pairs: 5 register rows, whole quads + one column");
-    static constexpr bool SIX = KV >= 0;
-    static constexpr int KR = SIX ? KV : 0;                       // columns of the LDS-resident rows that stay in VGPRs
-    static_assert(!SIX || (sizeof(T) == 4 && !OP && !ODD && NP == 2 && RL == 2 && KV % 4 == 0 && KV < C), "two register row pairs + one split pair");
+    static_assert(!OP || (sizeof(T) == 4 && ODD && NP == 2 && RL == 2 && C % 4 == 1 && C >= 5),
+                  "odd row in column pairs: 5 register rows and 2 in LDS, whole quads + one column");
+    static_assert(KV >= 0 && KV % 4 == 0, "whole quads of the LDS-resident pair in VGPRs, or none");
+    static constexpr bool SIX = KV > 0;
+    static_assert(!SIX || (sizeof(T) == 4 && !OP && !ODD && NP == 2 && RL == 2 && C % 4 == 1 && KV + 4 <= C),
+                  "two register row pairs + one split pair: whole quads and one last column, behind at least one quad from LDS");
     static constexpr int WS = WSO ? WSO : S::WS;
-    static constexpr int NLV = RL * (C - KR), NU = (NLV + 3) / 4; // values and units of the LDS image per lane
-    // KV = 0: a half-empty last unit is stored and read as 8 bytes, lanes 8 bytes apart (four whole images of 13 x 16 bytes
-    // per lane do not fit three workgroups per CU); it costs one more address VGPR, which the tile with KV = 12 does not have
-    static constexpr bool HALF = SIX && KV == 0 && NLV % 4 == 2;
-    static constexpr int NUF = NU - (HALF ? 1 : 0);
-    static constexpr int lds_elems(int wg) { return NU == 0 ? 4 : HALF ? NUF * WS * 4 + wg * 2 : ((NU - 1) * WS + wg) * 4; }
+    static constexpr int NLV = RL * (C - KV), NU = (NLV + 3) / 4; // values and units of the LDS image per lane
+    static constexpr int lds_elems(int wg) { return NU == 0 ? 4 : ((NU - 1) * WS + wg) * 4; }
     using V2 = T __attribute__((ext_vector_type(2)));
     using V4 = T __attribute__((ext_vector_type(4)));
     V2 p[NP > 0 ? NP : 1][C];      // p[k][c] = (W[row 2k][c], W[row 2k+1][c])
     T o[ODD && !OP ? C : 1];       // last register row when RR is odd (OP: its last column only)
     V2 oc[OP ? C / 2 : 1];         // OP: oc[j] = (W[odd row][2j], W[odd row][2j+1])
-    V2 pv[KR > 0 ? KR : 1];        // KV: pv[c] = (W[row RR][c], W[row RR+1][c]), c < KV
-    unsigned wh;                   // HALF: LDS byte address of the image + 8 * tid (the 8-byte units lie 8 bytes apart)
+    V2 pv[SIX ? KV : 1];           // KV: pv[c] = (W[row RR][c], W[row RR+1][c]), c < KV
 
     template <bool TRANSPOSED>
     __device__ __forceinline__ void load(const T* A, int M, int rowbase, int colbase, T* wl, int tid) {
@@ -395,8 +356,6 @@ template <typename T, int RA, int C, int RL, bool OP = false, int KV = -1, int W
 #pragma unroll
             for (int c = 0; c < C; ++c) t[c] = (row < M && c < ncol) ? t[c] : (T)0;
         };
-        using LdsT = const __attribute__((address_space(3))) T*;
-        if constexpr (HALF) wh = (unsigned)(size_t)(LdsT)(wl + tid * 2);
         // LDS rows first, fenced off from the register rows (fewer values in flight at once)
         if (RL > 0 && tid < WS) {
             T t[RL > 0 ? RL : 1][C];
@@ -407,20 +366,15 @@ template <typename T, int RA, int C, int RL, bool OP = false, int KV = -1, int W
                 T v[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const int j = 4 * k + e, c = KR + j / (RL > 0 ? RL : 1), rl = j % (RL > 0 ? RL : 1);
+                    const int j = 4 * k + e, c = KV + j / (RL > 0 ? RL : 1), rl = j % (RL > 0 ? RL : 1);
                     v[e] = (j < NLV) ? t[rl][c] : (T)0;
                 }
-                if (HALF && k == NU - 1) {
-                    V2 q; q.x = v[0]; q.y = v[1];
-                    *reinterpret_cast<V2*>(&wl[(size_t)NUF * WS * 4 + tid * 2]) = q;
-                } else {
-                    V4 q; q.x = v[0]; q.y = v[1]; q.z = v[2]; q.w = v[3];
-                    *reinterpret_cast<V4*>(&wl[((size_t)k * WS + tid) * 4]) = q;
-                }
+                V4 q; q.x = v[0]; q.y = v[1]; q.z = v[2]; q.w = v[3];
+                *reinterpret_cast<V4*>(&wl[((size_t)k * WS + tid) * 4]) = q;
             }
-            if constexpr (KR > 0) {        // (tid < WS holds for every lane of an image with columns in VGPRs)
+            if constexpr (SIX) {           // (tid < WS holds for every lane of an image with columns in VGPRs)
 #pragma unroll
-                for (int c = 0; c < KR; ++c) { pv[c].x = t[0][c]; pv[c].y = t[1][c]; }
+                for (int c = 0; c < KV; ++c) { pv[c].x = t[0][c]; pv[c].y = t[1][c]; }
             }
         }
         asm volatile("" ::: "memory");
@@ -533,12 +487,102 @@ template <typename T, int RA, int C, int RL, bool OP = false, int KV = -1, int W
 #undef SSN_PK_STMT
 #undef SSN_PK_IN
 
+    // Per-stimulus partial sums of one matvec: the register row pairs, the odd row (ao2 with OP: even columns in .x, odd
+    // columns in .y) and the LDS-resident rows (two: al2, one: al1).
+    struct Sums { V2 a2[NP > 0 ? NP : 1], al2, ao2; T ao, al1; };
+    // acc (op)= w2 * (r, r), r = element e of the 16-byte read (rlo, rhi).  fp32: r is taken from ONE half of the aligned
+    // register pair the read left it in (op_sel broadcasts the low or the high half to both lanes of v_pk_fma_f32).  Written
+    // as asm because the compiler, short of registers, copies every fourth r into a fresh pair first (one v_mov per quad and
+    // accumulator group: ~15 of ~190 instructions per step).  fp64 has no packed form.
+    // first (MUL0): acc = w2 * (r, r), the chain's first product (column 0 is the low half of the low pair)
+    template <bool MUL0>
+    static __device__ __forceinline__ void pk_bcast(V2& acc, const V2& w2, const V2& rlo, const V2& rhi, int e, bool first = false) {
+        if constexpr (MUL0) {
+            if (first) { asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(acc) : "v"(w2), "v"(rlo)); return; }
+        }
+        if constexpr (sizeof(T) == 4) {
+            if (e == 0) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(w2), "v"(rlo));
+            else if (e == 1) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(w2), "v"(rlo));
+            else if (e == 2) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(w2), "v"(rhi));
+            else asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(w2), "v"(rhi));
+        } else {
+            const T r = e == 0 ? rlo.x : e == 1 ? rlo.y : e == 2 ? rhi.x : rhi.y;
+            acc = __builtin_elementwise_fma(w2, (V2){r, r}, acc);
+        }
+    }
+
+    // Quad q of columns for one stimulus in the two one-statement forms (matvec_at chooses once per instantiation between
+    // them and the generic chains); rr = (rlo, rhi): the quad's x values, wu: the W units of the LDS image.
+    // The one-statement block of a tile with two register row pairs: with OP the odd row's column pairs inside it and the
+    // LDS-resident pair in lds_block behind it (the last column: single instructions); without OP (the light wave of the
+    // mixed kernels, no LDS-resident rows) an odd row as its own chain.
+    // (q is a constant once the loop is unrolled; the other branches fold away.  In the first quad under MUL0 the
+    // accumulator of the LDS-resident rows does not exist yet: no tie there.)
+    template <bool MUL0>
+    __device__ __forceinline__ void quad_block(Sums& a, int q, const T (&rr)[4], const V2& rlo, const V2& rhi, const V4* wu) const {
+        static_assert(NP == 2 && (OP || RL == 0), "two register row pairs; LDS-resident rows only behind the odd row in column pairs");
+        const int nc = C - 4 * q < 4 ? C - 4 * q : 4;
+        const V2 *w0 = &p[0][4 * q], *w1 = &p[1][4 * q], *wo = &oc[OP ? 2 * q : 0];
+        V2 &x0 = a.a2[0], &x1 = a.a2[1], &xo = a.ao2, &t = a.al2;
+        if (MUL0 && q == 0) {
+            if (nc == 1) pk_block<1, true, false>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+            else if (nc == 2) pk_block<2, true, false>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+            else if (nc == 3) pk_block<3, true, false>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+            else pk_block<4, true, false, OP>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+        } else {
+            if (nc == 1) pk_block<1, false, RL == 2>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+            else if (nc == 2) pk_block<2, false, RL == 2>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+            else if (nc == 3) pk_block<3, false, RL == 2>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+            else pk_block<4, false, RL == 2, OP>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
+        }
+        if constexpr (OP) {
+            if (nc == 4) {
+                if (MUL0 && q == 0) lds_block<true>(t, wu[2 * q], wu[2 * q + 1], rlo, rhi);
+                else lds_block<false>(t, wu[2 * q], wu[2 * q + 1], rlo, rhi);
+            } else {
+                // column C - 1 into the low half, then the two halves: the odd row's partial sum
+                a.ao = fma(o[0], rr[0], a.ao2.x) + a.ao2.y;
+                const int j = (C - 1) * 2;
+                pk_bcast<MUL0>(t, (V2){wu[j / 4][j % 4], wu[j / 4][j % 4 + 1]}, rlo, rhi, 0);
+            }
+        } else if (ODD) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int c = 4 * q + e;
+                if (c < C) a.ao = (MUL0 && c == 0) ? o[c] * rr[e] : fma(o[c], rr[e], a.ao);
+            }
+        }
+    }
+    // The 6-row form.  Whole quads below KV: three register chains; then the two register pairs with the split pair's
+    // accumulator tied behind them, and the split pair from its two W units (the last column: from the half-filled one).
+    template <bool MUL0>
+    __device__ __forceinline__ void quad_six(Sums& a, int q, const T (&rr)[4], const V2& rlo, const V2& rhi, const V4* wu) const {
+        constexpr int QV = KV / 4;                            // quads of the split pair that come from VGPRs
+        const int nc = C - 4 * q < 4 ? C - 4 * q : 4;
+        const V2 *w0 = &p[0][4 * q], *w1 = &p[1][4 * q];
+        V2 &x0 = a.a2[0], &x1 = a.a2[1], &xo = a.ao2, &t = a.al2;
+        const bool first = MUL0 && q == 0;
+        if (q < QV) {
+            if (first) pk3_block<true>(x0, x1, t, w0, w1, &pv[SIX ? 4 * q : 0], rlo, rhi);
+            else pk3_block<false>(x0, x1, t, w0, w1, &pv[SIX ? 4 * q : 0], rlo, rhi);
+        } else {
+            const int k = (q - QV) * 2;
+            if (nc == 4) {
+                if (first) { pk_block<4, true, false>(x0, x1, xo, t, w0, w1, w0, rlo, rhi); lds_block<true>(t, wu[k], wu[k + 1], rlo, rhi); }
+                else { pk_block<4, false, true>(x0, x1, xo, t, w0, w1, w0, rlo, rhi); lds_block<false>(t, wu[k], wu[k + 1], rlo, rhi); }
+            } else {
+                pk_block<1, false, true>(x0, x1, xo, t, w0, w1, w0, rlo, rhi);
+                pk_bcast<MUL0>(t, (V2){wu[k].x, wu[k].y}, rlo, rhi, 0);
+            }
+        }
+    }
+
     // acc[s][a] = sum_c W[a][c] * x_s[col(cg, c)], rows a < RR from VGPRs, rows a >= RR from the LDS image.
     // Software pipeline per quad q of columns: issue the x reads of quad q+1 and the W units of quad q, run the
     // register FMAs of quad q (which cover the LDS latency), then the LDS-row FMAs.
-    // MODE (fp32 with SSN_PK_ASM only; 0 = the generator kernels' block): bit 0 = pk_block for a tile with two register row
-    // pairs (a tile with OP always asks for it: its odd row and, in lds_block, its LDS-resident rows are part of that form);
-    // bit 1 = the first product of every chain is a multiply, so no accumulator is zeroed first.  fma(w, r, +0) and
+    // MODE (fp32 only; 0 = the generator kernels' block): bit 0 = pk_block for a tile with two register row
+    // pairs (a tile with OP or KV always asks for it: its odd row and, in lds_block, its LDS-resident rows are part of that
+    // form); bit 1 = the first product of every chain is a multiply, so no accumulator is zeroed first.  fma(w, r, +0) and
     // w * r are the same bits unless the product is an exact zero of negative sign (+0 from the FMA, -0 from the
     // multiply); a chain can then end in -0 instead of +0 only if every one of its products is a zero, the
     // transpose-reduce adds it to the other partial sums (x + -0 = x, and -0 + +0 = +0), and a row whose partial sums are
@@ -560,13 +604,11 @@ template <typename T, int RA, int C, int RL, bool OP = false, int KV = -1, int W
     __device__ __forceinline__ void matvec_at(unsigned& xa, unsigned& wa, T (&acc)[NB][8]) const {
         constexpr int CP = SlabPad<C>::value;
         constexpr int NQ = (C + 3) / 4;
-        constexpr bool F32ASM = sizeof(T) == 4 && SSN_PK_ASM;
-        constexpr bool BLK = F32ASM && (MODE & 1) && NP == 2;
-        constexpr bool MUL0 = F32ASM && (MODE & 2);
+        constexpr bool BLK = sizeof(T) == 4 && (MODE & 1) && NP == 2;
+        constexpr bool MUL0 = sizeof(T) == 4 && (MODE & 2);
         static_assert(!OP || BLK, "the odd row in column pairs lives in the one-statement block");
         static_assert(!SIX || (BLK && NB == 1), "the 6-row forms are the fp32 NB = 1 solver's");
-        using LdsV2 = const __attribute__((address_space(3))) V2*;
-        constexpr int QV = KR / 4;                            // quads of the split pair that come from VGPRs
+        constexpr int QV = KV / 4;                            // quads of the split pair that come from VGPRs
         // Stage boundaries are enforced with data dependencies (an empty asm that "redefines" the LDS
         // addresses and the accumulators): the reads of stage q+1 cannot be hoisted above it, the FMAs of
         // stage q cannot sink below it.  __builtin_amdgcn_sched_barrier alone is not enough -- instruction
@@ -574,27 +616,21 @@ template <typename T, int RA, int C, int RL, bool OP = false, int KV = -1, int W
         // (~80 staging VGPRs).  The tied values are 32-bit LDS byte addresses: tying a generic pointer would
         // lose its address space and turn every ds_read into a flat_load.
         using LdsV4 = const __attribute__((address_space(3))) V4*;
-        V2 a2[NB][NP > 0 ? NP : 1], al2[NB], ao2[NB];     // ao2 (OP): odd row, even columns in .x, odd columns in .y
-        T ao[NB], al1[NB];
+        Sums a[NB];
         if constexpr (!MUL0) {
 #pragma unroll
             for (int s = 0; s < NB; ++s) {
 #pragma unroll
-                for (int k = 0; k < NP; ++k) a2[s][k] = (V2){(T)0, (T)0};
-                al2[s] = ao2[s] = (V2){(T)0, (T)0};
-                ao[s] = al1[s] = (T)0;
+                for (int k = 0; k < NP; ++k) a[s].a2[k] = (V2){(T)0, (T)0};
+                a[s].al2 = a[s].ao2 = (V2){(T)0, (T)0};
+                a[s].ao = a[s].al1 = (T)0;
             }
         }
         V4 rv[NQ][NB];
         V4 wu[NU > 0 ? NU : 1];
-        const int cg = threadIdx.x & 7;
-        const V4 stub = {(T)cg,(T)(cg + 1), (T)(cg + 2), (T)(cg + 3)};     // diagnostic builds (SSN_ABLATE) only
         auto load_quad = [&](int q) {
 #pragma unroll
-            for (int s = 0; s < NB; ++s) {
-                if constexpr (SSN_ABLATE & 8) rv[q][s] = stub;
-                else rv[q][s] = *(LdsV4)(size_t)(xa + (unsigned)sizeof(T) * (XOFF + s * 8 * CP + 4 * q));
-            }
+            for (int s = 0; s < NB; ++s) rv[q][s] = *(LdsV4)(size_t)(xa + (unsigned)sizeof(T) * (XOFF + s * 8 * CP + 4 * q));
         };
         load_quad(0);
 #pragma unroll
@@ -603,106 +639,39 @@ template <typename T, int RA, int C, int RL, bool OP = false, int KV = -1, int W
 #pragma unroll
             for (int uu = 0; uu < RL; ++uu) {                         // values 4*q*RL .. 4*(q+1)*RL - 1 (KV: of the image)
                 const int k = (q - QV) * RL + uu;
-                if (k >= 0 && k < NU) {
-                    if constexpr (SSN_ABLATE & 32) wu[k] = stub;
-                    else if (HALF && k == NU - 1) {
-                        // the 8-byte unit, behind the 16-byte ones
-                        const V2 h = *(LdsV2)(size_t)(wh + (unsigned)sizeof(T) * (NUF * WS * 4));
-                        wu[k].x = h.x; wu[k].y = h.y;
-                    } else wu[k] = *(LdsV4)(size_t)(wa + (unsigned)sizeof(T) * (k * WS * 4));
-                }
+                if (k >= 0 && k < NU) wu[k] = *(LdsV4)(size_t)(wa + (unsigned)sizeof(T) * (k * WS * 4));
             }
 #pragma unroll
             for (int s = 0; s < NB; ++s) {
+                // (r is used from the aligned register pairs the 16-byte read left it in)
                 const T rr[4] = {rv[q][s].x, rv[q][s].y, rv[q][s].z, rv[q][s].w};
-                // fp32: acc += w2 * (r, r) with r taken from ONE half of the aligned register pair the 16-byte read left it
-                // in (op_sel broadcasts the low or the high half to both lanes of v_pk_fma_f32).  Written as asm because
-                // the compiler, short of registers, copies every fourth r into a fresh pair first (one v_mov per quad and
-                // accumulator group: ~15 of ~190 instructions per step).
                 const V2 rlo = {rv[q][s].x, rv[q][s].y}, rhi = {rv[q][s].z, rv[q][s].w};
-                // first (MUL0): acc = w2 * (r, r), the chain's first product (column 0 is the low half of the low pair)
-                auto pk_bcast = [&](V2& acc, const V2& w2, int e, bool first = false) {
-                    if constexpr (MUL0) {
-                        if (first) { asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(acc) : "v"(w2), "v"(rlo)); return; }
-                    }
-                    if constexpr (sizeof(T) == 4 && SSN_PK_ASM) {
-                        if (e == 0) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(w2), "v"(rlo));
-                        else if (e == 1) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(w2), "v"(rlo));
-                        else if (e == 2) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(w2), "v"(rhi));
-                        else asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(w2), "v"(rhi));
-                    } else {
-                        acc = __builtin_elementwise_fma(w2, (V2){rr[e], rr[e]}, acc);
-                    }
-                };
-                if constexpr (SIX) {
-                    // whole quads below KV: three register chains; then the two register pairs with the split pair's
-                    // accumulator tied behind them, and the split pair from its two W units (the last column: from the half-filled one)
-                    const int nc = C - 4 * q < 4 ? C - 4 * q : 4;
-                    const V2 *w0 = &p[0][4 * q], *w1 = &p[1][4 * q];
-                    V2 &x0 = a2[s][0], &x1 = a2[s][1], &xo = ao2[s], &t = al2[s];
-                    const bool first = MUL0 && q == 0;
-                    if (q < QV) {
-                        if (first) pk3_block<true>(x0, x1, t, w0, w1, &pv[KR > 0 ? 4 * q : 0], rlo, rhi);
-                        else pk3_block<false>(x0, x1, t, w0, w1, &pv[KR > 0 ? 4 * q : 0], rlo, rhi);
-                    } else {
-                        const int k = (q - QV) * 2;
-                        if (nc == 4) {
-                            if (first) { pk_block<4, true, false>(x0, x1, xo, t, w0, w1, w0, rlo, rhi); lds_block<true>(t, wu[k], wu[k + 1], rlo, rhi); }
-                            else { pk_block<4, false, true>(x0, x1, xo, t, w0, w1, w0, rlo, rhi); lds_block<false>(t, wu[k], wu[k + 1], rlo, rhi); }
-                        } else {
-                            static_assert(C % 4 == 1 && 4 * QV + 4 <= C, "whole quads and one last column, behind at least one quad from LDS");
-                            pk_block<1, false, true>(x0, x1, xo, t, w0, w1, w0, rlo, rhi);
-                            pk_bcast(t, (V2){wu[k].x, wu[k].y}, 0);
+                if constexpr (SIX) quad_six<MUL0>(a[s], q, rr, rlo, rhi, wu);
+                else if constexpr (BLK) quad_block<MUL0>(a[s], q, rr, rlo, rhi, wu);
+                else {
+                    // the generic chains, one instruction per statement: the generator kernels' block (MODE = 0) and the
+                    // solver shapes without two register row pairs.  (In place: as a function of its own the same
+                    // statements are scheduled differently, and solve_tile_mixed_kernel at C = 19 takes two more VGPRs.)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int c = 4 * q + e;
+                        if (c < C) {
+#pragma unroll
+                            for (int k = 0; k < NP; ++k) pk_bcast<MUL0>(a[s].a2[k], p[k][c], rlo, rhi, e, c == 0);
+                            if (ODD) a[s].ao = (MUL0 && c == 0) ? o[c] * rr[e] : fma(o[c], rr[e], a[s].ao);
                         }
                     }
-                } else if constexpr (BLK) {
-                    // (q is a constant once the loop is unrolled; the other branches fold away.  In the first quad
-                    // under MUL0 the accumulator of the LDS-resident rows does not exist yet: no tie there.)
-                    const int nc = C - 4 * q < 4 ? C - 4 * q : 4;
-                    const V2 *w0 = &p[0][4 * q], *w1 = &p[1][4 * q], *wo = &oc[OP ? 2 * q : 0];
-                    V2 &x0 = a2[s][0], &x1 = a2[s][1], &xo = ao2[s], &t = al2[s];
-                    if (MUL0 && q == 0) {
-                        if (nc == 1) pk_block<1, true, false>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
-                        else if (nc == 2) pk_block<2, true, false>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
-                        else if (nc == 3) pk_block<3, true, false>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
-                        else pk_block<4, true, false, OP>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
-                    } else {
-                        if (nc == 1) pk_block<1, false, RL == 2>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
-                        else if (nc == 2) pk_block<2, false, RL == 2>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
-                        else if (nc == 3) pk_block<3, false, RL == 2>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
-                        else pk_block<4, false, RL == 2, OP>(x0, x1, xo, t, w0, w1, wo, rlo, rhi);
-                    }
-                }
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int c = 4 * q + e;
-                    if (c < C) {
-                        if constexpr (!BLK) {
-#pragma unroll
-                            for (int k = 0; k < NP; ++k) pk_bcast(a2[s][k], p[k][c], e, c == 0);
-                        }
-                        if constexpr (OP) {
-                            // column C - 1 into the low half, then the two halves: the row's partial sum
-                            if (c == C - 1) ao[s] = fma(o[0], rr[e], ao2[s].x) + ao2[s].y;
-                        } else if (ODD) ao[s] = (MUL0 && c == 0) ? o[c] * rr[e] : fma(o[c], rr[e], ao[s]);
-                    }
-                }
-                if constexpr (OP && RL == 2) {
-                    if (C - 4 * q >= 4) {
-                        if (MUL0 && q == 0) lds_block<true>(al2[s], wu[2 * q], wu[2 * q + 1], rlo, rhi);
-                        else lds_block<false>(al2[s], wu[2 * q], wu[2 * q + 1], rlo, rhi);
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int c = 4 * q + e;
-                    if (c < C && !SIX && !(OP && RL == 2 && C - 4 * q >= 4)) {
-                        if constexpr (RL == 2) {
-                            const int j = c * 2;
-                            const V2 wp = {wu[j / 4][j % 4], wu[j / 4][j % 4 + 1]};
-                            pk_bcast(al2[s], wp, e, c == 0);
-                        } else if constexpr (RL == 1) {
-                            al1[s] = (MUL0 && c == 0) ? wu[c / 4][c % 4] * rr[e] : fma(wu[c / 4][c % 4], rr[e], al1[s]);
+                    for (int e = 0; e < 4; ++e) {
+                        const int c = 4 * q + e;
+                        if (c < C) {
+                            if constexpr (RL == 2) {
+                                const int j = c * 2;
+                                const V2 wp = {wu[j / 4][j % 4], wu[j / 4][j % 4 + 1]};
+                                pk_bcast<MUL0>(a[s].al2, wp, rlo, rhi, e, c == 0);
+                            } else if constexpr (RL == 1) {
+                                a[s].al1 = (MUL0 && c == 0) ? wu[c / 4][c % 4] * rr[e] : fma(wu[c / 4][c % 4], rr[e], a[s].al1);
+                            }
                         }
                     }
                 }
@@ -711,11 +680,11 @@ template <typename T, int RA, int C, int RL, bool OP = false, int KV = -1, int W
 #pragma unroll
                 for (int s = 0; s < NB; ++s) {
 #pragma unroll
-                    for (int k = 0; k < NP; ++k) asm volatile("" : "+v"(a2[s][k]));
-                    if (OP) asm volatile("" : "+v"(ao2[s]));
-                    else if (ODD) asm volatile("" : "+v"(ao[s]));
-                    if (RL == 2) asm volatile("" : "+v"(al2[s]));
-                    if (RL == 1) asm volatile("" : "+v"(al1[s]));
+                    for (int k = 0; k < NP; ++k) asm volatile("" : "+v"(a[s].a2[k]));
+                    if (OP) asm volatile("" : "+v"(a[s].ao2));
+                    else if (ODD) asm volatile("" : "+v"(a[s].ao));
+                    if (RL == 2) asm volatile("" : "+v"(a[s].al2));
+                    if (RL == 1) asm volatile("" : "+v"(a[s].al1));
                 }
                 asm volatile("" : "+v"(xa), "+v"(wa));
             }
@@ -725,10 +694,10 @@ template <typename T, int RA, int C, int RL, bool OP = false, int KV = -1, int W
 #pragma unroll
             for (int r = 0; r < 8; ++r) acc[s][r] = (T)0;
 #pragma unroll
-            for (int k = 0; k < NP; ++k) { acc[s][2 * k] = a2[s][k].x; acc[s][2 * k + 1] = a2[s][k].y; }
-            if (ODD) acc[s][RR - 1] = ao[s];
-            if (RL == 2) { acc[s][RR] = al2[s].x; acc[s][RR + 1] = al2[s].y; }
-            if (RL == 1) acc[s][RR] = al1[s];
+            for (int k = 0; k < NP; ++k) { acc[s][2 * k] = a[s].a2[k].x; acc[s][2 * k + 1] = a[s].a2[k].y; }
+            if (ODD) acc[s][RR - 1] = a[s].ao;
+            if (RL == 2) { acc[s][RR] = a[s].al2.x; acc[s][RR + 1] = a[s].al2.y; }
+            if (RL == 1) acc[s][RR] = a[s].al1;
         }
     }
 };

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a second copy of libssnode.so with extra compiler flags into tools/ab/<tag>/ for A/B timing on ONE box:
-#   tools/ab_build.sh noasm -DSSN_PK_ASM=0     then   SSN_LIBDIR=tools/ab/noasm python bench.py ...
+#   tools/ab_build.sh kv8 -DSSN_TILE_KV=8     then   SSN_LIBDIR=tools/ab/kv8 python bench.py ...
 # Every file is compiled by tc_gan_amd/csrc/Makefile, with its flags for that file, and the extra ones behind them.
 set -e
 tag=$1; shift
