@@ -22,6 +22,13 @@
 //   fp32 path  v_mfma_f32_32x32x2_f32 (exact fp32 products) for parity tests.
 // The layer GEMMs here are tiny (batch x 11..512 x 512): they are launch/latency bound,
 // not MFMA bound; the tile is chosen for simplicity and full generality in the strides.
+//
+// Host code, in file order: gemm() with the split-K plan and the batched launch; one launch wrapper per small kernel; then the
+// passes -- a GemmArgs per role from one function each (gemm_layer / gemm_head / gemm_back / gemm_second / gemm_wgrad on
+// gemm_plain), offsets from CriticLayout, the workspace from carve_rows / carve_update, the weight-gradient GEMMs of an update
+// as one list (critic_weight_grads) that the chain path and the row-block path both issue from, critic_stage_inputs for the
+// input blocks of both, and critic_loss_grad = validate, carve, then critic_update_rows or critic_wasserstein_half +
+// critic_penalty_half between CriticFork::Scope's fork and join.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <type_traits>
@@ -411,6 +418,11 @@ hipError_t critic_splitk_flush(hipStream_t st) {
 struct GemmBatch { bool on; int blocks; GemmBatchArgs b; };
 static thread_local GemmBatch tl_batch{false, 0, {}};
 static void gemm_batch_begin() { tl_batch.on = true; tl_batch.blocks = 0; tl_batch.b.n = 0; tl_batch.b.first[0] = 0; }
+// begins a batch if asked to; no batch is left open on any way out of the scope
+struct GemmBatchScope {
+    explicit GemmBatchScope(bool begin) { if (begin) gemm_batch_begin(); }
+    ~GemmBatchScope() { tl_batch.on = false; tl_batch.b.n = 0; }
+};
 static hipError_t gemm_batch_flush(hipStream_t st) {
     tl_batch.on = false;
     if (tl_batch.b.n == 0) return hipSuccess;
@@ -655,406 +667,8 @@ __global__ void __launch_bounds__(256) axpy_kernel(float* __restrict__ y, const 
 }
 
 // ---------------------------------------------------------------------------------
-// critic passes
+// launch wrappers of the kernels above (the exported ones are building blocks of ssn_critic_ln.hip as well)
 // ---------------------------------------------------------------------------------
-// activations h[l] (l = 0..L) for `batch` rows live at act + offsets; returns D in dout[batch]
-static hipError_t critic_forward_pass(const CriticLayout& net, float* const* h, float* dout, int batch, bool bf16, hipStream_t st) {
-    hipError_t e;
-    for (int l = 0; l < net.L; ++l) {
-        GemmArgs g{};
-        g.A = h[l]; g.sam = net.dims[l]; g.sak = 1;
-        g.B = net.W[l]; g.sbk = net.dims[l + 1]; g.sbn = 1;
-        g.C = h[l + 1]; g.ldc = net.dims[l + 1];
-        g.M = batch; g.N = net.dims[l + 1]; g.K = net.dims[l];
-        g.bias = net.b[l]; g.epilogue = EPI_BIAS_RELU; g.leak = net.act.leak;
-        if ((e = gemm(g, bf16, st)) != hipSuccess) return e;
-    }
-    GemmArgs g{};
-    const int L = net.L;
-    g.A = h[L]; g.sam = net.dims[L]; g.sak = 1;
-    g.B = net.wout; g.sbk = 1; g.sbn = 1;
-    g.C = dout; g.ldc = 1; g.M = batch; g.N = 1; g.K = net.dims[L];
-    g.alpha = 1.f; g.beta = 0.f; g.epilogue = EPI_PLAIN;
-    return gemm(g, bf16, st);
-}
-
-// Backward chain with masks from h[]: v[L] given; computes v[l-1] = m_{l-1} * (v[l] W_l^T) down to
-// v[0] = v[1] W_1^T (no mask on the input).  If grads != nullptr also accumulates parameter gradients
-// of "sum_b up_b D_b" style losses: dW_l += h_{l-1}^T v_l,  db_l += colsum(v_l).
-struct CriticFork;
-static hipError_t critic_hand_over(CriticFork* fk, hipStream_t from);
-static hipStream_t critic_grad_stream(CriticFork* fk, hipStream_t st);
-static hipError_t critic_backward_chain(const CriticLayout& net, float* const* h, float* const* v, int batch, float* grads,
-                                        bool want_input_grad, bool bf16, hipStream_t st, CriticFork* fk = nullptr) {
-    hipError_t e;
-    const hipStream_t sg = critic_grad_stream(fk, st);        // weight gradients and bias sums (st itself without a fork)
-    long off_end = net.nparams - net.dims[net.L];
-    long off = off_end;
-    for (int l = net.L - 1; l >= 0; --l) {
-        const int nin = net.dims[l], nout = net.dims[l + 1];
-        off -= nout;                    // bias of layer l
-        const long off_b = off;
-        off -= (long)nin * nout;        // weight of layer l
-        const long off_w = off;
-        if (grads) {
-            GemmArgs g{};               // dW_l[i][k] += scale * sum_b h_l[b][i] v_{l+1}[b][k]
-            g.A = h[l]; g.sam = 1; g.sak = nin;            // op(A)(i, b) = h[b][i]
-            g.B = v[l + 1]; g.sbk = nout; g.sbn = 1;        // op(B)(b, k)
-            g.C = grads + off_w; g.ldc = nout; g.M = nin; g.N = nout; g.K = batch;
-            g.alpha = 1.f; g.beta = 1.f; g.epilogue = EPI_PLAIN;
-            if ((e = critic_hand_over(fk, st)) != hipSuccess) return e;          // v[l + 1] is queued on st
-            if ((e = gemm(g, bf16, sg)) != hipSuccess) return e;
-            hipLaunchKernelGGL(colsum_kernel, dim3((nout + 63) / 64), dim3(1024), 0, sg, v[l + 1], grads + off_b, batch, nout, 1.f);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        }
-        if (l > 0 || want_input_grad) {
-            GemmArgs g{};               // v_l = (v_{l+1} W_l^T) [* mask_l]
-            g.A = v[l + 1]; g.sam = nout; g.sak = 1;
-            g.B = net.W[l]; g.sbk = 1; g.sbn = nout;        // op(B)(k, i) = W[i][k]
-            g.C = v[l]; g.ldc = nin; g.M = batch; g.N = nin; g.K = nout;
-            if (l > 0) { g.epilogue = EPI_MASK; g.mask = h[l]; g.ldm = nin; g.leak = net.act.leak; }
-            else { g.alpha = 1.f; g.beta = 0.f; g.epilogue = EPI_PLAIN; }
-            if ((e = gemm(g, bf16, st)) != hipSuccess) return e;
-        }
-    }
-    return hipSuccess;
-}
-
-size_t critic_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p) {
-    // (1) h_0..h_L and v_0..v_L for the [xg; xd] rows + upstream; (2) h, v, e for the xp rows + D(xp); + scratch
-    long per_row = 0, maxd = 0;
-    for (int l = 0; l <= nlayers; ++l) { per_row += dims[l]; if (dims[l] > maxd) maxd = dims[l]; }
-    return (size_t)(2L * batch_gd * per_row + batch_gd + 3L * batch_p * per_row + batch_p + maxd + 64) +
-           critic_splitk_scratch_floats(dims, nlayers, batch_gd + batch_p) + critic_rows_workspace_floats(dims, nlayers, batch_p);
-}
-
-// Wide plain critics on bf16 operands: D (mode 0) or D and the input gradient (mode 1) of `batch` rows whose input block h0 is
-// built, in two launches -- weights to B fragments, the row-block kernel (ssn_critic_rows.hip).  `free_ws`: workspace behind h0.
-static hipError_t critic_rows_eval(const CriticLayout& net, float* h0, int batch, float* dvals, int mode, float* gx, float scale,
-                                   int nx, float* free_ws, hipStream_t st) {
-    RowsArgs ra{};
-    ra.L = net.L; ra.leak = net.act.leak; ra.mode = mode; ra.nx = nx; ra.dvals = dvals; ra.gx = gx; ra.scale = scale;
-    for (int l = 0; l <= net.L; ++l) ra.dims[l] = net.dims[l];
-    if (mode == 0) { ra.h[0] = h0; ra.ng = batch; } else { ra.hp[0] = h0; ra.np = batch; }
-    hipError_t e = critic_rows_pack(net, free_ws, ra, nullptr, 0, st);
-    return e != hipSuccess ? e : critic_rows_launch(ra, st);
-}
-
-// D values for a batch (inference / accuracy): out[batch]
-hipError_t critic_forward(const CriticSpec& c, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st) {
-    CriticLayout net;
-    if (!critic_layout(c, net)) return hipErrorInvalidValue;
-    const int* const dims = net.dims;
-    const int nc = cond ? 3 : 0, nx = dims[0] - nc;          // (no condition columns: the unconditional critic)
-    float* h[10];
-    float* p = ws;
-    for (int l = 0; l <= net.L; ++l) { h[l] = p; p += (long)batch * dims[l]; }
-    hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)batch * dims[0])), dim3(256), 0, st, x, cond, h[0], batch, nx, c.hide_cell_type, nc);
-    if (c.bf16 && batch > 0 && critic_rows_supported(dims, net.L))
-        return critic_rows_eval(net, h[0], batch, out, 0, nullptr, 0.f, nx, h[1], st);
-    return critic_forward_pass(net, h, out, batch, c.bf16, st);
-}
-
-// D values of TWO batches in one pass over the stacked rows [xa; xb] (the accuracy mean D(xg) - mean D(xd) after every critic
-// update, cwgan.py:505-507): every output row depends on its own input row alone and a forward GEMM is never split over K,
-// so the values are those of two separate forwards, bit for bit, for one chain of launches instead of two.
-// out[na + nb]; ws as critic_forward with batch = na + nb (<= 2 max(na, nb): what the callers reserve).
-hipError_t critic_forward2(const CriticSpec& c, const float* xa, const float* ca, int na, const float* xb, const float* cb, int nb,
-                           float* out, float* ws, hipStream_t st, bool inputs_ready) {
-    CriticLayout net;
-    if (!critic_layout(c, net)) return hipErrorInvalidValue;
-    const int* const dims = net.dims;
-    if ((ca == nullptr) != (cb == nullptr) && na > 0 && nb > 0) return hipErrorInvalidValue;
-    const int nc = (ca || cb) ? 3 : 0, nx = dims[0] - nc, batch = na + nb;
-    if (batch == 0) return hipSuccess;
-    float* h[10];
-    float* p = ws;
-    for (int l = 0; l <= net.L; ++l) { h[l] = p; p += (long)batch * dims[l]; }
-    if (na > 0 && !inputs_ready) hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)na * dims[0])), dim3(256), 0, st, xa, ca, h[0], na, nx, c.hide_cell_type, nc);
-    if (nb > 0 && !inputs_ready) hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)nb * dims[0])), dim3(256), 0, st, xb, cb, h[0] + (long)na * dims[0], nb, nx, c.hide_cell_type, nc);
-    if (c.bf16 && critic_rows_supported(dims, net.L))
-        return critic_rows_eval(net, h[0], batch, out, 0, nullptr, 0.f, nx, h[1], st);
-    return critic_forward_pass(net, h, out, batch, c.bf16, st);
-}
-
-// The two halves of a critic update -- the Wasserstein term on [xg; xd] and the gradient penalty on xp -- are independent
-// chains of ~20 small launches each (forward, backward chain, weight gradients), latency-bound one after the other: the
-// penalty half runs on a second stream beside the first (fork behind the inputs, join in front of the final sums), and the
-// weight-gradient GEMMs and bias sums of BOTH halves -- which nothing in the chains waits for -- on a third, each behind an
-// event that says its operands are queued.  The
-// results do not change by a bit: every weight-gradient GEMM is split over K into slabs of its own, and the slabs are added
-// by ONE kernel after the join, in the order the GEMMs were ISSUED (critic_splitk_flush) -- which is the host's order, not
-// the order of execution.  A shape whose weight-gradient GEMMs would add into the gradient directly (choose_splits == 1:
-// K < 512 or >= 256 output tiles) keeps the one stream.  SSN_CRITIC_PAR=0 switches the second stream off (A/B runs).
-struct CriticFork {
-    hipStream_t aux, gs;               // penalty half; weight-gradient GEMMs and bias column sums of both halves
-    hipEvent_t fork, join, join_g;
-    hipEvent_t ready[24]; unsigned nready;  // "operands of the next gradient GEMM are there", one per hand-over, reused every call
-    // the gradient stream takes its next launch behind everything `from` holds so far
-    hipError_t hand_over(hipStream_t from) {
-        hipEvent_t ev = ready[nready++ % 24];
-        hipError_t e = hipEventRecord(ev, from);
-        return e != hipSuccess ? e : hipStreamWaitEvent(gs, ev, 0);
-    }
-};
-static CriticFork* critic_fork() {
-    static thread_local CriticFork* per_dev[64] = {};   // per calling thread and device: the event ring is not shared
-    static const bool on = [] { const char* e = getenv("SSN_CRITIC_PAR"); return !(e && e[0] == '0'); }();
-    if (!on) return nullptr;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    if (!per_dev[dev]) {
-        CriticFork* f = new CriticFork{};
-        bool ok = hipStreamCreateWithFlags(&f->aux, hipStreamNonBlocking) == hipSuccess &&
-                  hipStreamCreateWithFlags(&f->gs, hipStreamNonBlocking) == hipSuccess &&
-                  hipEventCreateWithFlags(&f->fork, hipEventDisableTiming) == hipSuccess &&
-                  hipEventCreateWithFlags(&f->join, hipEventDisableTiming) == hipSuccess &&
-                  hipEventCreateWithFlags(&f->join_g, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; i < 24 && ok; ++i) ok = hipEventCreateWithFlags(&f->ready[i], hipEventDisableTiming) == hipSuccess;
-        if (!ok) { delete f; return nullptr; }
-        per_dev[dev] = f;
-    }
-    return per_dev[dev];
-}
-
-static hipError_t critic_hand_over(CriticFork* fk, hipStream_t from) { return fk ? fk->hand_over(from) : hipSuccess; }
-static hipStream_t critic_grad_stream(CriticFork* fk, hipStream_t st) { return fk ? fk->gs : st; }
-
-// Full critic loss + gradient.  stats[0..3] = mean D(xg), mean D(xd), penalty, loss.
-hipError_t critic_loss_grad(const CriticSpec& c, const float* xg, const float* cg, const float* xd, const float* cd, const float* xp,
-                            const float* cp, int ng, int nd, int np, float lmd, float* grads, float* stats, float* dvals, float* ws,
-                            hipStream_t st, const float* eps, float* xp_out) {
-    // eps != nullptr: xp is not an input -- it is formed here, together with the three input blocks, in one launch (xp_out
-    // receives it; ng = nd = np and ONE condition array for the three inputs: the single-process critic step)
-    CriticLayout net;
-    if (!critic_layout(c, net)) return hipErrorInvalidValue;
-    const int* const dims = net.dims;
-    if (eps && (!xp_out || ng != nd || nd != np || cg != cd || cd != cp)) return hipErrorInvalidValue;
-    hipError_t e;
-    const int nc = (cg || cd || cp) ? 3 : 0;
-    if (nc && ((ng && !cg) || (nd && !cd) || (np && !cp))) return hipErrorInvalidValue;   // conditions for all inputs or for none
-    const int L = net.L, nx = dims[0] - nc;
-    const int bgd = ng + nd;
-    // (the row-block path of wide plain critics zeroes the gradient in its weight-packing launch)
-    const bool rows_path = c.bf16 && bgd > 0 && np > 0 && critic_rows_supported(dims, net.L);
-    if (!rows_path && (e = hipMemsetAsync(grads, 0, net.nparams * sizeof(float), st)) != hipSuccess) return e;
-    float* p = ws;
-    // ---------------- (1) mean D(xg) - mean D(xd) on the concatenated batch -------------------
-    float *h[10], *v[10];
-    for (int l = 0; l <= L; ++l) { h[l] = p; p += (long)bgd * dims[l]; }
-    for (int l = 0; l <= L; ++l) { v[l] = p; p += (long)bgd * dims[l]; }
-    float* up = p; p += bgd;
-    float *hp[10], *vp[10], *ep[10];
-    for (int l = 0; l <= L; ++l) { hp[l] = p; p += (long)np * dims[l]; }
-    for (int l = 0; l <= L; ++l) { vp[l] = p; p += (long)np * dims[l]; }
-    for (int l = 0; l <= L; ++l) { ep[l] = p; p += (long)np * dims[l]; }
-    float* dp = p; p += np;
-    float* tmp = p; p += dims[L];
-    critic_splitk_begin(p, critic_splitk_scratch_floats(dims, net.L, bgd + np));     // the rest of the workspace
-    struct PlanScope { ~PlanScope() { critic_splitk_begin(nullptr, 0); } } plan_scope;    // closed on every return path
-    // second stream for the penalty half, when every weight-gradient GEMM of both halves goes to slabs (see critic_fork)
-    bool par = np > 0 && bgd > 0 && choose_splits(dims[L], 1, bgd) > 1;
-    for (int l = 0; l < L && par; ++l) par = choose_splits(dims[l], dims[l + 1], bgd) > 1 && choose_splits(dims[l], dims[l + 1], np) > 1;
-    CriticFork* const fk = par ? critic_fork() : nullptr;
-    hipStream_t sp = st;                            // stream of the penalty half
-    const hipStream_t sg = critic_grad_stream(fk, st);   // stream of the weight-gradient GEMMs and bias sums
-    // Once the side streams carry work, EVERY way out of this function joins them to st first: an error return that left
-    // them running would hand the caller back a workspace that is still being read and written.
-    struct JoinScope {
-        CriticFork* fk; hipStream_t st; bool forked = false, joined = false;
-        hipError_t join() {
-            if (!fk || !forked || joined) return hipSuccess;
-            joined = true;
-            hipError_t e = hipEventRecord(fk->join, fk->aux), e2;
-            if (e == hipSuccess) e = hipStreamWaitEvent(st, fk->join, 0);
-            e2 = hipEventRecord(fk->join_g, fk->gs);
-            if (e2 == hipSuccess) e2 = hipStreamWaitEvent(st, fk->join_g, 0);
-            return e != hipSuccess ? e : e2;
-        }
-        ~JoinScope() { (void)join(); }
-    } join_scope{fk, st};
-    // ---------------- wide plain critics on bf16 operands: the row-local chains of both halves in ONE launch (ssn_critic_rows.hip),
-    // then the weight-gradient GEMMs, whose operands are all there, on the three streams.  Same bits as the chains below.
-    if (rows_path) {
-        if (eps) hipLaunchKernelGGL(critic_step_inputs_kernel, dim3(blocks_for((long)ng * dims[0])), dim3(256), 0, st, xg, xd, cg, eps, xp_out,
-                                    h[0], hp[0], ng, nx, c.hide_cell_type, nc);
-        else {
-            hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)ng * dims[0])), dim3(256), 0, st, xg, cg, h[0], ng, nx, c.hide_cell_type, nc);
-            hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)nd * dims[0])), dim3(256), 0, st, xd, cd, h[0] + (long)ng * dims[0], nd, nx, c.hide_cell_type, nc);
-            hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)np * dims[0])), dim3(256), 0, st, xp, cp, hp[0], np, nx, c.hide_cell_type, nc);
-        }
-        RowsArgs ra{};
-        ra.L = L; ra.leak = net.act.leak; ra.mode = 2;
-        for (int l = 0; l <= L; ++l) { ra.dims[l] = dims[l]; ra.h[l] = h[l]; ra.v[l] = v[l]; ra.hp[l] = hp[l]; ra.vp[l] = vp[l]; ra.ep[l] = ep[l]; }
-        ra.up = up; ra.dvals = dvals; ra.ng = ng; ra.nd = nd; ra.np = np; ra.nx = nx;
-        float* const rws = p + critic_splitk_scratch_floats(dims, net.L, bgd + np);
-        ra.dnorm = rws;
-        if ((e = critic_rows_pack(net, rws + np, ra, grads, net.nparams, st)) != hipSuccess) return e;
-        if ((e = critic_rows_launch(ra, st)) != hipSuccess) return e;
-        // every operand of the weight gradients is there: ONE launch for the GEMMs (split over K into slabs of their own, in the
-        // order of the chains below), one for the bias sums, the w_out term of the penalty and the statistics, one for the slabs
-        // (`par`: every weight-gradient GEMM of both halves is split over K -- the condition of the three streams below; any other
-        // shape issues them one by one, in the order and with the direct additions of the chains below)
-        if (par) gemm_batch_begin();
-        struct BatchScope { ~BatchScope() { tl_batch.on = false; tl_batch.b.n = 0; } } batch_scope;
-        ColsumBatchArgs cs{};
-        auto add_colsum = [&](const float* X, float* out, int batch, int n, float beta, float* axpy_to, float axpy_a) {
-            const int i = cs.cnt++;
-            cs.X[i] = X; cs.out[i] = out; cs.batch[i] = batch; cs.n[i] = n; cs.beta[i] = beta; cs.axpy_to[i] = axpy_to; cs.axpy_a[i] = axpy_a;
-            cs.first[i + 1] = cs.first[i] + (n + 63) / 64;
-        };
-        {
-            GemmArgs g{};                               // d/dw_out = sum_b up_b h_L[b][:]
-            g.A = h[L]; g.sam = 1; g.sak = dims[L];
-            g.B = up; g.sbk = 1; g.sbn = 1;
-            g.C = grads + (net.nparams - dims[L]); g.ldc = 1; g.M = dims[L]; g.N = 1; g.K = bgd;
-            g.alpha = 1.f; g.beta = 1.f; g.epilogue = EPI_PLAIN;
-            if ((e = gemm(g, c.bf16, st)) != hipSuccess) return e;
-        }
-        long off = net.nparams - dims[L];
-        for (int l = L - 1; l >= 0; --l) {              // dW_l += h_l^T v_{l+1},  db_l += colsum(v_{l+1})
-            const int nin = dims[l], nout = dims[l + 1];
-            off -= nout;
-            const long off_b = off;
-            off -= (long)nin * nout;
-            GemmArgs g{};
-            g.A = h[l]; g.sam = 1; g.sak = nin;
-            g.B = v[l + 1]; g.sbk = nout; g.sbn = 1;
-            g.C = grads + off; g.ldc = nout; g.M = nin; g.N = nout; g.K = bgd;
-            g.alpha = 1.f; g.beta = 1.f; g.epilogue = EPI_PLAIN;
-            if ((e = gemm(g, c.bf16, st)) != hipSuccess) return e;
-            add_colsum(v[l + 1], grads + off_b, bgd, nout, 1.f, nullptr, 0.f);
-        }
-        off = 0;
-        for (int l = 0; l < L; ++l) {                   // dW_l += lmd e_l^T v'_{l+1}
-            const int nin = dims[l], nout = dims[l + 1];
-            GemmArgs g{};
-            g.A = ep[l]; g.sam = 1; g.sak = nin;
-            g.B = vp[l + 1]; g.sbk = nout; g.sbn = 1;
-            g.C = grads + off; g.ldc = nout; g.M = nin; g.N = nout; g.K = np;
-            g.alpha = lmd; g.beta = 1.f; g.epilogue = EPI_PLAIN;
-            if ((e = gemm(g, c.bf16, st)) != hipSuccess) return e;
-            off += (long)nin * nout + nout;
-        }
-        if ((e = gemm_batch_flush(st)) != hipSuccess) return e;
-        // d/dw_out[k] += lmd * sum_b e_L[b][k]   (behind the GEMMs: one of them may have added into that gradient directly)
-        add_colsum(ep[L], tmp, np, dims[L], 0.f, grads + (net.nparams - dims[L]), lmd);
-        cs.dvals = dvals; cs.dnorm = ra.dnorm; cs.stats = stats; cs.ng = ng; cs.nd = nd; cs.np = np; cs.lmd = lmd;
-        hipLaunchKernelGGL(colsum_batch_kernel, dim3(cs.first[cs.cnt] + 1), dim3(1024), 0, st, cs);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        return critic_splitk_flush(st);
-    }
-    if (eps)        // (in front of the fork: the penalty half reads hp[0])
-        hipLaunchKernelGGL(critic_step_inputs_kernel, dim3(blocks_for((long)ng * dims[0])), dim3(256), 0, st, xg, xd, cg, eps, xp_out,
-                           h[0], hp[0], ng, nx, c.hide_cell_type, nc);
-    if (fk) {
-        if ((e = hipEventRecord(fk->fork, st)) != hipSuccess) return e;          // behind the memset and everything the caller queued
-        join_scope.forked = true;
-        if ((e = hipStreamWaitEvent(fk->aux, fk->fork, 0)) != hipSuccess) return e;
-        sp = fk->aux;
-    }
-    if (!eps) {
-        hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)ng * dims[0])), dim3(256), 0, st, xg, cg, h[0], ng, nx, c.hide_cell_type, nc);
-        hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)nd * dims[0])), dim3(256), 0, st, xd, cd, h[0] + (long)ng * dims[0], nd, nx, c.hide_cell_type, nc);
-    }
-    if ((e = critic_forward_pass(net, h, dvals, bgd, c.bf16, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(two_means_kernel, dim3(1), dim3(256), 0, st, dvals, stats, ng, nd);
-    hipLaunchKernelGGL(fill_updown_kernel, dim3(blocks_for(bgd)), dim3(256), 0, st, up, ng, nd);
-    // d/dw_out = sum_b up_b h_L[b][:]
-    {
-        GemmArgs g{};
-        g.A = h[L]; g.sam = 1; g.sak = dims[L];      // op(A)(k, b) = h_L[b][k]
-        g.B = up; g.sbk = 1; g.sbn = 1;
-        g.C = grads + (net.nparams - dims[L]); g.ldc = 1; g.M = dims[L]; g.N = 1; g.K = bgd;
-        g.alpha = 1.f; g.beta = 1.f; g.epilogue = EPI_PLAIN;
-        if ((e = critic_hand_over(fk, st)) != hipSuccess) return e;              // h[L] and up are queued on st
-        if ((e = gemm(g, c.bf16, sg)) != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(critic_outgrad_kernel, dim3(blocks_for((long)bgd * dims[L])), dim3(256), 0, st, h[L], net.wout, up, v[L], bgd, dims[L], net.act.leak);
-    if ((e = critic_backward_chain(net, h, v, bgd, grads, false, c.bf16, st, fk)) != hipSuccess) return e;
-
-    // ---------------- (2) gradient penalty on xp ------------------------------------------------
-    if (!eps) hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)np * dims[0])), dim3(256), 0, sp, xp, cp, hp[0], np, nx, c.hide_cell_type, nc);
-    if ((e = critic_forward_pass(net, hp, dp, np, c.bf16, sp)) != hipSuccess) return e;
-    // input gradient g = dD/dh0 per sample: v_L = m_L * w_out, chain down to vp[0]
-    hipLaunchKernelGGL(critic_outgrad_kernel, dim3(blocks_for((long)np * dims[L])), dim3(256), 0, sp, hp[L], net.wout, (const float*)nullptr, vp[L], np, dims[L], net.act.leak);
-    if ((e = critic_backward_chain(net, hp, vp, np, nullptr, true, c.bf16, sp)) != hipSuccess) return e;
-    // penalty and its gradient w.r.t. g: ep[0] = ghat (np x n0)
-    hipLaunchKernelGGL(gp_head_kernel, dim3(1), dim3(256), 0, sp, vp[0], ep[0], stats + 2, np, dims[0], nx);
-    // backprop through the linear chain g = v_1 W_1^T, v_{l} = m_l * (v_{l+1} W_{l+1}^T), v_L = m_L * w_out:
-    //   dW_l[i][k] += lmd * sum_b e_{l-1}[b][i] v_l[b][k],   e_l = m_l * (e_{l-1} W_l)   (e_0 = ghat)
-    long off = 0;
-    for (int l = 0; l < L; ++l) {
-        const int nin = dims[l], nout = dims[l + 1];
-        {
-            GemmArgs g{};
-            g.A = ep[l]; g.sam = 1; g.sak = nin;               // op(A)(i, b) = e_l[b][i]
-            g.B = vp[l + 1]; g.sbk = nout; g.sbn = 1;
-            g.C = grads + off; g.ldc = nout; g.M = nin; g.N = nout; g.K = np;
-            g.alpha = lmd; g.beta = 1.f; g.epilogue = EPI_PLAIN;
-            if ((e = critic_hand_over(fk, sp)) != hipSuccess) return e;          // e_l (and v_{l+1} before it) are queued on sp
-            if ((e = gemm(g, c.bf16, sg)) != hipSuccess) return e;
-        }
-        {
-            GemmArgs g{};                                       // e_{l+1} = m_{l+1} * (e_l W_l)
-            g.A = ep[l]; g.sam = nin; g.sak = 1;
-            g.B = net.W[l]; g.sbk = nout; g.sbn = 1;
-            g.C = ep[l + 1]; g.ldc = nout; g.M = np; g.N = nout; g.K = nin;
-            g.epilogue = EPI_MASK; g.mask = hp[l + 1]; g.ldm = nout; g.leak = net.act.leak;
-            if ((e = gemm(g, c.bf16, sp)) != hipSuccess) return e;
-        }
-        off += (long)nin * nout + nout;
-    }
-    // d/dw_out[k] += lmd * sum_b e_L[b][k]      (v_L = m_L * w_out, mask already applied in e_L)
-    hipLaunchKernelGGL(colsum_kernel, dim3((dims[L] + 63) / 64), dim3(1024), 0, sp, ep[L], tmp, np, dims[L], 0.f);
-    if (fk) {                                       // join: the sums below and the slab reduction see both halves
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = join_scope.join()) != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(axpy_kernel, dim3(blocks_for(dims[L])), dim3(256), 0, st, grads + (net.nparams - dims[L]), tmp, lmd, (long)dims[L]);
-    hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(1), 0, st, stats, lmd);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    return critic_splitk_flush(st);                   // grads += the split GEMMs' slabs, in slice order
-}
-
-// Gradient of  -mean D(x)  w.r.t. the tuning-curve part of the input (generator side, wgan.py:236):
-// gx[batch][nx];  also returns mean D in stats[0].
-hipError_t critic_input_grad(const CriticSpec& c, const float* x, const float* cond, int batch, float scale, float* gx, float* stats,
-                             float* ws, hipStream_t st) {
-    CriticLayout net;
-    if (!critic_layout(c, net)) return hipErrorInvalidValue;
-    const int* const dims = net.dims;
-    hipError_t e;
-    const int L = net.L, nc = cond ? 3 : 0, nx = dims[0] - nc;
-    float *h[10], *v[10];
-    float* p = ws;
-    for (int l = 0; l <= L; ++l) { h[l] = p; p += (long)batch * dims[l]; }
-    for (int l = 0; l <= L; ++l) { v[l] = p; p += (long)batch * dims[l]; }
-    float* dv = p; p += batch;
-    hipLaunchKernelGGL(critic_input_kernel, dim3(blocks_for((long)batch * dims[0])), dim3(256), 0, st, x, cond, h[0], batch, nx, c.hide_cell_type, nc);
-    if (c.bf16 && batch > 0 && critic_rows_supported(dims, net.L)) {
-        if ((e = critic_rows_eval(net, h[0], batch, dv, 1, gx, scale, nx, p, st)) != hipSuccess) return e;
-        hipLaunchKernelGGL(two_means_kernel, dim3(1), dim3(256), 0, st, dv, stats, batch, 0);
-        return hipGetLastError();
-    }
-    if ((e = critic_forward_pass(net, h, dv, batch, c.bf16, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(two_means_kernel, dim3(1), dim3(256), 0, st, dv, stats, batch, 0);
-    hipLaunchKernelGGL(critic_outgrad_kernel, dim3(blocks_for((long)batch * dims[L])), dim3(256), 0, st, h[L], net.wout, (const float*)nullptr, v[L], batch, dims[L], net.act.leak);
-    if ((e = critic_backward_chain(net, h, v, batch, nullptr, true, c.bf16, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(gather_scale_kernel, dim3(blocks_for((long)batch * nx)), dim3(256), 0, st, v[0], gx, batch, dims[0], nx, scale);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------
-// building blocks exported to ssn_critic_ln.hip
-// ---------------------------------------------------------------------------------
-hipError_t critic_gemm(const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C, long ldc,
-                       int M, int N, int K, float alpha, float beta, bool bf16, hipStream_t st) {
-    GemmArgs g{};
-    g.A = A; g.sam = sam; g.sak = sak; g.B = B; g.sbk = sbk; g.sbn = sbn; g.C = C; g.ldc = ldc;
-    g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta; g.epilogue = EPI_PLAIN;
-    return gemm(g, bf16, st);
-}
 hipError_t critic_colsum(const float* X, float* out, int batch, int n, float beta, hipStream_t st) {
     hipLaunchKernelGGL(colsum_kernel, dim3((n + 63) / 64), dim3(1024), 0, st, X, out, batch, n, beta);
     return hipGetLastError();
@@ -1080,6 +694,425 @@ hipError_t critic_loss_combine(float* stats, float lmd, hipStream_t st) {
 hipError_t critic_gather_scale(const float* v0, float* gx, int batch, int n0, int nx, float s, hipStream_t st) {
     hipLaunchKernelGGL(gather_scale_kernel, dim3(blocks_for((long)batch * nx)), dim3(256), 0, st, v0, gx, batch, n0, nx, s);
     return hipGetLastError();
+}
+static hipError_t critic_outgrad(const float* hL, const float* wout, const float* up, float* vL, int batch, int nL, float leak, hipStream_t st) {
+    hipLaunchKernelGGL(critic_outgrad_kernel, dim3(blocks_for((long)batch * nL)), dim3(256), 0, st, hL, wout, up, vL, batch, nL, leak);
+    return hipGetLastError();
+}
+static hipError_t critic_fill_updown(float* up, int ng, int nd, hipStream_t st) {
+    hipLaunchKernelGGL(fill_updown_kernel, dim3(blocks_for(ng + nd)), dim3(256), 0, st, up, ng, nd);
+    return hipGetLastError();
+}
+static hipError_t critic_axpy(float* y, const float* x, float a, long n, hipStream_t st) {
+    hipLaunchKernelGGL(axpy_kernel, dim3(blocks_for(n)), dim3(256), 0, st, y, x, a, n);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
+// critic passes
+// ---------------------------------------------------------------------------------
+// ---- the GEMMs of a critic, one function per role.  gemm() splits over K what has the PLAIN epilogue, beta == 1 and ldc == N
+// (the weight gradients, nothing else); the BIAS_RELU and MASK epilogues read neither alpha nor beta, which stay zero there.
+static GemmArgs gemm_plain(const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C, long ldc,
+                           int M, int N, int K, float alpha, float beta) {
+    GemmArgs g{};
+    g.A = A; g.sam = sam; g.sak = sak; g.B = B; g.sbk = sbk; g.sbn = sbn; g.C = C; g.ldc = ldc;
+    g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta; g.epilogue = EPI_PLAIN;
+    return g;
+}
+hipError_t critic_gemm(const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C, long ldc,
+                       int M, int N, int K, float alpha, float beta, bool bf16, hipStream_t st) {
+    return gemm(gemm_plain(A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, alpha, beta), bf16, st);
+}
+// h_{l+1} = act(h_l W_l + b_l)
+static GemmArgs gemm_layer(const CriticLayout& net, int l, const float* hl, float* hnext, int rows) {
+    const int nin = net.dims[l], nout = net.dims[l + 1];
+    GemmArgs g = gemm_plain(hl, nin, 1, net.W[l], nout, 1, hnext, nout, rows, nout, nin, 0.f, 0.f);
+    g.bias = net.b[l]; g.epilogue = EPI_BIAS_RELU; g.leak = net.act.leak;
+    return g;
+}
+// D = h_L w_out
+static GemmArgs gemm_head(const CriticLayout& net, const float* hL, float* dout, int rows) {
+    return gemm_plain(hL, net.dims[net.L], 1, net.wout, 1, 1, dout, 1, rows, 1, net.dims[net.L], 1.f, 0.f);
+}
+// v_l = m_l * (v_{l+1} W_l^T), m_l from mask = h_l;  mask == nullptr: v_0 = v_1 W_0^T (no mask on the input)
+static GemmArgs gemm_back(const CriticLayout& net, int l, const float* vnext, float* vl, const float* mask, int rows) {
+    const int nin = net.dims[l], nout = net.dims[l + 1];
+    GemmArgs g = gemm_plain(vnext, nout, 1, net.W[l], 1, nout, vl, nin, rows, nin, nout, mask ? 0.f : 1.f, 0.f);   // op(B)(k, i) = W[i][k]
+    if (mask) { g.epilogue = EPI_MASK; g.mask = mask; g.ldm = nin; g.leak = net.act.leak; }
+    return g;
+}
+// e_{l+1} = m_{l+1} * (e_l W_l), m_{l+1} from mask = h_{l+1}   (the second chain of the penalty)
+static GemmArgs gemm_second(const CriticLayout& net, int l, const float* el, float* enext, const float* mask, int rows) {
+    const int nin = net.dims[l], nout = net.dims[l + 1];
+    GemmArgs g = gemm_plain(el, nin, 1, net.W[l], nout, 1, enext, nout, rows, nout, nin, 0.f, 0.f);
+    g.epilogue = EPI_MASK; g.mask = mask; g.ldm = nout; g.leak = net.act.leak;
+    return g;
+}
+// C[M][N] += alpha A^T V over K rows (A [K][M], V [K][N]): op(A)(i, b) = A[b][i].  The form gemm() splits over K.
+static GemmArgs gemm_wgrad(const float* A, const float* V, float* C, int M, int N, int K, float alpha) {
+    return gemm_plain(A, 1, M, V, N, 1, C, N, M, N, K, alpha, 1.f);
+}
+
+// ---- workspace.  Rows of one batch: activations h[l] (l = 0..L) and, with_v, the backward chain v[l] behind them
+struct CriticRows { float *h[10], *v[10]; };
+static void carve_rows(float*& p, const CriticLayout& net, int rows, bool with_v, CriticRows& R) {
+    for (int l = 0; l <= net.L; ++l) R.h[l] = carve(p, (long)rows * net.dims[l]);
+    for (int l = 0; l <= net.L; ++l) R.v[l] = with_v ? carve(p, (long)rows * net.dims[l]) : nullptr;
+}
+// Workspace of an update (critic_loss_grad).  Order and sizes are part of the results: oracle/critic_cases.plain_chain_slabs
+// predicts where the split-K slabs land from them, and gemm_pipe_mode picks a kernel from the alignment of the operands.
+struct CriticUpdateWs {
+    CriticRows gd; float* up;                   // rows of [xg; xd], upstream of D per row
+    CriticRows pen; float* ep[10]; float* dp;   // rows of xp: h, v, the second chain e; D(xp)
+    float* tmp;                                 // colsum(e_L)
+    float* scratch; size_t nscratch;            // split-K slabs
+    float* rows_ws;                             // the row-block path's own (norm - 1 per penalty row, packed weights)
+};
+static void carve_update(float* p, const CriticLayout& net, int bgd, int np, CriticUpdateWs& w) {
+    carve_rows(p, net, bgd, true, w.gd);
+    w.up = carve(p, bgd);
+    carve_rows(p, net, np, true, w.pen);
+    for (int l = 0; l <= net.L; ++l) w.ep[l] = carve(p, (long)np * net.dims[l]);
+    w.dp = carve(p, np);
+    w.tmp = carve(p, net.dims[net.L]);
+    w.nscratch = critic_splitk_scratch_floats(net.dims, net.L, bgd + np);
+    w.scratch = carve(p, (long)w.nscratch);
+    w.rows_ws = p;
+}
+// bounds carve_update (tmp as the widest layer, 64 floats of slack) and what critic_rows_pack takes behind it; the one- and
+// two-array carves of critic_forward / critic_forward2 / critic_input_grad on the same rows are smaller
+size_t critic_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p) {
+    long per_row = 0, maxd = 0;
+    for (int l = 0; l <= nlayers; ++l) { per_row += dims[l]; if (dims[l] > maxd) maxd = dims[l]; }
+    return (size_t)(2L * batch_gd * per_row + batch_gd + 3L * batch_p * per_row + batch_p + maxd + 64) +
+           critic_splitk_scratch_floats(dims, nlayers, batch_gd + batch_p) + critic_rows_workspace_floats(dims, nlayers, batch_p);
+}
+
+// The two halves of a critic update -- the Wasserstein term on [xg; xd] and the gradient penalty on xp -- are independent
+// chains of ~20 small launches each (forward, backward chain, weight gradients), latency-bound one after the other: the
+// penalty half runs on a second stream beside the first (fork behind the inputs, join in front of the final sums), and the
+// weight-gradient GEMMs and bias sums of BOTH halves -- which nothing in the chains waits for -- on a third, each behind an
+// event that says its operands are queued.  The
+// results do not change by a bit: every weight-gradient GEMM is split over K into slabs of its own, and the slabs are added
+// by ONE kernel after the join, in the order the GEMMs were ISSUED (critic_splitk_flush) -- which is the host's order, not
+// the order of execution.  A shape whose weight-gradient GEMMs would add into the gradient directly (choose_splits == 1:
+// K < 512 or >= 256 output tiles) keeps the one stream.  SSN_CRITIC_PAR=0 switches the second stream off (A/B runs).
+struct CriticFork {
+    hipStream_t aux, gs;               // penalty half; weight-gradient GEMMs and bias column sums of both halves
+    hipEvent_t fork, join, join_g;
+    hipEvent_t ready[24]; unsigned nready;  // "operands of the next gradient GEMM are there", one per hand-over, reused every call
+    // the gradient stream takes its next launch behind everything `from` holds so far
+    hipError_t hand_over(hipStream_t from) {
+        hipEvent_t ev = ready[nready++ % 24];
+        hipError_t e = hipEventRecord(ev, from);
+        return e != hipSuccess ? e : hipStreamWaitEvent(gs, ev, 0);
+    }
+    // One update's use of the side streams (fk == nullptr: none, everything stays on st).  Once they carry work, EVERY way out
+    // of the update joins them to st first: an error return that left them running would hand the caller back a workspace that
+    // is still being read and written.
+    struct Scope {
+        CriticFork* fk; hipStream_t st; bool forked = false, joined = false;
+        // the penalty stream starts behind everything st holds so far
+        hipError_t fork() {
+            if (!fk) return hipSuccess;
+            hipError_t e = hipEventRecord(fk->fork, st);
+            if (e != hipSuccess) return e;
+            forked = true;
+            return hipStreamWaitEvent(fk->aux, fk->fork, 0);
+        }
+        hipError_t join() {
+            if (!fk || !forked || joined) return hipSuccess;
+            joined = true;
+            hipError_t e = hipEventRecord(fk->join, fk->aux), e2;
+            if (e == hipSuccess) e = hipStreamWaitEvent(st, fk->join, 0);
+            e2 = hipEventRecord(fk->join_g, fk->gs);
+            if (e2 == hipSuccess) e2 = hipStreamWaitEvent(st, fk->join_g, 0);
+            return e != hipSuccess ? e : e2;
+        }
+        ~Scope() { (void)join(); }
+    };
+};
+static CriticFork* critic_fork() {
+    static thread_local CriticFork* per_dev[64] = {};   // per calling thread and device: the event ring is not shared
+    static const bool on = [] { const char* e = getenv("SSN_CRITIC_PAR"); return !(e && e[0] == '0'); }();
+    if (!on) return nullptr;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    if (!per_dev[dev]) {
+        CriticFork* f = new CriticFork{};
+        bool ok = hipStreamCreateWithFlags(&f->aux, hipStreamNonBlocking) == hipSuccess &&
+                  hipStreamCreateWithFlags(&f->gs, hipStreamNonBlocking) == hipSuccess &&
+                  hipEventCreateWithFlags(&f->fork, hipEventDisableTiming) == hipSuccess &&
+                  hipEventCreateWithFlags(&f->join, hipEventDisableTiming) == hipSuccess &&
+                  hipEventCreateWithFlags(&f->join_g, hipEventDisableTiming) == hipSuccess;
+        for (int i = 0; i < 24 && ok; ++i) ok = hipEventCreateWithFlags(&f->ready[i], hipEventDisableTiming) == hipSuccess;
+        if (!ok) { delete f; return nullptr; }
+        per_dev[dev] = f;
+    }
+    return per_dev[dev];
+}
+static hipError_t critic_hand_over(CriticFork* fk, hipStream_t from) { return fk ? fk->hand_over(from) : hipSuccess; }
+static hipStream_t critic_grad_stream(CriticFork* fk, hipStream_t st) { return fk ? fk->gs : st; }
+
+// The weight-gradient GEMMs of an update, in the order BOTH paths of critic_loss_grad issue them.  That is the order of the
+// split-K plan, so it fixes the slab layout and the order of the additions in splitk_reduce_kernel:
+//   dw_out += h_L^T up;   dW_l += h_l^T v_{l+1}, l = L-1 .. 0, K = ng + nd;   dW_l += lmd e_l^T v'_{l+1}, l = 0 .. L-1, K = np
+struct WeightGrads {
+    int L; GemmArgs g[2 * 8 + 1];
+    int count() const { return 2 * L + 1; }
+    const GemmArgs& wout() const { return g[0]; }
+    const GemmArgs& chain(int l) const { return g[L - l]; }
+    const GemmArgs& penalty(int l) const { return g[L + 1 + l]; }
+};
+static void critic_weight_grads(const CriticLayout& net, const CriticUpdateWs& w, float* grads, int bgd, int np, float lmd, WeightGrads& wg) {
+    const int L = wg.L = net.L;
+    wg.g[0] = gemm_wgrad(w.gd.h[L], w.up, grads + net.offout, net.dims[L], 1, bgd, 1.f);
+    for (int l = 0; l < L; ++l) {
+        wg.g[L - l] = gemm_wgrad(w.gd.h[l], w.gd.v[l + 1], grads + net.offW[l], net.dims[l], net.dims[l + 1], bgd, 1.f);
+        wg.g[L + 1 + l] = gemm_wgrad(w.ep[l], w.pen.v[l + 1], grads + net.offW[l], net.dims[l], net.dims[l + 1], np, lmd);
+    }
+}
+
+// activations h[l] (l = 0..L) of `batch` rows from h[0]; returns D in dout[batch]
+static hipError_t critic_forward_pass(const CriticLayout& net, float* const* h, float* dout, int batch, bool bf16, hipStream_t st) {
+    hipError_t e;
+    for (int l = 0; l < net.L; ++l)
+        if ((e = gemm(gemm_layer(net, l, h[l], h[l + 1], batch), bf16, st)) != hipSuccess) return e;
+    return gemm(gemm_head(net, h[net.L], dout, batch), bf16, st);
+}
+
+// Backward chain with masks from h[]: v[L] given; computes v[l] = m_l * (v[l+1] W_l^T) down to l = 1, and
+// v[0] = v[1] W_0^T (no mask on the input) if asked for.  With wg, the parameter gradients of a "sum_b up_b D_b" loss on the
+// way: dW_l += h_l^T v_{l+1} (wg->chain(l)) and db_l += colsum(v_{l+1}), on the gradient stream of the fork.
+static hipError_t critic_backward_chain(const CriticLayout& net, float* const* h, float* const* v, int batch, const WeightGrads* wg,
+                                        float* grads, bool want_input_grad, bool bf16, hipStream_t st, CriticFork* fk = nullptr) {
+    hipError_t e;
+    const hipStream_t sg = critic_grad_stream(fk, st);        // weight gradients and bias sums (st itself without a fork)
+    for (int l = net.L - 1; l >= 0; --l) {
+        if (wg) {
+            if ((e = critic_hand_over(fk, st)) != hipSuccess) return e;          // v[l + 1] is queued on st
+            if ((e = gemm(wg->chain(l), bf16, sg)) != hipSuccess) return e;
+            if ((e = critic_colsum(v[l + 1], grads + net.offb[l], batch, net.dims[l + 1], 1.f, sg)) != hipSuccess) return e;
+        }
+        if (l > 0 || want_input_grad)
+            if ((e = gemm(gemm_back(net, l, v[l + 1], v[l], l > 0 ? h[l] : nullptr, batch), bf16, st)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// Wide plain critics on bf16 operands: D (mode 0) or D and the input gradient (mode 1) of `batch` rows whose input block h0 is
+// built, in two launches -- weights to B fragments, the row-block kernel (ssn_critic_rows.hip).  `free_ws`: workspace behind h0.
+static hipError_t critic_rows_eval(const CriticLayout& net, float* h0, int batch, float* dvals, int mode, float* gx, float scale,
+                                   int nx, float* free_ws, hipStream_t st) {
+    RowsArgs ra{};
+    ra.L = net.L; ra.leak = net.act.leak; ra.mode = mode; ra.nx = nx; ra.dvals = dvals; ra.gx = gx; ra.scale = scale;
+    for (int l = 0; l <= net.L; ++l) ra.dims[l] = net.dims[l];
+    if (mode == 0) { ra.h[0] = h0; ra.ng = batch; } else { ra.hp[0] = h0; ra.np = batch; }
+    hipError_t e = critic_rows_pack(net, free_ws, ra, nullptr, 0, st);
+    return e != hipSuccess ? e : critic_rows_launch(ra, st);
+}
+
+// D values of TWO batches in one pass over the stacked rows [xa; xb] (the accuracy mean D(xg) - mean D(xd) after every critic
+// update, cwgan.py:505-507): every output row depends on its own input row alone and a forward GEMM is never split over K,
+// so the values are those of two separate forwards, bit for bit, for one chain of launches instead of two.
+// out[na + nb]; ws: h_0..h_L of na + nb rows (<= 2 max(na, nb): what the callers reserve).
+hipError_t critic_forward2(const CriticSpec& c, const float* xa, const float* ca, int na, const float* xb, const float* cb, int nb,
+                           float* out, float* ws, hipStream_t st, bool inputs_ready) {
+    CriticLayout net;
+    if (!critic_layout(c, net)) return hipErrorInvalidValue;
+    if ((ca == nullptr) != (cb == nullptr) && na > 0 && nb > 0) return hipErrorInvalidValue;
+    const int nc = (ca || cb) ? 3 : 0, nx = net.dims[0] - nc, batch = na + nb;          // (nc = 0: the unconditional critic)
+    if (batch == 0) return hipSuccess;
+    hipError_t e;
+    CriticRows R;
+    carve_rows(ws, net, batch, false, R);
+    if (!inputs_ready) {
+        if ((e = critic_make_input(xa, ca, R.h[0], na, nx, c.hide_cell_type, st)) != hipSuccess) return e;
+        if ((e = critic_make_input(xb, cb, R.h[0] + (long)na * net.dims[0], nb, nx, c.hide_cell_type, st)) != hipSuccess) return e;
+    }
+    if (c.bf16 && critic_rows_supported(net.dims, net.L))
+        return critic_rows_eval(net, R.h[0], batch, out, 0, nullptr, 0.f, nx, R.h[1], st);
+    return critic_forward_pass(net, R.h, out, batch, c.bf16, st);
+}
+// D values for a batch (inference / accuracy): out[batch].  The same pass with no second batch.
+hipError_t critic_forward(const CriticSpec& c, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st) {
+    return critic_forward2(c, x, cond, batch, nullptr, nullptr, 0, out, ws, st, false);
+}
+
+// ---- the update.  One call of critic_loss_grad: its arguments, the layout, the carved workspace, the weight-gradient list
+struct CriticUpdate {
+    const CriticSpec& c; const CriticLayout& net;
+    const float *xg, *cg, *xd, *cd, *xp, *cp, *eps; float* xp_out;
+    int ng, nd, np, nx; float lmd;
+    float *grads, *stats, *dvals;
+    CriticUpdateWs w; WeightGrads wg;
+};
+// The input blocks h0 = [rows of xg; rows of xd] (INPUT_GD) and hp0 = rows of xp (INPUT_P), on st.  eps: both, in ONE launch
+// that forms xp = eps xd + (1 - eps) xg as well; otherwise one launch per input, and the chain path asks for the two halves'
+// blocks where each half begins (the one of xp on the penalty stream behind the fork).
+enum { INPUT_GD = 1, INPUT_P = 2 };
+static hipError_t critic_stage_inputs(const CriticUpdate& u, int which, hipStream_t st) {
+    hipError_t e;
+    const int n0 = u.net.dims[0], hide = u.c.hide_cell_type;
+    if (u.eps) {
+        if (which != (INPUT_GD | INPUT_P)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(critic_step_inputs_kernel, dim3(blocks_for((long)u.ng * n0)), dim3(256), 0, st, u.xg, u.xd, u.cg, u.eps, u.xp_out,
+                           u.w.gd.h[0], u.w.pen.h[0], u.ng, u.nx, hide, n0 - u.nx);
+        return hipGetLastError();
+    }
+    if (which & INPUT_GD) {
+        if ((e = critic_make_input(u.xg, u.cg, u.w.gd.h[0], u.ng, u.nx, hide, st)) != hipSuccess) return e;
+        if ((e = critic_make_input(u.xd, u.cd, u.w.gd.h[0] + (long)u.ng * n0, u.nd, u.nx, hide, st)) != hipSuccess) return e;
+    }
+    return (which & INPUT_P) ? critic_make_input(u.xp, u.cp, u.w.pen.h[0], u.np, u.nx, hide, st) : hipSuccess;
+}
+
+// Wide plain critics on bf16 operands: the row-local chains of both halves in ONE launch (ssn_critic_rows.hip), then the
+// weight-gradient GEMMs, whose operands are then all there.  Same bits as the two halves below.
+// `batched` (every weight-gradient GEMM of both halves is split over K, the condition of the fork below): ONE launch for the GEMMs,
+// each into slabs of its own; any other shape issues them one by one, with the direct additions of the chains below.  Then one
+// launch for the bias sums, the w_out term of the penalty and the statistics, and one for the slabs.
+static hipError_t critic_update_rows(const CriticUpdate& u, bool batched, hipStream_t st) {
+    const CriticLayout& net = u.net;
+    const CriticUpdateWs& w = u.w;
+    const int L = net.L, bgd = u.ng + u.nd;
+    hipError_t e;
+    if ((e = critic_stage_inputs(u, INPUT_GD | INPUT_P, st)) != hipSuccess) return e;
+    RowsArgs ra{};
+    ra.L = L; ra.leak = net.act.leak; ra.mode = 2;
+    for (int l = 0; l <= L; ++l) { ra.dims[l] = net.dims[l]; ra.h[l] = w.gd.h[l]; ra.v[l] = w.gd.v[l]; ra.hp[l] = w.pen.h[l]; ra.vp[l] = w.pen.v[l]; ra.ep[l] = w.ep[l]; }
+    ra.up = w.up; ra.dvals = u.dvals; ra.ng = u.ng; ra.nd = u.nd; ra.np = u.np; ra.nx = u.nx;
+    ra.dnorm = w.rows_ws;
+    // (the weight-packing launch zeroes the gradient)
+    if ((e = critic_rows_pack(net, w.rows_ws + u.np, ra, u.grads, net.nparams, st)) != hipSuccess) return e;
+    if ((e = critic_rows_launch(ra, st)) != hipSuccess) return e;
+    {
+        GemmBatchScope batch(batched);
+        for (int i = 0; i < u.wg.count(); ++i)
+            if ((e = gemm(u.wg.g[i], u.c.bf16, st)) != hipSuccess) return e;
+        if ((e = gemm_batch_flush(st)) != hipSuccess) return e;
+    }
+    ColsumBatchArgs cs{};
+    auto add_colsum = [&](const float* X, float* out, int batch, int n, float beta, float* axpy_to, float axpy_a) {
+        const int i = cs.cnt++;
+        cs.X[i] = X; cs.out[i] = out; cs.batch[i] = batch; cs.n[i] = n; cs.beta[i] = beta; cs.axpy_to[i] = axpy_to; cs.axpy_a[i] = axpy_a;
+        cs.first[i + 1] = cs.first[i] + (n + 63) / 64;
+    };
+    for (int l = L - 1; l >= 0; --l) add_colsum(w.gd.v[l + 1], u.grads + net.offb[l], bgd, net.dims[l + 1], 1.f, nullptr, 0.f);   // db_l += colsum(v_{l+1})
+    // d/dw_out[k] += lmd * sum_b e_L[b][k]   (behind the GEMMs: one of them may have added into that gradient directly)
+    add_colsum(w.ep[L], w.tmp, u.np, net.dims[L], 0.f, u.grads + net.offout, u.lmd);
+    cs.dvals = u.dvals; cs.dnorm = ra.dnorm; cs.stats = u.stats; cs.ng = u.ng; cs.nd = u.nd; cs.np = u.np; cs.lmd = u.lmd;
+    hipLaunchKernelGGL(colsum_batch_kernel, dim3(cs.first[cs.cnt] + 1), dim3(1024), 0, st, cs);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return critic_splitk_flush(st);
+}
+
+// (1) mean D(xg) - mean D(xd) on the concatenated batch, chains on st; every weight-gradient GEMM and bias sum goes to the
+// fork's gradient stream behind a hand-over that says its operands are queued (without a fork: to st)
+static hipError_t critic_wasserstein_half(const CriticUpdate& u, CriticFork* fk, hipStream_t st) {
+    const CriticLayout& net = u.net;
+    const CriticRows& R = u.w.gd;
+    const int L = net.L, bgd = u.ng + u.nd;
+    const bool bf16 = u.c.bf16;
+    hipError_t e;
+    if (!u.eps && (e = critic_stage_inputs(u, INPUT_GD, st)) != hipSuccess) return e;
+    if ((e = critic_forward_pass(net, R.h, u.dvals, bgd, bf16, st)) != hipSuccess) return e;
+    if ((e = critic_two_means(u.dvals, u.stats, u.ng, u.nd, st)) != hipSuccess) return e;
+    if ((e = critic_fill_updown(u.w.up, u.ng, u.nd, st)) != hipSuccess) return e;
+    if ((e = critic_hand_over(fk, st)) != hipSuccess) return e;              // h[L] and up are queued on st
+    if ((e = gemm(u.wg.wout(), bf16, critic_grad_stream(fk, st))) != hipSuccess) return e;
+    if ((e = critic_outgrad(R.h[L], net.wout, u.w.up, R.v[L], bgd, net.dims[L], net.act.leak, st)) != hipSuccess) return e;
+    return critic_backward_chain(net, R.h, R.v, bgd, &u.wg, u.grads, false, bf16, st, fk);
+}
+
+// (2) gradient penalty on xp, chains on sp (the fork's penalty stream, or st); leaves colsum(e_L) in tmp
+static hipError_t critic_penalty_half(const CriticUpdate& u, CriticFork* fk, hipStream_t sp, hipStream_t sg) {
+    const CriticLayout& net = u.net;
+    const CriticUpdateWs& w = u.w;
+    const int L = net.L, np = u.np;
+    const bool bf16 = u.c.bf16;
+    hipError_t e;
+    if (!u.eps && (e = critic_stage_inputs(u, INPUT_P, sp)) != hipSuccess) return e;
+    if ((e = critic_forward_pass(net, w.pen.h, w.dp, np, bf16, sp)) != hipSuccess) return e;
+    // input gradient g = dD/dh0 per sample: v_L = m_L * w_out, chain down to vp[0]
+    if ((e = critic_outgrad(w.pen.h[L], net.wout, nullptr, w.pen.v[L], np, net.dims[L], net.act.leak, sp)) != hipSuccess) return e;
+    if ((e = critic_backward_chain(net, w.pen.h, w.pen.v, np, nullptr, nullptr, true, bf16, sp)) != hipSuccess) return e;
+    // penalty and its gradient w.r.t. g: ep[0] = ghat (np x n0)
+    if ((e = critic_gp_head(w.pen.v[0], w.ep[0], u.stats + 2, np, net.dims[0], u.nx, sp)) != hipSuccess) return e;
+    // backprop through the linear chain g = v_1 W_1^T, v_{l} = m_l * (v_{l+1} W_{l+1}^T), v_L = m_L * w_out:
+    //   dW_l[i][k] += lmd * sum_b e_{l-1}[b][i] v_l[b][k],   e_l = m_l * (e_{l-1} W_l)   (e_0 = ghat)
+    for (int l = 0; l < L; ++l) {
+        if ((e = critic_hand_over(fk, sp)) != hipSuccess) return e;          // e_l (and v_{l+1} before it) are queued on sp
+        if ((e = gemm(u.wg.penalty(l), bf16, sg)) != hipSuccess) return e;
+        if ((e = gemm(gemm_second(net, l, w.ep[l], w.ep[l + 1], w.pen.h[l + 1], np), bf16, sp)) != hipSuccess) return e;
+    }
+    // d/dw_out[k] += lmd * sum_b e_L[b][k]      (v_L = m_L * w_out, mask already applied in e_L): the sum here, the axpy behind the join
+    return critic_colsum(w.ep[L], w.tmp, np, net.dims[L], 0.f, sp);
+}
+
+// Full critic loss + gradient.  stats[0..3] = mean D(xg), mean D(xd), penalty, loss.
+hipError_t critic_loss_grad(const CriticSpec& c, const float* xg, const float* cg, const float* xd, const float* cd, const float* xp,
+                            const float* cp, int ng, int nd, int np, float lmd, float* grads, float* stats, float* dvals, float* ws,
+                            hipStream_t st, const float* eps, float* xp_out) {
+    // eps != nullptr: xp is not an input -- it is formed here, together with the three input blocks, in one launch (xp_out
+    // receives it; ng = nd = np and ONE condition array for the three inputs: the single-process critic step)
+    CriticLayout net;
+    if (!critic_layout(c, net)) return hipErrorInvalidValue;
+    const int* const dims = net.dims;
+    if (eps && (!xp_out || ng != nd || nd != np || cg != cd || cd != cp)) return hipErrorInvalidValue;
+    hipError_t e;
+    const int nc = (cg || cd || cp) ? 3 : 0;
+    if (nc && ((ng && !cg) || (nd && !cd) || (np && !cp))) return hipErrorInvalidValue;   // conditions for all inputs or for none
+    const int L = net.L, bgd = ng + nd;
+    // (the row-block path of wide plain critics zeroes the gradient in its weight-packing launch)
+    const bool rows_path = c.bf16 && bgd > 0 && np > 0 && critic_rows_supported(dims, L);
+    if (!rows_path && (e = hipMemsetAsync(grads, 0, net.nparams * sizeof(float), st)) != hipSuccess) return e;
+    CriticUpdate u{c, net, xg, cg, xd, cd, xp, cp, eps, xp_out, ng, nd, np, dims[0] - nc, lmd, grads, stats, dvals, {}, {}};
+    carve_update(ws, net, bgd, np, u.w);
+    critic_weight_grads(net, u.w, grads, bgd, np, lmd, u.wg);
+    SplitKScope plan(u.w.scratch, u.w.nscratch);      // closed on every return path
+    // side streams (see CriticFork), when every weight-gradient GEMM of both halves goes to slabs
+    bool par = np > 0 && bgd > 0;
+    for (int i = 0; i < u.wg.count() && par; ++i) par = choose_splits(u.wg.g[i].M, u.wg.g[i].N, u.wg.g[i].K) > 1;
+    CriticFork* const fk = par ? critic_fork() : nullptr;
+    if (rows_path) return critic_update_rows(u, par, st);
+    CriticFork::Scope side{fk, st};                   // joined on every return path
+    // (the one-launch inputs in front of the fork: the penalty half reads hp[0]; otherwise each half builds its own)
+    if (eps && (e = critic_stage_inputs(u, INPUT_GD | INPUT_P, st)) != hipSuccess) return e;
+    if ((e = side.fork()) != hipSuccess) return e;    // behind the memset and everything the caller queued
+    const hipStream_t sp = fk ? fk->aux : st;         // stream of the penalty half
+    if ((e = critic_wasserstein_half(u, fk, st)) != hipSuccess) return e;
+    if ((e = critic_penalty_half(u, fk, sp, critic_grad_stream(fk, st))) != hipSuccess) return e;
+    if ((e = side.join()) != hipSuccess) return e;    // the sums below and the slab reduction see both halves
+    if ((e = critic_axpy(grads + net.offout, u.w.tmp, lmd, (long)dims[L], st)) != hipSuccess) return e;
+    if ((e = critic_loss_combine(stats, lmd, st)) != hipSuccess) return e;
+    return critic_splitk_flush(st);                   // grads += the split GEMMs' slabs, in slice order
+}
+
+// Gradient of  -mean D(x)  w.r.t. the tuning-curve part of the input (generator side, wgan.py:236):
+// gx[batch][nx];  also returns mean D in stats[0].
+hipError_t critic_input_grad(const CriticSpec& c, const float* x, const float* cond, int batch, float scale, float* gx, float* stats,
+                             float* ws, hipStream_t st) {
+    CriticLayout net;
+    if (!critic_layout(c, net)) return hipErrorInvalidValue;
+    const int* const dims = net.dims;
+    hipError_t e;
+    const int L = net.L, nc = cond ? 3 : 0, nx = dims[0] - nc;
+    float* p = ws;
+    CriticRows R;
+    carve_rows(p, net, batch, true, R);
+    float* dv = carve(p, batch);
+    if ((e = critic_make_input(x, cond, R.h[0], batch, nx, c.hide_cell_type, st)) != hipSuccess) return e;
+    if (c.bf16 && batch > 0 && critic_rows_supported(dims, L)) {
+        if ((e = critic_rows_eval(net, R.h[0], batch, dv, 1, gx, scale, nx, p, st)) != hipSuccess) return e;
+        return critic_two_means(dv, stats, batch, 0, st);
+    }
+    if ((e = critic_forward_pass(net, R.h, dv, batch, c.bf16, st)) != hipSuccess) return e;
+    if ((e = critic_two_means(dv, stats, batch, 0, st)) != hipSuccess) return e;
+    if ((e = critic_outgrad(R.h[L], net.wout, nullptr, R.v[L], batch, dims[L], net.act.leak, st)) != hipSuccess) return e;
+    if ((e = critic_backward_chain(net, R.h, R.v, batch, nullptr, nullptr, true, c.bf16, st)) != hipSuccess) return e;
+    return critic_gather_scale(R.v[0], gx, batch, dims[0], nx, scale, st);
 }
 
 // ---------------------------------------------------------------------------------

@@ -32,9 +32,6 @@ hipError_t critic_make_input(const float* x, const float* cond, float* h0, int b
 hipError_t critic_gp_head(const float* g, float* ghat, float* pen, int batch, int n0, int nx, hipStream_t st);
 hipError_t critic_two_means(const float* d, float* out, int ng, int nd, hipStream_t st);
 hipError_t critic_loss_combine(float* stats, float lmd, hipStream_t st);
-size_t critic_splitk_scratch_floats(const int* dims, int nlayers, int rows);
-void critic_splitk_begin(float* scratch, size_t cap);
-hipError_t critic_splitk_flush(hipStream_t st);
 hipError_t critic_gather_scale(const float* v0, float* gx, int batch, int n0, int nx, float s, hipStream_t st);
 
 constexpr float LN_EPS = 1e-4f;
@@ -333,8 +330,7 @@ hipError_t critic_norm_loss_grad(const CriticSpec& c, const float* xg, const flo
     }
     float* prod = net.scaled ? carve(p, (long)np * maxd) : nullptr;       // dq p, then dpre y: summed over the rows at once
     // (dh_{l-1} of sweep 2 is written into dc[l-1], which is free by then)
-    critic_splitk_begin(p, critic_splitk_scratch_floats(dims, L, rows));      // the rest of the workspace
-    struct PlanScope { ~PlanScope() { critic_splitk_begin(nullptr, 0); } } plan_scope;    // closed on every return path
+    SplitKScope plan(p, critic_splitk_scratch_floats(dims, L, rows));      // the rest of the workspace; closed on every return path
     if ((e = critic_make_input(xg, cg, A.h[0], ng, nx, c.hide_cell_type, st)) != hipSuccess) return e;
     if ((e = critic_make_input(xd, cd, A.h[0] + (long)ng * dims[0], nd, nx, c.hide_cell_type, st)) != hipSuccess) return e;
     if ((e = critic_make_input(xp, cp, P.h[0], np, nx, c.hide_cell_type, st)) != hipSuccess) return e;

@@ -281,6 +281,17 @@ inline int blocks_for(long n) { long b = (n + 255) / 256; return (int)(b < 1 ? 1
 inline float* carve(float*& p, long n) { float* r = p; p += n; return r; }
 
 // ssn_critic.hip: plain layers, any slope (the layer-by-layer MFMA GEMM chain)
+// (deterministic split-K of the weight-gradient GEMMs: between begin and flush every split GEMM of the calling thread writes slabs
+// into `scratch`, and the flush adds them in the order of issue)
+size_t critic_splitk_scratch_floats(const int* dims, int nlayers, int rows);
+void critic_splitk_begin(float* scratch, size_t cap);
+hipError_t critic_splitk_flush(hipStream_t st);
+struct SplitKScope {     // the plan is closed on every way out of the scope, flushed or not
+    SplitKScope(float* scratch, size_t cap) { critic_splitk_begin(scratch, cap); }
+    ~SplitKScope() { critic_splitk_begin(nullptr, 0); }
+    SplitKScope(const SplitKScope&) = delete;
+    SplitKScope& operator=(const SplitKScope&) = delete;
+};
 size_t critic_workspace_floats(const int* dims, int nlayers, int batch_gd, int batch_p);
 hipError_t critic_forward(const CriticSpec& c, const float* x, const float* cond, int batch, float* out, float* ws, hipStream_t st);
 // (inputs_ready: ws already starts with the input block of [xa; xb] -- critic_loss_grad on the same rows leaves it there)
