@@ -28,6 +28,12 @@ int fail(hipError_t e, const char* where) {
         if (e__ != hipSuccess) return fail(e__, #expr);   \
     } while (0)
 
+// J, D, S of the C surface (four values each) as the launchers take them: jds[12]
+template <typename T>
+void pack_jds(const T* J, const T* D, const T* S, T* jds) {
+    for (int q = 0; q < 4; ++q) { jds[q] = J[q]; jds[4 + q] = D[q]; jds[8 + q] = S[q]; }
+}
+
 // one round of the device rejection sampler (ssn_fp_select_f64 / _f32)
 template <typename T>
 int fp_select_impl(const char* name, const int* codes, const T* x, int A, int R, int NB, int M, const int* probes, int nprobe,
@@ -712,7 +718,7 @@ static int build_dw_impl(const T* z, const T* J, const T* D, const T* S, int whi
         return SSN_ERR_BASE + (int)hipErrorInvalidValue;
     }
     T jds[12];
-    for (int q = 0; q < 4; ++q) { jds[q] = J[q]; jds[4 + q] = D[q]; jds[8 + q] = S[q]; }
+    pack_jds(J, D, S, jds);
     SSN_TRY(ssn::launch_build_dw<T>(z, jds, which, dW, B, N, (hipStream_t)stream));
     return 0;
 }
@@ -729,6 +735,28 @@ static int ss_system_impl(const T* R, const T* W, const T* dW, int dw_per_draw, 
                                      (hipStream_t)stream));
     return 0;
 }
+
+// the device MT19937 draw (ssn_mt19937.hip): one body per _f32 / _f64 pair, and the tail of a call
+template <typename T>
+static int mt_sample(unsigned int* key, int* pos, unsigned long long total, unsigned long long skip, unsigned long long count, T* out, void* stream) {
+    if (!key || !pos) { g_last_error = "ssn_mt19937_random_sample: null state"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    SSN_TRY(ssn::mt19937_draw(key, pos, total, skip, count, out, (int)sizeof(T), (hipStream_t)stream));
+    return 0;
+}
+template <typename T>
+static int mt_sample_begin(const unsigned int* key, int pos, unsigned long long total, unsigned long long skip, unsigned long long count,
+                           T* out, void* stream, int* ticket) {
+    if (!key || !ticket) { g_last_error = "ssn_mt19937_random_sample_begin: null state / ticket"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
+    *ticket = -1;
+    SSN_TRY(ssn::mt19937_begin(key, pos, total, skip, count, out, (int)sizeof(T), (hipStream_t)stream, ticket));
+    return 0;
+}
+static ssn::MtTail mt_tail(int kind, unsigned long long total, unsigned long long skip, unsigned long long count, float* out) {
+    ssn::MtTail tail;
+    tail.kind = kind; tail.total = total; tail.skip = skip; tail.count = count; tail.out = out;
+    return tail;
+}
+
 extern "C" {
 
 long ssn_critic_num_params(const int* dims, int nlayers) { return critic_num_params(dims, nullptr, nlayers); }
@@ -1311,14 +1339,14 @@ int ssn_weight_grad_f64(const double* delta, const double* traj, double* gW, int
 int ssn_jds_grad_f32(const float* gW, const float* z, const float* J, const float* D, const float* S, double* out,
                      int B, int N, void* stream) {
     float jds[12];
-    for (int q = 0; q < 4; ++q) { jds[q] = J[q]; jds[4 + q] = D[q]; jds[8 + q] = S[q]; }
+    pack_jds(J, D, S, jds);
     SSN_TRY(ssn::launch_jds_grad<float>(gW, z, jds, out, B, N, (hipStream_t)stream));
     return 0;
 }
 int ssn_jds_grad_f64(const double* gW, const double* z, const double* J, const double* D, const double* S, double* out,
                      int B, int N, void* stream) {
     double jds[12];
-    for (int q = 0; q < 4; ++q) { jds[q] = J[q]; jds[4 + q] = D[q]; jds[8 + q] = S[q]; }
+    pack_jds(J, D, S, jds);
     SSN_TRY(ssn::launch_jds_grad<double>(gW, z, jds, out, B, N, (hipStream_t)stream));
     return 0;
 }
@@ -1370,7 +1398,7 @@ int ssn_solve_batch_host_f64(const double* W, const double* ext, int ext_per_dra
 
 int ssn_build_w_f32(const float* z, const float* J, const float* D, const float* S, float* W, int B, int N, void* stream) {
     float jds[12];
-    for (int q = 0; q < 4; ++q) { jds[q] = J[q]; jds[4 + q] = D[q]; jds[8 + q] = S[q]; }
+    pack_jds(J, D, S, jds);
     SSN_TRY(ssn::launch_build_w<float>(z, jds, W, B, N, (hipStream_t)stream));
     return 0;
 }
@@ -1381,21 +1409,21 @@ int ssn_build_w_devparams_f32(const float* z, const float* jds_dev, float* W, in
 }
 int ssn_build_w_f64(const double* z, const double* J, const double* D, const double* S, double* W, int B, int N, void* stream) {
     double jds[12];
-    for (int q = 0; q < 4; ++q) { jds[q] = J[q]; jds[4 + q] = D[q]; jds[8 + q] = S[q]; }
+    pack_jds(J, D, S, jds);
     SSN_TRY(ssn::launch_build_w<double>(z, jds, W, B, N, (hipStream_t)stream));
     return 0;
 }
 int ssn_build_w_philox_f32(unsigned long long seed, unsigned long long offset, const float* J, const float* D, const float* S,
                            float* W, float* z, int B, int N, void* stream) {
     float jds[12];
-    for (int q = 0; q < 4; ++q) { jds[q] = J[q]; jds[4 + q] = D[q]; jds[8 + q] = S[q]; }
+    pack_jds(J, D, S, jds);
     SSN_TRY(ssn::launch_build_w_philox<float>(seed, offset, jds, W, z, B, N, (hipStream_t)stream));
     return 0;
 }
 int ssn_build_w_philox_f64(unsigned long long seed, unsigned long long offset, const double* J, const double* D, const double* S,
                            double* W, double* z, int B, int N, void* stream) {
     double jds[12];
-    for (int q = 0; q < 4; ++q) { jds[q] = J[q]; jds[4 + q] = D[q]; jds[8 + q] = S[q]; }
+    pack_jds(J, D, S, jds);
     SSN_TRY(ssn::launch_build_w_philox<double>(seed, offset, jds, W, z, B, N, (hipStream_t)stream));
     return 0;
 }
@@ -1409,29 +1437,19 @@ int ssn_mt19937_jump_poly(unsigned long long nblocks, unsigned long long* bits) 
 }
 int ssn_mt19937_random_sample_f32(unsigned int* key, int* pos, unsigned long long total, unsigned long long skip,
                                   unsigned long long count, float* out, void* stream) {
-    if (!key || !pos) { g_last_error = "ssn_mt19937_random_sample: null state"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    SSN_TRY(ssn::mt19937_draw(key, pos, total, skip, count, out, 4, (hipStream_t)stream));
-    return 0;
+    return mt_sample<float>(key, pos, total, skip, count, out, stream);
 }
 int ssn_mt19937_random_sample_f64(unsigned int* key, int* pos, unsigned long long total, unsigned long long skip,
                                   unsigned long long count, double* out, void* stream) {
-    if (!key || !pos) { g_last_error = "ssn_mt19937_random_sample: null state"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    SSN_TRY(ssn::mt19937_draw(key, pos, total, skip, count, out, 8, (hipStream_t)stream));
-    return 0;
+    return mt_sample<double>(key, pos, total, skip, count, out, stream);
 }
 int ssn_mt19937_random_sample_begin_f32(const unsigned int* key, int pos, unsigned long long total, unsigned long long skip,
                                         unsigned long long count, float* out, void* stream, int* ticket) {
-    if (!key || !ticket) { g_last_error = "ssn_mt19937_random_sample_begin: null state / ticket"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    *ticket = -1;
-    SSN_TRY(ssn::mt19937_begin(key, pos, total, skip, count, out, 4, (hipStream_t)stream, ticket));
-    return 0;
+    return mt_sample_begin<float>(key, pos, total, skip, count, out, stream, ticket);
 }
 int ssn_mt19937_random_sample_begin_f64(const unsigned int* key, int pos, unsigned long long total, unsigned long long skip,
                                         unsigned long long count, double* out, void* stream, int* ticket) {
-    if (!key || !ticket) { g_last_error = "ssn_mt19937_random_sample_begin: null state / ticket"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    *ticket = -1;
-    SSN_TRY(ssn::mt19937_begin(key, pos, total, skip, count, out, 8, (hipStream_t)stream, ticket));
-    return 0;
+    return mt_sample_begin<double>(key, pos, total, skip, count, out, stream, ticket);
 }
 int ssn_build_w_mt19937_begin_f32(const unsigned int* key, int pos, int B_total, int b0, int nb, const float* J, const float* D,
                                   const float* S, float* W, float* z, int N, void* stream, int* ticket) {
@@ -1441,7 +1459,7 @@ int ssn_build_w_mt19937_begin_f32(const unsigned int* key, int pos, int B_total,
     }
     *ticket = -1;
     float jds[12];
-    for (int q = 0; q < 4; ++q) { jds[q] = J[q]; jds[4 + q] = D[q]; jds[8 + q] = S[q]; }
+    pack_jds(J, D, S, jds);
     const unsigned long long mm = 4ull * N * N;
     SSN_TRY(ssn::mt19937_begin(key, pos, mm * B_total, mm * b0, mm * nb, z, 4, (hipStream_t)stream, ticket, nb ? W : nullptr, jds, N));
     return 0;
@@ -1453,8 +1471,7 @@ int ssn_mt19937_random_sample_tail_begin_f32(const unsigned int* key, int pos, u
     if (!key || !ticket) { g_last_error = "ssn_mt19937_random_sample_tail_begin: null state / ticket"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
     *ticket = -1;
     if (tail_kind != 1 && tail_kind != 2) { g_last_error = "ssn_mt19937_random_sample_tail_begin: tail_kind must be 1 (choice(2, n) * 2 - 1) or 2 (rand(n) * 2 - 1)"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
-    ssn::MtTail tail;
-    tail.kind = tail_kind; tail.total = tail_total; tail.skip = tail_skip; tail.count = tail_count; tail.out = tail_out;
+    const ssn::MtTail tail = mt_tail(tail_kind, tail_total, tail_skip, tail_count, tail_out);
     SSN_TRY(ssn::mt19937_begin(key, pos, total, skip, count, out, 4, (hipStream_t)stream, ticket, nullptr, nullptr, 0, &tail));
     return 0;
 }
@@ -1467,10 +1484,9 @@ int ssn_build_w_mt19937_tail_begin_f32(const unsigned int* key, int pos, int B_t
     }
     *ticket = -1;
     float jds[12];
-    for (int q = 0; q < 4; ++q) { jds[q] = J[q]; jds[4 + q] = D[q]; jds[8 + q] = S[q]; }
+    pack_jds(J, D, S, jds);
     const unsigned long long mm = 4ull * N * N, m = 2ull * N;
-    ssn::MtTail tail;
-    tail.kind = tail_kind; tail.total = m * B_total; tail.skip = m * b0; tail.count = m * nb; tail.out = zin;
+    const ssn::MtTail tail = mt_tail(tail_kind, m * B_total, m * b0, m * nb, zin);
     SSN_TRY(ssn::mt19937_begin(key, pos, mm * B_total, mm * b0, mm * nb, z, 4, (hipStream_t)stream, ticket, nb ? W : nullptr, jds, N, &tail));
     return 0;
 }
@@ -1480,8 +1496,7 @@ int ssn_mt19937_plan(int pos, unsigned long long total, unsigned long long skip,
 }
 int ssn_mt19937_plan_tail(int pos, unsigned long long total, unsigned long long skip, unsigned long long count, int tail_kind,
                           unsigned long long tail_total, unsigned long long tail_skip, unsigned long long tail_count, long* out) {
-    ssn::MtTail tail;
-    tail.kind = tail_kind; tail.total = tail_total; tail.skip = tail_skip; tail.count = tail_count;
+    const ssn::MtTail tail = mt_tail(tail_kind, tail_total, tail_skip, tail_count, nullptr);
     if (!out || !ssn::mt19937_plan(pos, total, skip, count, out, &tail)) { g_last_error = "ssn_mt19937_plan_tail: invalid argument"; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
     return 0;
 }

@@ -36,6 +36,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 #include "ssn_host.h"
 #include "ssn_mt19937_poly.h"
@@ -43,21 +44,10 @@
 namespace ssn {
 namespace mt {
 
-#ifndef SSN_MT_STRIDE0_LOG2
-#define SSN_MT_STRIDE0_LOG2 7
-#endif
-#ifndef SSN_MT_RADIX_LOG2
-#define SSN_MT_RADIX_LOG2 8
-#endif
-#ifndef SSN_MT_MAX_STEP
-#define SSN_MT_MAX_STEP 8
-#endif
-#ifndef SSN_MT_FRACTIONAL_ROUNDS
-#define SSN_MT_FRACTIONAL_ROUNDS 0
-#endif
 constexpr int kLevels = 3;                 // strides 128 * 256^l blocks
-constexpr int kStride0Log2 = SSN_MT_STRIDE0_LOG2;
-constexpr int kRadixLog2 = SSN_MT_RADIX_LOG2;   // 255 polynomials per level: up to 255 * 128 * step blocks (10 M doubles x step) in ONE round of jumps
+constexpr int kStride0Log2 = 7;
+constexpr int kRadixLog2 = 8;              // 255 polynomials per level: up to 255 * 128 * step blocks (10 M doubles x step) in ONE round of jumps
+constexpr int kMaxStep = 8;                // segments of 128 * step blocks, step = 1, 2, 4, 8
 constexpr int kDigits = (1 << kRadixLog2) - 1;
 constexpr int kSegLevel = 0;               // segments start at states of level 0: every `step`-th one, 128 * step blocks long
 constexpr int kSoloParts = 16;             // workgroups of the kernel that computes the state after the draw
@@ -108,17 +98,23 @@ __device__ __forceinline__ uint32_t xor_parts(const uint32_t* src, int nparts, i
     return v;
 }
 
+// x[624 .. 624 + n) of a sequence whose first 624 words are in x (LDS), in place: 227 independent words per step, by threads
+// 0 .. 226 of the whole workgroup, one barrier a step
+__device__ __forceinline__ void extend_sequence(uint32_t* x, int n, int tid) {
+    for (int k0 = 0; k0 < n; k0 += kN - kM) {
+        const int k = k0 + tid;
+        if (tid < kN - kM && k < n) x[k + kN] = x[k + kM] ^ twist_d(x[k], x[k + 1]);
+        __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(256) void mt_expand_kernel(const ExpandArgs a) {
     extern __shared__ __align__(16) uint32_t x[];
     const int tid = threadIdx.x;
     const uint32_t* src = a.states ? a.states + (size_t)blockIdx.x * a.nparts * kN : nullptr;
     for (int j = tid; j < kN; j += 256) x[j] = src ? xor_parts(src, a.nparts, j) : a.root.w[j];
     __syncthreads();
-    for (int k0 = 0; k0 + kN < kXSeq; k0 += kN - kM) {          // 227 independent words per step
-        const int k = k0 + tid;
-        if (tid < kN - kM && k + kN < kXSeq) x[k + kN] = x[k + kM] ^ twist_d(x[k], x[k + 1]);
-        __syncthreads();
-    }
+    extend_sequence(x, kXSeq - kN, tid);
     uint32_t* o = a.xseq + (size_t)blockIdx.x * kXSeq;
     for (int k = tid; k < kXSeq; k += 256) o[k] = x[k];
 }
@@ -147,6 +143,33 @@ struct JumpArgs {
     }
 #define SSN_MT_TAP8(k) SSN_MT_TAP2(k) SSN_MT_TAP2(k + 1) SSN_MT_TAP2(k + 2) SSN_MT_TAP2(k + 3)
 
+// A share's window in a workgroup's LDS: the words at c0, the same shifted by one word at c1 (the caller fills both), and the
+// zero area that the padding codes point to (cleared before the barrier that precedes the taps)
+__device__ __forceinline__ uint32_t* window_words(unsigned char* lds) { return (uint32_t*)lds; }
+__device__ __forceinline__ uint32_t* window_shifted(unsigned char* lds) { return (uint32_t*)(lds + kCopy1Off); }
+__device__ __forceinline__ void clear_zero_area(unsigned char* lds, int tid) {
+    uint32_t* zz = (uint32_t*)(lds + kZeroOff);
+    for (int k = tid; k < 640; k += 320) zz[k] = 0u;
+}
+// XOR of the word pairs at a share's taps, for lane pair `tid` of the 312 (the lanes beyond read with the last one and keep
+// nothing).  codes / count: the share's; its groups of 128 taps are split evenly among the share's `sub` workgroups, this is `sb`.
+__device__ __forceinline__ void accumulate_taps(const unsigned char* lds, const uint16_t* codes, int count, int sb, int sub, int tid,
+                                                uint32_t& acc0, uint32_t& acc1) {
+    const int groups = count >> 7;
+    const int g0 = groups * sb / sub, g1 = groups * (sb + 1) / sub;
+    const uint32_t* cp = (const uint32_t*)codes + (tid & 63);
+    const int lane8 = (tid < kN / 2 ? tid : kN / 2 - 1) * 8;
+    uint32_t cw = cp[(size_t)g0 * 64];
+    for (int g = g0; g < g1; ++g) {
+        const uint32_t cnext = cp[(size_t)(g + 1) * 64];                   // (the table is padded: one group ahead is in bounds)
+        SSN_MT_TAP8(0) SSN_MT_TAP8(4) SSN_MT_TAP8(8) SSN_MT_TAP8(12) SSN_MT_TAP8(16) SSN_MT_TAP8(20) SSN_MT_TAP8(24) SSN_MT_TAP8(28)
+        SSN_MT_TAP8(32) SSN_MT_TAP8(36) SSN_MT_TAP8(40) SSN_MT_TAP8(44) SSN_MT_TAP8(48) SSN_MT_TAP8(52) SSN_MT_TAP8(56) SSN_MT_TAP8(60)
+        cw = cnext;
+    }
+}
+#undef SSN_MT_TAP8
+#undef SSN_MT_TAP2
+
 __global__ __launch_bounds__(320) void mt_jump_kernel(const JumpArgs a) {
     extern __shared__ __align__(16) unsigned char lds[];
     const int tid = threadIdx.x;
@@ -160,28 +183,18 @@ __global__ __launch_bounds__(320) void mt_jump_kernel(const JumpArgs a) {
         return;
     }
     const int base = f * kShareSpan;
-    uint32_t* c0 = (uint32_t*)lds;
-    uint32_t* c1 = (uint32_t*)(lds + kCopy1Off);
-    uint32_t* zz = (uint32_t*)(lds + kZeroOff);
+    uint32_t* c0 = window_words(lds);
+    uint32_t* c1 = window_shifted(lds);
     for (int k = tid; k <= kShareSpan + kN; k += 320) {
         const uint32_t v = xs[base + k];
         if (k < kShareSpan + kN) c0[k] = v;
         if (k) c1[k - 1] = v;
     }
-    for (int k = tid; k < 640; k += 320) zz[k] = 0u;
+    clear_zero_area(lds, tid);
     __syncthreads();
-    const int groups = a.counts[(d - 1) * kShares + f] >> 7;                 // groups of 128 taps
-    const int g0 = groups * sb / a.sub, g1 = groups * (sb + 1) / a.sub;
-    const uint32_t* cp = (const uint32_t*)(a.codes + ((size_t)(d - 1) * kShares + f) * kCodeCap) + (tid & 63);
-    const int lane8 = (tid < kN / 2 ? tid : kN / 2 - 1) * 8;
+    const int share = (d - 1) * kShares + f;
     uint32_t acc0 = 0, acc1 = 0;
-    uint32_t cw = cp[(size_t)g0 * 64];
-    for (int g = g0; g < g1; ++g) {
-        const uint32_t cnext = cp[(size_t)(g + 1) * 64];                   // (the table is padded: one group ahead is in bounds)
-        SSN_MT_TAP8(0) SSN_MT_TAP8(4) SSN_MT_TAP8(8) SSN_MT_TAP8(12) SSN_MT_TAP8(16) SSN_MT_TAP8(20) SSN_MT_TAP8(24) SSN_MT_TAP8(28)
-        SSN_MT_TAP8(32) SSN_MT_TAP8(36) SSN_MT_TAP8(40) SSN_MT_TAP8(44) SSN_MT_TAP8(48) SSN_MT_TAP8(52) SSN_MT_TAP8(56) SSN_MT_TAP8(60)
-        cw = cnext;
-    }
+    accumulate_taps(lds, a.codes + (size_t)share * kCodeCap, a.counts[share], sb, a.sub, tid, acc0, acc1);
     if (tid < kN / 2) { out[2 * tid] = acc0; out[2 * tid + 1] = acc1; }
 }
 
@@ -211,11 +224,10 @@ __global__ __launch_bounds__(320) void mt_solo_kernel(const SoloArgs a) {
     constexpr int sub = kSoloParts / kShares;
     const int f = blockIdx.y / sub, sb = blockIdx.y % sub;
     const int base = f * kShareSpan;
-    uint32_t* c0 = (uint32_t*)lds;
-    uint32_t* c1 = (uint32_t*)(lds + kCopy1Off);
-    uint32_t* zz = (uint32_t*)(lds + kZeroOff);
+    uint32_t* c0 = window_words(lds);
+    uint32_t* c1 = window_shifted(lds);
     for (int j = tid; j < kN; j += 320) ring[j] = a.root.w[j];
-    for (int k = tid; k < 640; k += 320) zz[k] = 0u;
+    clear_zero_area(lds, tid);
     __syncthreads();
     // run-up: x[624 .. ) in the ring (x[k] at k mod 1248) until x[base .. base + 624) is there
     int k0 = 0;
@@ -227,25 +239,11 @@ __global__ __launch_bounds__(320) void mt_solo_kernel(const SoloArgs a) {
     }
     for (int j = tid; j < kN; j += 320) c0[j] = ring[(base + j) % (2 * kN)];
     __syncthreads();
-    for (int q0 = 0; q0 + kN <= kShareSpan + kN; q0 += kN - kM) {          // the window, in place
-        const int q = q0 + tid;
-        if (tid < kN - kM && q + kN <= kShareSpan + kN) c0[q + kN] = c0[q + kM] ^ twist_d(c0[q], c0[q + 1]);
-        __syncthreads();
-    }
+    extend_sequence(c0, kShareSpan + 1, tid);                              // the window, in place
     for (int k = tid; k < kShareSpan + kN; k += 320) c1[k] = c0[k + 1];
     __syncthreads();
-    const int groups = a.counts[f] >> 7;
-    const int g0 = groups * sb / sub, g1 = groups * (sb + 1) / sub;
-    const uint32_t* cp = (const uint32_t*)(a.codes + (size_t)f * kCodeCap) + (tid & 63);
-    const int lane8 = (tid < kN / 2 ? tid : kN / 2 - 1) * 8;
     uint32_t acc0 = 0, acc1 = 0;
-    uint32_t cw = cp[(size_t)g0 * 64];
-    for (int g = g0; g < g1; ++g) {
-        const uint32_t cnext = cp[(size_t)(g + 1) * 64];
-        SSN_MT_TAP8(0) SSN_MT_TAP8(4) SSN_MT_TAP8(8) SSN_MT_TAP8(12) SSN_MT_TAP8(16) SSN_MT_TAP8(20) SSN_MT_TAP8(24) SSN_MT_TAP8(28)
-        SSN_MT_TAP8(32) SSN_MT_TAP8(36) SSN_MT_TAP8(40) SSN_MT_TAP8(44) SSN_MT_TAP8(48) SSN_MT_TAP8(52) SSN_MT_TAP8(56) SSN_MT_TAP8(60)
-        cw = cnext;
-    }
+    accumulate_taps(lds, a.codes + (size_t)f * kCodeCap, a.counts[f], sb, sub, tid, acc0, acc1);
     uint32_t* mine = a.partials + (size_t)blockIdx.y * kN;
     if (tid < kN / 2) { mine[2 * tid] = acc0; mine[2 * tid + 1] = acc1; }
     // the last workgroup to get here finishes the job (nobody waits for anybody)
@@ -261,16 +259,7 @@ __global__ __launch_bounds__(320) void mt_solo_kernel(const SoloArgs a) {
         ring[j] = v;
     }
     __syncthreads();
-    // one regeneration, not in place: new block into ring[624 ..)
-    for (int q0 = 0; q0 < kN; q0 += kN - kM) {
-        const int q = q0 + tid;
-        if (tid < kN - kM && q < kN) {
-            const uint32_t nxt = q + 1 < kN ? ring[q + 1] : ring[kN];                 // x[624] = the new word 0
-            const uint32_t far = q + kM < kN ? ring[q + kM] : ring[kN + q + kM - kN];
-            ring[kN + q] = far ^ twist_d(ring[q], nxt);
-        }
-        __syncthreads();
-    }
+    extend_sequence(ring, kN, tid);            // one regeneration: the new block into ring[624 ..)
     for (int j = tid; j < kN; j += 320) a.out[j] = ring[kN + j];
     if (tid == 0) *a.counter = 0u;
 }
@@ -346,6 +335,11 @@ __device__ __forceinline__ void gen_block(uint32_t* flat, int lane) {
     gen_store<5>(flat, neww, lane, act, r1);
 }
 
+// randomkit rk_double: (a >> 5, b >> 6) -> (a * 2^26 + b) / 2^53, exact in double
+__device__ __forceinline__ double rk_double(uint32_t w0, uint32_t w1) {
+    return ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6)) * (1.0 / 9007199254740992.0);
+}
+
 template <typename T, bool ODD, bool BUILDW, bool TAIL>
 __device__ __forceinline__ void emit_pass(const GenArgs<T>& a, const uint32_t* blk, const uint32_t* carry_in,
                                           int c, int lane, long qb, const float* gtab) {
@@ -364,9 +358,7 @@ __device__ __forceinline__ void emit_pass(const GenArgs<T>& a, const uint32_t* b
     w1 = temper_d(w1);
     const long qq = qb + (i >> 1) - a.skip;
     if (act && (unsigned long)qq < (unsigned long)a.count) {
-        // randomkit rk_double: (a >> 5, b >> 6) -> (a * 2^26 + b) / 2^53, exact in double
-        const double v = ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6)) * (1.0 / 9007199254740992.0);
-        const T z = (T)v;          // T = float: round to nearest even, as numpy's astype(float32)
+        const T z = (T)rk_double(w0, w1);          // T = float: round to nearest even, as numpy's astype(float32)
         if constexpr (BUILDW) {
             // the element's place in its draw: e = (b M + row) M + col
             const unsigned e = (unsigned)qq, M = 2u * (unsigned)a.N;
@@ -396,8 +388,7 @@ __device__ __forceinline__ void emit_pass(const GenArgs<T>& a, const uint32_t* b
             } else {
                 const long e = tq - a.tail_skip;
                 if ((unsigned long)e < (unsigned long)a.tail_count) {
-                    const double v = ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6)) * (1.0 / 9007199254740992.0);
-                    a.tail_out[e] = (float)(2.0 * v - 1.0);       // (exact in double, then round to nearest: the host's astype)
+                    a.tail_out[e] = (float)(2.0 * rk_double(w0, w1) - 1.0);      // (exact in double, then round to nearest: the host's astype)
                 }
             }
         }
@@ -510,12 +501,15 @@ struct HostTables {
 };
 static HostTables& host_tables() { static HostTables* t = new HostTables; return *t; }
 
+struct CodeTable { uint16_t* codes = nullptr; int* counts = nullptr; };     // a polynomial on the device, as pack_codes lays it out
+
 struct DeviceTables {
-    uint16_t* codes[kLevels] = {};
-    int* counts[kLevels] = {};
-    bool lds_attr = false;
-    // side stream, pinned state buffer and workspace of the kernel that computes the state after the draw
+    int dev = 0;
+    CodeTable level[kLevels];
+    // side stream, every event and pinned buffer below, the workspace of the kernel that computes the state after the draw, the
+    // expand kernel's LDS attribute (make_side_state: `side_ready` is set last, so a call that failed half way is taken up by the next)
     hipStream_t side = nullptr;
+    bool side_ready = false;
     // the state after a draw is handed over through a ticket (a draw may return before that state is known: the host does
     // the waiting when it next needs its generator): pinned key buffer + event per ticket
     static constexpr int kTickets = 8;
@@ -542,14 +536,29 @@ struct DeviceTables {
     BulkSet bulk[kBulkSets];
     unsigned next_bulk = 0;
     // exact polynomials by jump length in blocks (a run draws the same shapes over and over: two lengths per shape)
-    struct Exact { uint16_t* codes; int* counts; };
-    std::map<long, Exact> exact;
+    std::map<long, CodeTable> exact;
 };
+using Ticket = DeviceTables::Ticket;
+using BulkSet = DeviceTables::BulkSet;
 static std::mutex g_dev_mu;
 static DeviceTables* g_dev[64] = {};
 
+// a (codes, counts) pair to device memory; on failure nothing stays allocated
+static hipError_t upload_codes(const uint16_t* codes, size_t ncodes, const int* counts, size_t ncounts, CodeTable* out) {
+    CodeTable d;
+    hipError_t e;
+    if ((e = hipMalloc((void**)&d.codes, ncodes * sizeof(uint16_t))) == hipSuccess
+        && (e = hipMalloc((void**)&d.counts, ncounts * sizeof(int))) == hipSuccess
+        && (e = hipMemcpy(d.codes, codes, ncodes * sizeof(uint16_t), hipMemcpyHostToDevice)) == hipSuccess)
+        e = hipMemcpy(d.counts, counts, ncounts * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) { *out = d; return e; }
+    if (d.codes) (void)hipFree(d.codes);
+    if (d.counts) (void)hipFree(d.counts);
+    return e;
+}
+
 // the device copy of t^(624 nblocks) mod phi (caller holds t->chain_mu)
-static hipError_t exact_poly(DeviceTables* t, long nblocks, DeviceTables::Exact* out) {
+static hipError_t exact_poly(DeviceTables* t, long nblocks, CodeTable* out) {
     auto it = t->exact.find(nblocks);
     if (it != t->exact.end()) { *out = it->second; return hipSuccess; }
     if (t->exact.size() >= 256) {          // (a run that keeps changing its draw length: start over rather than grow for ever)
@@ -564,32 +573,16 @@ static hipError_t exact_poly(DeviceTables* t, long nblocks, DeviceTables::Exact*
         if (!h.ensure_field()) return hipErrorUnknown;
         pack_codes(h.field.block_jump((unsigned long long)nblocks), codes.data(), counts);
     }
-    DeviceTables::Exact x{};
-    hipError_t e;
-    if ((e = hipMalloc((void**)&x.codes, codes.size() * sizeof(uint16_t))) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&x.counts, sizeof counts)) == hipSuccess
-        && (e = hipMemcpy(x.codes, codes.data(), codes.size() * sizeof(uint16_t), hipMemcpyHostToDevice)) == hipSuccess)
-        e = hipMemcpy(x.counts, counts, sizeof counts, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(x.codes); if (x.counts) (void)hipFree(x.counts); return e; }
-    t->exact[nblocks] = x;
-    *out = x;
-    return hipSuccess;
+    const hipError_t e = upload_codes(codes.data(), codes.size(), counts, kShares, out);
+    if (e == hipSuccess) t->exact[nblocks] = *out;
+    return e;
 }
 
-static hipError_t device_tables(int need_level, DeviceTables** out) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+// each piece made once, `side_ready` set when all are there: a call that fails half way is taken up by the next where it stopped
+static hipError_t make_side_state(DeviceTables* t) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mt_expand_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)(kXSeq * sizeof(uint32_t)));
     if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    std::lock_guard<std::mutex> g(g_dev_mu);
-    DeviceTables*& t = g_dev[dev];
-    if (!t) t = new DeviceTables;
-    if (!t->lds_attr) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(mt_expand_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(kXSeq * sizeof(uint32_t)));
-        if (e != hipSuccess) return e;
-        t->lds_attr = true;
-    }
     if (!t->side) {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
@@ -597,26 +590,53 @@ static hipError_t device_tables(int need_level, DeviceTables** out) {
         const char* pe = getenv("SSN_MT_PRIORITY");
         const int prio = (pe && pe[0] == 'l') ? lo : ((pe && pe[0] == 'm') ? (lo + hi) / 2 : hi);
         if ((e = hipStreamCreateWithPriority(&t->side, hipStreamNonBlocking, prio)) != hipSuccess) return e;
-        for (auto& tk : t->tickets) {
-            if ((e = hipEventCreateWithFlags(&tk.done, hipEventDisableTiming)) != hipSuccess) return e;
-            if ((e = hipHostMalloc((void**)&tk.pinned, sizeof(uint32_t) * kN, hipHostMallocDefault)) != hipSuccess) return e;
-        }
-        if ((e = hipMalloc((void**)&t->chain, sizeof(uint32_t) * ((size_t)kSoloParts * kN + 16))) != hipSuccess) return e;
-        if ((e = hipMemset(t->chain, 0, sizeof(uint32_t) * ((size_t)kSoloParts * kN + 16))) != hipSuccess) return e;
     }
+    for (auto& tk : t->tickets)
+        if ((!tk.done && (e = hipEventCreateWithFlags(&tk.done, hipEventDisableTiming)) != hipSuccess)
+            || (!tk.pinned && (e = hipHostMalloc((void**)&tk.pinned, sizeof(uint32_t) * kN, hipHostMallocDefault)) != hipSuccess)) return e;
+    for (auto& bs : t->bulk)
+        if ((!bs.ready && (e = hipEventCreateWithFlags(&bs.ready, hipEventDisableTiming)) != hipSuccess)
+            || (!bs.consumed && (e = hipEventCreateWithFlags(&bs.consumed, hipEventDisableTiming)) != hipSuccess)) return e;
+    const size_t chain_bytes = sizeof(uint32_t) * ((size_t)kSoloParts * kN + 16);
+    if (!t->chain && (e = hipMalloc((void**)&t->chain, chain_bytes)) != hipSuccess) return e;
+    if ((e = hipMemset(t->chain, 0, chain_bytes)) != hipSuccess) return e;
+    t->side_ready = true;
+    return hipSuccess;
+}
+
+// the current device's tables, with the polynomial levels 0 .. need_level on the device (-1: none)
+static hipError_t device_tables(int need_level, DeviceTables** out) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+    std::lock_guard<std::mutex> g(g_dev_mu);
+    DeviceTables*& t = g_dev[dev];
+    if (!t) { t = new DeviceTables; t->dev = dev; }
+    if (!t->side_ready && (e = make_side_state(t)) != hipSuccess) return e;
     HostTables& h = host_tables();
     std::lock_guard<std::mutex> gh(h.mu);
     if (need_level >= 0 && !h.ensure_level(need_level)) return hipErrorUnknown;
-    for (int l = 0; l <= need_level; ++l) {
-        if (t->codes[l]) continue;
-        uint16_t* dc = nullptr; int* dn = nullptr;
-        if ((e = hipMalloc((void**)&dc, h.codes[l].size() * sizeof(uint16_t))) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&dn, h.counts[l].size() * sizeof(int))) != hipSuccess) return e;
-        if ((e = hipMemcpy(dc, h.codes[l].data(), h.codes[l].size() * sizeof(uint16_t), hipMemcpyHostToDevice)) != hipSuccess) return e;
-        if ((e = hipMemcpy(dn, h.counts[l].data(), h.counts[l].size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) return e;
-        t->codes[l] = dc; t->counts[l] = dn;
-    }
+    for (int l = 0; l <= need_level; ++l)
+        if (!t->level[l].codes
+            && (e = upload_codes(h.codes[l].data(), h.codes[l].size(), h.counts[l].data(), h.counts[l].size(), &t->level[l])) != hipSuccess)
+            return e;
     *out = t;
+    return hipSuccess;
+}
+
+// ---- host: tickets -------------------------------------------------------------------------------------------------------
+// A ticket's id: generation of its slot (15 bits: has the slot been taken over since? then the state is in `parked`), device, slot
+struct TicketId { int gen, dev, slot; };
+static inline int ticket_id(unsigned gen, int dev, int slot) { return (int)((gen & 0x7fffu) << 16) | (dev << 8) | slot; }
+static inline TicketId ticket_parts(int id) { return {id >> 16, (id >> 8) & 255, id & 255}; }
+
+// the state a busy ticket stands for: the key its draw began with, or what the solo kernel wrote (waits for that launch)
+static hipError_t read_ticket_state(Ticket& tk, uint32_t* key, int* pos) {
+    const hipError_t e = tk.computed ? hipEventSynchronize(tk.done) : hipSuccess;
+    if (e != hipSuccess) return e;
+    std::memcpy(key, tk.computed ? tk.pinned : tk.key, sizeof(uint32_t) * kN);
+    *pos = tk.pos;
     return hipSuccess;
 }
 
@@ -648,12 +668,10 @@ static bool make_plan(int pos, unsigned long long total, unsigned long long skip
         // segment length 128 * step blocks, by a cost model of the two launches that matter (measured, MI355X): the jump runs 4
         // workgroups per state, 768 at a time, ~70 us a round; a segment's workgroup generates a block in ~0.5 us
         double best = 1e30;
-        for (int c = 1; c <= SSN_MT_MAX_STEP; c *= 2) {
+        for (int c = 1; c <= kMaxStep; c *= 2) {
             const long len = (long)c << kStride0Log2;
             const long nseg = (pl.b_hi - pl.b_lo + len) / len;
-            const double rounds = SSN_MT_FRACTIONAL_ROUNDS ? (4.0 * (double)nseg / 768.0 < 1.0 ? 1.0 : 4.0 * (double)nseg / 768.0)
-                                                           : (double)((4 * nseg + 767) / 768);
-            const double cost = 70.0 * rounds + 0.5 * (double)len;
+            const double cost = 70.0 * (double)((4 * nseg + 767) / 768) + 0.5 * (double)len;
             if (cost < best) { best = cost; pl.step = c; }
         }
         const long seg_blocks = (long)pl.step << kStride0Log2;
@@ -664,6 +682,134 @@ static bool make_plan(int pos, unsigned long long total, unsigned long long skip
 }
 // workgroups per share of a round with `count` states: enough to put a workgroup on most CUs when the states are few
 static inline int sub_for(long count) { return count * kShares * 4 <= 512 ? 4 : (count * kShares * 2 <= 512 ? 2 : 1); }
+
+// The state after the draw, on the side stream (block b_f - 1 by the exact polynomial, then one regeneration; a draw that stays
+// in the caller's current block leaves the key as it is), under the next ticket of the ring.  The slot is marked and *ticket
+// written LAST, when all is queued: after a failure the slot is free and *ticket as the caller left it.  (Caller holds chain_mu.)
+static hipError_t queue_state_after(DeviceTables* t, const uint32_t* key, const Plan& pl, int* ticket) {
+    const int slot = (int)(t->next_ticket++ % DeviceTables::kTickets);
+    Ticket& tk = t->tickets[slot];
+    hipError_t e;
+    // a slot still marked busy after the ring has come round: its owner has not asked for the state yet (a generator that sat
+    // idle while others drew, or one that was dropped).  The state is fetched now (its launch is long over) and parked.
+    if (tk.busy) {
+        DeviceTables::Parked pk;
+        if ((e = read_ticket_state(tk, pk.key, &pk.pos)) != hipSuccess) return e;
+        if (t->parked.size() >= 4096) t->parked.erase(t->parked.begin());       // (dropped generators: do not grow for ever)
+        t->parked[ticket_id(tk.gen, t->dev, slot)] = pk;
+        tk.busy = false;
+    }
+    const bool computed = pl.b_f >= 1;
+    if (computed) {
+        CodeTable ex;
+        if ((e = exact_poly(t, pl.b_f - 1, &ex)) != hipSuccess) return e;
+        SoloArgs sa{{}, ex.codes, ex.counts, t->chain, (unsigned*)(t->chain + (size_t)kSoloParts * kN), tk.pinned};
+        std::memcpy(sa.root.w, key, sizeof sa.root.w);
+        hipLaunchKernelGGL(mt_solo_kernel, dim3(1, kSoloParts), dim3(320), kJumpLds, t->side, sa);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipEventRecord(tk.done, t->side)) != hipSuccess) return e;
+    } else {
+        std::memcpy(tk.key, key, sizeof tk.key);
+    }
+    ++tk.gen;
+    tk.busy = true; tk.computed = computed;
+    tk.pos = (int)(pl.p_end - pl.b_f * kN);
+    *ticket = ticket_id(tk.gen, t->dev, slot);
+    return hipSuccess;
+}
+
+static hipError_t grow(uint32_t*& p, size_t& cap, size_t need) {
+    if (need <= cap) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    const hipError_t e = hipMalloc((void**)&p, need + need / 4);
+    if (e == hipSuccess) cap = need + need / 4;
+    return e;
+}
+// (growing is rare -- a larger draw than any before; kernels of an earlier draw may still read the set: waited for before any free)
+static hipError_t reserve_level(DeviceTables* t, BulkSet& bs, int l, size_t need_x, size_t need_s) {
+    if (need_x <= bs.xseq_cap[l] && need_s <= bs.states_cap[l]) return hipSuccess;
+    hipError_t e;
+    if (bs.used && (e = hipEventSynchronize(bs.consumed)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(t->side)) != hipSuccess) return e;
+    if ((e = grow(bs.xseq[l], bs.xseq_cap[l], need_x)) != hipSuccess) return e;
+    return grow(bs.states[l], bs.states_cap[l], need_s);
+}
+
+// The states of every level between the root and the segments, top down, on the side stream (behind the solo launch) into the
+// next set of the library's buffers; returns those the segments start from.  (Caller holds chain_mu.)
+struct SegStates { const uint32_t* states; long count; int parts; BulkSet* set; };
+static hipError_t queue_segment_states(DeviceTables* t, const uint32_t* key, const Plan& pl, int top, SegStates* out) {
+    BulkSet& bs = t->bulk[t->next_bulk++ % DeviceTables::kBulkSets];
+    hipError_t e;
+    if (bs.used && (e = hipStreamWaitEvent(t->side, bs.consumed, 0)) != hipSuccess) return e;
+    ExpandArgs xa;
+    std::memcpy(xa.root.w, key, sizeof xa.root.w);
+    SegStates s{nullptr, 1, 1, &bs};
+    for (int l = top; l >= kSegLevel; --l) {
+        const int sh = level_shift(l) - level_shift(kSegLevel);
+        // level 0: the segment starts (every step-th state); above: every state between the first and the last one's ancestors
+        const int lstep = l == kSegLevel ? pl.step : 1;
+        const long lo = (pl.s_lo * pl.step) >> sh, hi = (pl.s_hi * pl.step) >> sh, cnt = (hi - lo) / lstep + 1;
+        const int sub = sub_for(cnt);
+        if ((e = reserve_level(t, bs, l, sizeof(uint32_t) * (size_t)s.count * kXSeq, sizeof(uint32_t) * (size_t)cnt * kShares * sub * kN)) != hipSuccess)
+            return e;
+        xa.states = s.states; xa.nparts = s.parts; xa.xseq = bs.xseq[l];
+        hipLaunchKernelGGL(mt_expand_kernel, dim3((unsigned)s.count), dim3(256), kXSeq * sizeof(uint32_t), t->side, xa);
+        const JumpArgs ja{bs.xseq[l], lo >> kRadixLog2, bs.states[l], lo, lstep, sub, t->level[l].codes, t->level[l].counts};
+        hipLaunchKernelGGL(mt_jump_kernel, dim3((unsigned)cnt, kShares * sub), dim3(320), kJumpLds, t->side, ja);
+        s.states = bs.states[l]; s.count = cnt; s.parts = kShares * sub;
+    }
+    *out = s;
+    return hipGetLastError();
+}
+
+// mt_gen_kernel<T, ODD, BUILDW, TAIL> by its three switches (BUILDW and TAIL exist for float alone)
+template <typename T, bool BUILDW, bool TAIL>
+static auto gen_kernel_of(bool odd) { return odd ? mt_gen_kernel<T, true, BUILDW, TAIL> : mt_gen_kernel<T, false, BUILDW, TAIL>; }
+template <typename T>
+static auto gen_kernel(bool odd, bool buildw, bool tail) {
+    if constexpr (std::is_same<T, float>::value) {
+        if (buildw) return tail ? gen_kernel_of<T, true, true>(odd) : gen_kernel_of<T, true, false>(odd);
+        if (tail) return gen_kernel_of<T, false, true>(odd);
+    }
+    return gen_kernel_of<T, false, false>(odd);
+}
+
+// what mt19937_begin was asked for (tail: null unless a window of the tail is wanted)
+struct Draw { int pos; unsigned long long total, skip, count; void* out; float* W; const float* jds12; int N; const MtTail* tail; };
+
+// the numbers: the caller's stream waits for the segment states and runs the generation kernel, whose end frees the set of buffers
+template <typename T>
+static hipError_t launch_gen(DeviceTables* t, const Draw& d, const Plan& pl, const SegStates& ss, hipStream_t st) {
+    BulkSet& bs = *ss.set;
+    hipError_t e;
+    if ((e = hipEventRecord(bs.ready, t->side)) != hipSuccess) return e;
+    if ((e = hipStreamWaitEvent(st, bs.ready, 0)) != hipSuccess) return e;
+    GenArgs<T> ga{ss.states, ss.parts, pl.s_lo, pl.s_hi, pl.step << kStride0Log2, pl.b_hi, d.pos, (long)d.skip, (long)d.count, (T*)d.out};
+    if (d.tail) {
+        ga.tail_q0 = (long)d.total; ga.tail_skip = (long)d.tail->skip; ga.tail_count = (long)d.tail->count;
+        ga.tail_kind = d.tail->kind; ga.tail_out = d.tail->out;
+    }
+    size_t glds = 0;
+    if constexpr (std::is_same<T, float>::value) {
+        if (d.W) {
+            ga.W = d.W; ga.N = d.N;
+            ga.magic_m = ((1ull << 40) + 2ull * d.N - 1) / (2ull * d.N);
+            for (int q = 0; q < 4; ++q) {
+                ga.p.J[q] = d.jds12[q]; ga.p.D[q] = d.jds12[4 + q];
+                ga.p.inv2s2[q] = 1.f / (2.f * d.jds12[8 + q] * d.jds12[8 + q]);
+            }
+            glds = sizeof(float) * 4 * (size_t)d.N;
+        }
+    }
+    hipLaunchKernelGGL(gen_kernel<T>(d.pos & 1, d.W != nullptr, d.tail != nullptr), dim3((unsigned)(pl.s_hi - pl.s_lo + 1)),
+                       dim3(d.W ? 576 : 256), glds, st, ga);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    e = hipEventRecord(bs.consumed, st);
+    bs.used = true;
+    return e;
+}
 
 }  // namespace mt
 
@@ -692,28 +838,22 @@ bool mt19937_plan(int pos, unsigned long long total, unsigned long long skip, un
 // The state after a draw begun with mt19937_begin: waits for that draw's one launch on the library's stream, nothing else.
 hipError_t mt19937_finish(int ticket, uint32_t* key, int* pos) {
     using namespace mt;
-    const int dev = (ticket >> 8) & 255, slot = ticket & 255;
-    if (ticket < 0 || dev >= 64 || slot >= DeviceTables::kTickets || !g_dev[dev]) return hipErrorInvalidValue;
-    std::lock_guard<std::mutex> lock(g_dev[dev]->chain_mu);
-    DeviceTables::Ticket& tk = g_dev[dev]->tickets[slot];
-    if (!tk.busy || (int)(tk.gen & 0x7fffu) != (ticket >> 16)) {
-        auto it = g_dev[dev]->parked.find(ticket);           // its slot was taken over: the state was fetched then
-        if (it == g_dev[dev]->parked.end()) return hipErrorInvalidValue;      // (finished before, or never begun)
+    const TicketId id = ticket_parts(ticket);
+    if (ticket < 0 || id.dev >= 64 || id.slot >= DeviceTables::kTickets || !g_dev[id.dev]) return hipErrorInvalidValue;
+    DeviceTables* t = g_dev[id.dev];
+    std::lock_guard<std::mutex> lock(t->chain_mu);
+    Ticket& tk = t->tickets[id.slot];
+    if (!tk.busy || (int)(tk.gen & 0x7fffu) != id.gen) {
+        auto it = t->parked.find(ticket);           // its slot was taken over: the state was fetched then
+        if (it == t->parked.end()) return hipErrorInvalidValue;      // (finished before, or never begun)
         std::memcpy(key, it->second.key, sizeof(uint32_t) * kN);
         *pos = it->second.pos;
-        g_dev[dev]->parked.erase(it);
+        t->parked.erase(it);
         return hipSuccess;
     }
-    if (tk.computed) {
-        const hipError_t e = hipEventSynchronize(tk.done);
-        if (e != hipSuccess) return e;
-        std::memcpy(key, tk.pinned, sizeof(uint32_t) * kN);
-    } else {
-        std::memcpy(key, tk.key, sizeof(uint32_t) * kN);
-    }
-    *pos = tk.pos;
-    tk.busy = false;
-    return hipSuccess;
+    const hipError_t e = read_ticket_state(tk, key, pos);
+    if (e == hipSuccess) tk.busy = false;
+    return e;
 }
 
 // The draw.  key / pos: numpy's RandomState state (host).  The next `total` doubles of the stream are consumed; doubles
@@ -742,150 +882,22 @@ hipError_t mt19937_begin(const uint32_t* key, int pos, unsigned long long total,
     }
     Plan pl;
     if (!make_plan(pos, total, skip, count, pl, tail)) return hipErrorInvalidValue;
-    const long p_end = pl.p_end, b_f = pl.b_f, b_hi = pl.b_hi, s_lo = pl.s_lo, s_hi = pl.s_hi;
-    const int step = pl.step;
     // levels needed: the top digit of the last segment must be <= kDigits
     const bool any = count || want_tail;
-    int top_b = any ? kSegLevel : -1;
+    int top = any ? kSegLevel : -1;
     if (any)
-        while (((s_hi * step) >> (level_shift(top_b) - level_shift(kSegLevel))) > kDigits) if (++top_b >= kLevels) return hipErrorInvalidValue;
+        while (((pl.s_hi * pl.step) >> (level_shift(top) - level_shift(kSegLevel))) > kDigits) if (++top >= kLevels) return hipErrorInvalidValue;
     DeviceTables* t = nullptr;
-    hipError_t e = device_tables(top_b, &t);
+    hipError_t e = device_tables(top, &t);
     if (e != hipSuccess) return e;
-
-    ExpandArgs xa;
-    std::memcpy(xa.root.w, key, sizeof xa.root.w);
-    const size_t xlds = kXSeq * sizeof(uint32_t);
-    JumpArgs ja;
-
-    // (1) the state after the draw, on the side stream: block b_f - 1 by the exact polynomial, then one regeneration
-    std::unique_lock<std::mutex> chain_lock(t->chain_mu);
-    if (ticket) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const int slot = (int)(t->next_ticket++ % DeviceTables::kTickets);
-        DeviceTables::Ticket& tk = t->tickets[slot];
-        // a slot still marked busy after the ring has come round: its owner has not asked for the state yet (a generator that sat
-        // idle while others drew, or one that was dropped).  The state is fetched now (its launch is long over) and parked.
-        if (tk.busy) {
-            DeviceTables::Parked pk;
-            pk.pos = tk.pos;
-            if (tk.computed) {
-                if ((e = hipEventSynchronize(tk.done)) != hipSuccess) return e;
-                std::memcpy(pk.key, tk.pinned, sizeof pk.key);
-            } else {
-                std::memcpy(pk.key, tk.key, sizeof pk.key);
-            }
-            if (t->parked.size() >= 4096) t->parked.erase(t->parked.begin());       // (dropped generators: do not grow for ever)
-            t->parked[(int)((tk.gen & 0x7fffu) << 16) | (dev << 8) | slot] = pk;
-            tk.busy = false;
-        }
-        ++tk.gen;
-        tk.busy = true; tk.computed = b_f >= 1;
-        tk.pos = b_f >= 1 ? (int)(p_end - b_f * kN) : (int)p_end;
-        if (b_f < 1) std::memcpy(tk.key, key, sizeof tk.key);
-        *ticket = (int)((tk.gen & 0x7fffu) << 16) | (dev << 8) | slot;
-        if (b_f >= 1) {
-            DeviceTables::Exact ex{};
-            if ((e = exact_poly(t, b_f - 1, &ex)) != hipSuccess) return e;
-            SoloArgs sa;
-            std::memcpy(sa.root.w, key, sizeof sa.root.w);
-            sa.codes = ex.codes; sa.counts = ex.counts;
-            sa.partials = t->chain; sa.counter = (unsigned*)(t->chain + (size_t)kSoloParts * kN); sa.out = tk.pinned;
-            hipLaunchKernelGGL(mt_solo_kernel, dim3(1, kSoloParts), dim3(320), kJumpLds, t->side, sa);
-            if ((e = hipGetLastError()) != hipSuccess) { tk.busy = false; return e; }
-            if ((e = hipEventRecord(tk.done, t->side)) != hipSuccess) { tk.busy = false; return e; }
-        }
-    }
-
-    // (2) the wanted doubles: the states of every level between the root and the segments, top down, on the side stream (behind
-    // the launch above) into a set of the library's buffers; then, on the caller's stream, the generation kernel
-    if (any) {
-        DeviceTables::BulkSet& bs = t->bulk[t->next_bulk++ % DeviceTables::kBulkSets];
-        if (!bs.ready) {
-            if ((e = hipEventCreateWithFlags(&bs.ready, hipEventDisableTiming)) != hipSuccess) return e;
-            if ((e = hipEventCreateWithFlags(&bs.consumed, hipEventDisableTiming)) != hipSuccess) return e;
-        }
-        if (bs.used && (e = hipStreamWaitEvent(t->side, bs.consumed, 0)) != hipSuccess) return e;
-        const uint32_t* parent = nullptr; long parent_cnt = 1; int parent_parts = 1;
-        for (int l = top_b; l >= kSegLevel && e == hipSuccess; --l) {
-            const int sh = level_shift(l) - level_shift(kSegLevel);
-            // level 0: the segment starts (every step-th state); above: every state between the first and the last one's ancestors
-            const int lstep = l == kSegLevel ? step : 1;
-            const long lo = (s_lo * step) >> sh, hi = (s_hi * step) >> sh, cnt = (hi - lo) / lstep + 1;
-            const int sub = sub_for(cnt);
-            const size_t need_x = sizeof(uint32_t) * (size_t)parent_cnt * kXSeq, need_s = sizeof(uint32_t) * (size_t)cnt * kShares * sub * kN;
-            if (need_x > bs.xseq_cap[l] || need_s > bs.states_cap[l]) {
-                // (grow: rare -- a larger draw than any before.  The set may still be read by the kernels of an earlier draw)
-                if (bs.used && (e = hipEventSynchronize(bs.consumed)) != hipSuccess) break;
-                if ((e = hipStreamSynchronize(t->side)) != hipSuccess) break;
-                if (need_x > bs.xseq_cap[l]) {
-                    if (bs.xseq[l]) (void)hipFree(bs.xseq[l]);
-                    bs.xseq[l] = nullptr; bs.xseq_cap[l] = 0;
-                    if ((e = hipMalloc((void**)&bs.xseq[l], need_x + need_x / 4)) != hipSuccess) break;
-                    bs.xseq_cap[l] = need_x + need_x / 4;
-                }
-                if (need_s > bs.states_cap[l]) {
-                    if (bs.states[l]) (void)hipFree(bs.states[l]);
-                    bs.states[l] = nullptr; bs.states_cap[l] = 0;
-                    if ((e = hipMalloc((void**)&bs.states[l], need_s + need_s / 4)) != hipSuccess) break;
-                    bs.states_cap[l] = need_s + need_s / 4;
-                }
-            }
-            xa.states = parent; xa.nparts = parent_parts; xa.xseq = bs.xseq[l];
-            hipLaunchKernelGGL(mt_expand_kernel, dim3((unsigned)parent_cnt), dim3(256), xlds, t->side, xa);
-            ja.xseq = bs.xseq[l]; ja.parent_lo = lo >> kRadixLog2;
-            ja.dst = bs.states[l]; ja.lo = lo; ja.step = lstep; ja.sub = sub;
-            ja.codes = t->codes[l]; ja.counts = t->counts[l];
-            hipLaunchKernelGGL(mt_jump_kernel, dim3((unsigned)cnt, kShares * sub), dim3(320), kJumpLds, t->side, ja);
-            parent = bs.states[l]; parent_cnt = cnt; parent_parts = kShares * sub;
-        }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(bs.ready, t->side);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, bs.ready, 0);
-        if (e == hipSuccess) {
-            const unsigned nseg = (unsigned)(s_hi - s_lo + 1);
-            const bool odd = pos & 1;
-            if (elem == 4) {
-                GenArgs<float> ga{parent, parent_parts, s_lo, s_hi, step << kStride0Log2, b_hi, pos, (long)skip, (long)count, (float*)out};
-                if (want_tail) {
-                    ga.tail_q0 = (long)total; ga.tail_skip = (long)tail->skip; ga.tail_count = (long)tail->count;
-                    ga.tail_kind = tail->kind; ga.tail_out = tail->out;
-                }
-                size_t glds = 0;
-                if (W) {
-                    ga.W = W; ga.N = N;
-                    ga.magic_m = ((1ull << 40) + 2ull * N - 1) / (2ull * N);
-                    for (int q = 0; q < 4; ++q) {
-                        ga.p.J[q] = jds12[q]; ga.p.D[q] = jds12[4 + q];
-                        ga.p.inv2s2[q] = 1.f / (2.f * jds12[8 + q] * jds12[8 + q]);
-                    }
-                    glds = sizeof(float) * 4 * (size_t)N;
-                }
-                // <float, ODD, BUILDW, TAIL>
-                const int form = (odd ? 4 : 0) | (W ? 2 : 0) | (want_tail ? 1 : 0);
-                const dim3 grid(nseg), blk(W ? 576 : 256);
-                switch (form) {
-                    case 0: hipLaunchKernelGGL((mt_gen_kernel<float, false, false, false>), grid, blk, glds, st, ga); break;
-                    case 1: hipLaunchKernelGGL((mt_gen_kernel<float, false, false, true>), grid, blk, glds, st, ga); break;
-                    case 2: hipLaunchKernelGGL((mt_gen_kernel<float, false, true, false>), grid, blk, glds, st, ga); break;
-                    case 3: hipLaunchKernelGGL((mt_gen_kernel<float, false, true, true>), grid, blk, glds, st, ga); break;
-                    case 4: hipLaunchKernelGGL((mt_gen_kernel<float, true, false, false>), grid, blk, glds, st, ga); break;
-                    case 5: hipLaunchKernelGGL((mt_gen_kernel<float, true, false, true>), grid, blk, glds, st, ga); break;
-                    case 6: hipLaunchKernelGGL((mt_gen_kernel<float, true, true, false>), grid, blk, glds, st, ga); break;
-                    default: hipLaunchKernelGGL((mt_gen_kernel<float, true, true, true>), grid, blk, glds, st, ga); break;
-                }
-            } else {
-                GenArgs<double> ga{parent, parent_parts, s_lo, s_hi, step << kStride0Log2, b_hi, pos, (long)skip, (long)count, (double*)out};
-                if (odd) hipLaunchKernelGGL((mt_gen_kernel<double, true, false, false>), dim3(nseg), dim3(256), 0, st, ga);
-                else hipLaunchKernelGGL((mt_gen_kernel<double, false, false, false>), dim3(nseg), dim3(256), 0, st, ga);
-            }
-            e = hipGetLastError();
-            if (e == hipSuccess) { e = hipEventRecord(bs.consumed, st); bs.used = true; }
-        }
-    }
-
-    return e;
+    // the side stream's work first (the state after the draw, then the segment states), the caller's stream last
+    std::lock_guard<std::mutex> chain_lock(t->chain_mu);
+    if (ticket && (e = queue_state_after(t, key, pl, ticket)) != hipSuccess) return e;
+    if (!any) return hipSuccess;
+    SegStates ss{};
+    if ((e = queue_segment_states(t, key, pl, top, &ss)) != hipSuccess) return e;
+    const Draw d{pos, total, skip, count, out, W, jds12, N, want_tail ? tail : nullptr};
+    return elem == 4 ? launch_gen<float>(t, d, pl, ss, st) : launch_gen<double>(t, d, pl, ss, st);
 }
 
 // begin + finish: returns when the state after the draw is known
