@@ -754,6 +754,29 @@ int ssn_tc_features_f32(const float *tc, float *feat, long rows, int NC, int NB,
 int ssn_ks_columns_f32(const float *x, const float *truth_sorted, const int *m, int S, int B, int C, int T, int *n,
                        long long *num, void *stream);
 
+/* ---- Wasserstein distances of the scored checkpoints (analyzers/distdiff.py, wasserstein=True; csrc/ssn_wdist.hip) ----
+ * The first Wasserstein distance of two samples on the line is the integral of |F_x - F_t|; with the counts the KS kernel
+ * already has it is a sum over the pooled points, kept -- like num -- before the division by n m.
+ * ssn_ks_w1_columns_f32: the arguments, the refusals and n, num of ssn_ks_columns_f32 (the same integers), and
+ *   wnum[s][c] = sum_{k < K} gap_k w_k over the distinct finite values p_0 < p_1 < ... < p_K of the pooled sample (a value that
+ *   occurs several times, in one sample or in both, is one point):
+ *     gap_k = (double) p_{k+1} - (double) p_k,   w_k = (double) |#{x <= p_k} m - #{t <= p_k} n|   (an integer, 64-bit arithmetic)
+ *   so that W1 = wnum / (n m), in the unit of x; n = 0 or m = 0 gives wnum = 0.  Every product is rounded once to fp64; the sum
+ *   is in fp64 in an order the launch geometry fixes (per thread in index order, lanes 32, 16, ... 1 apart, the four waves in
+ *   order), without atomics: two calls give the same bits.  All terms are non-negative, a product and a partial sum carry one
+ *   rounding each and there are at most n + m terms: |wnum - exact| <= (n + m + 2) 2^-52 exact.  Where every gap, product and
+ *   partial sum is representable (values on a lattice) wnum is exact.
+ * ssn_project_rows_f32: out[r][l] = (float) acc with acc = 0 and, for c = 0 .. C - 1 in this order,
+ *   acc = fma((double) x[r ldx + c], (double) theta[l C + c], acc): the products of two floats are exact in fp64, so this is the
+ *   sequential fp64 sum of exact products, rounded to float at the end.  x: device [rows][ldx] of which the first C of a row
+ *   are read (ldx >= C), theta: device [L][C], out: device [rows][L].  A non-finite x makes every projection of its row
+ *   non-finite.  L <= SSN_W1_MAX_DIRECTIONS; more, a negative size, ldx < C or a null pointer is refused; rows == 0 or L == 0
+ *   is success. */
+#define SSN_W1_MAX_DIRECTIONS 4096
+int ssn_ks_w1_columns_f32(const float *x, const float *truth_sorted, const int *m, int S, int B, int C, int T, int *n,
+                          long long *num, double *wnum, void *stream);
+int ssn_project_rows_f32(const float *x, long rows, int ldx, int C, const float *theta, int L, float *out, void *stream);
+
 /* ---- Rejection sampling of fixed points on the device (ssnode.sample_tuning_curves_table; csrc/ssn_fpsample.hip) ----
  * A parameter sets see the same stream of candidate draws; every (set, candidate) pair is solved for NB stimuli by
  * ssn_solve_batch_* (the A R pairs as its batch, set-major), and the first NZ candidates of a set, in stream order, whose solves

@@ -29,10 +29,23 @@ on the device), with the truth's solver options.  A checkpoint that rejects draw
 count -- and the counts of rejected draws per error code are part of the result (``rejections.csv``): the rejection rate is
 the diagnostic for a generator that has left the stable regime.
 
+``wasserstein=True`` (``--wasserstein``) adds the distance the training loop minimises, in the unit of the column (Hz for a raw
+column), where KS saturates at 1 for every sample that lies on one side of the truth's.  The KS launch is replaced by one
+``ssn_ks_w1_columns_f32`` launch over the same columns: the same integers ``num`` and ``n``, and beside them
+``wnum = sum_k (p_{k+1} - p_k) |#{x <= p_k} m - #{t <= p_k} n|`` over the distinct pooled values ``p_0 < ... < p_K`` in fp64, so
+that ``W1 = wnum / (n m)`` -- ``scipy.stats.wasserstein_distance``.  The sliced distance ``SW1`` of a checkpoint is the mean over
+`directions` unit vectors (`slice_directions`: seeded, shared by all checkpoints and by the truth) of the W1 between the
+projections of the generated rows and of the truth's rows onto the vector: the raw columns of a chunk are projected by
+``ssn_project_rows_f32`` (a sequential fp64 sum per (row, direction), rounded to float32) and a second
+``ssn_ks_w1_columns_f32`` launch treats the directions as columns.  A row that is not finite drops out of every direction.
+The command line then writes ``wdist.csv`` (gen_step, stat, W1, n, m; one ``sliced_w1`` row per checkpoint) and ``wdist.json``;
+``distdiff.csv`` and ``distdiff.json`` are what they are without the option.
+
     ./run tc_gan.analyzers.distdiff -- RUNDIR [--steps ::10] [--draws 30] [--seed 0] [--gen-kernel K]
                                        [--max-draws-per-launch D] [--output DIR] [--save-tuning-curves]
                                        [--dynamics {fixed-time,fixed-point}] [--max-candidates N]
                                        [--solver-dtype {float64,float32}]
+                                       [--wasserstein] [--directions 128] [--direction-seed 0]
 """
 import ctypes
 import json
@@ -54,6 +67,10 @@ FIXED_POINT_SOLVER_OPTIONS = SSNODE_TRUTH_OPTIONS
 FIXED_POINT_OPTION_KEYS = ('io_type', 'k', 'n', 'smoothness', 'dt', 'max_iter', 'atol', 'tau', 'rate_stop_at', 'rate_soft_bound',
                            'rate_hard_bound', 'solver')
 #: the command-line arguments distdiff.json records in the fixed-time mode: the file keeps the keys it always had
+#: the command-line arguments of the Wasserstein distances: wdist.json records them, distdiff.json never does
+_WASSERSTEIN_ARGUMENTS = ('wasserstein', 'directions', 'direction_seed')
+DEFAULT_DIRECTIONS = 128
+SLICED_STAT = 'sliced_w1'
 _FIXED_TIME_ARGUMENTS = ('rundir', 'steps', 'draws', 'seed', 'gen_kernel', 'max_draws_per_launch', 'output', 'save_tuning_curves')
 _SAMPLER_KEYS = ('num_sites', 'bandwidths', 'contrasts', 'smoothness', 'k', 'n', 'tau_E', 'tau_I', 'dt', 'io_type', 'seqlen',
                  'skip_steps')
@@ -136,6 +153,47 @@ def write_long_table(path, result):
     """`long_table` as CSV.  KSD is written with the digits that give the double back (``pandas.read_csv(path,
     float_precision='round_trip')``; pandas' default parser may be one ulp off -- n and m are exact either way)."""
     long_table(result).to_csv(path, index=False)
+
+
+def slice_directions(directions, columns, seed=0):
+    """The directions of the sliced distance, float32 (directions, columns): the rows of
+    ``numpy.random.RandomState(seed).randn(directions, columns)``, each divided by its float64 norm, then rounded to float32."""
+    directions, columns = int(directions), int(columns)
+    if directions < 1:
+        raise ValueError('directions must be at least 1, got {}'.format(directions))
+    if directions > clib.W1_MAX_DIRECTIONS:
+        raise ValueError('directions = {} is more than the {} the projection kernel takes'.format(directions, clib.W1_MAX_DIRECTIONS))
+    if columns < 1:
+        raise ValueError('directions need at least one column, got {}'.format(columns))
+    g = np.random.RandomState(seed).randn(directions, columns)
+    return np.ascontiguousarray(g / np.sqrt((g * g).sum(axis=1, keepdims=True)), dtype='float32')
+
+
+def w1_from_sums(wnum, n, m):
+    """W1 = wnum / (n m); NaN where a side has no finite value."""
+    wnum, n, m = np.asarray(wnum, dtype='float64'), np.asarray(n, dtype='float64'), np.asarray(m, dtype='float64')
+    den = n * m
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(den > 0, wnum / np.where(den > 0, den, 1.0), np.nan)
+
+
+def wdist_table(result):
+    """The long-format table of the Wasserstein distances of a result: per checkpoint one row per statistic of ``stat`` and one
+    `SLICED_STAT` row -- gen_step, stat, W1, n, m."""
+    import pandas
+    S, C = result['wnum'].shape
+    sl = result['sliced']
+    stat = np.asarray(list(result['stat']) + [SLICED_STAT], dtype=object)
+    return pandas.DataFrame(dict(
+        gen_step=np.repeat(np.asarray(result['gen_step']), C + 1), stat=np.tile(stat, S),
+        W1=np.concatenate([result['W1'], np.asarray(result['SW1'])[:, None]], axis=1).reshape(-1),
+        n=np.concatenate([result['n'], np.asarray(sl['n'])[:, None]], axis=1).reshape(-1),
+        m=np.tile(np.concatenate([result['m'], [sl['m']]]), S)), columns=['gen_step', 'stat', 'W1', 'n', 'm'])
+
+
+def write_wdist_table(path, result):
+    """`wdist_table` as CSV, W1 with the digits that give the double back (see `write_long_table`)."""
+    wdist_table(result).to_csv(path, index=False)
 
 
 def _shape_of(cfg):
@@ -275,7 +333,14 @@ def _truth_on_device(truth32, shape):
     nc, nb, ct, npr = shape[:4]
     T = truth32.shape[0]
     t = torch.as_tensor(truth32).to('cuda')
-    allcols = torch.cat([t, _features(t, nc, nb, ct * npr)], dim=1)
+    return _sorted_columns(torch.cat([t, _features(t, nc, nb, ct * npr)], dim=1))
+
+
+def _sorted_columns(allcols):
+    """The columns of a device (T, C') array as the KS kernels take a truth: (float32 [C'][T] ascending with the finite values
+    first, device int32 [C'] of their counts, the counts as host int64)."""
+    import torch
+    T = allcols.shape[0]
     finite = torch.isfinite(allcols)
     srt = torch.sort(torch.where(finite, allcols, torch.full_like(allcols, float('inf'))), dim=0).values
     m = finite.sum(dim=0).to(torch.int32).contiguous()
@@ -291,11 +356,82 @@ def _features(tc, nc, nb, q):
     return feat
 
 
+def project_rows(x, theta, columns=None):
+    """Device float32 (rows, L): the first `columns` (default: all) values of every row of the device float32 matrix x (rows, ldx)
+    projected on the rows of theta (L, columns) by ``ssn_project_rows_f32``."""
+    import torch
+    rows, ldx = x.shape
+    C = ldx if columns is None else int(columns)
+    L = theta.shape[0]
+    if theta.shape[1] != C or not x.is_contiguous() or not theta.is_contiguous():
+        raise ValueError('project_rows: x (rows, ldx >= {0}) and theta (L, {0}) must be contiguous, got {1} and {2}'
+                         .format(C, tuple(x.shape), tuple(theta.shape)))
+    out = torch.empty((rows, L), device=x.device, dtype=torch.float32)
+    clib.check(libssnode.ssn_project_rows_f32(x.data_ptr(), rows, ldx, C, theta.data_ptr(), L, out.data_ptr(), clib.stream_ptr()),
+               'ssn_project_rows_f32')
+    return out
+
+
+def _sliced_on_device(truth32, directions, direction_seed):
+    """What a Wasserstein score carries from chunk to chunk: the directions on the device and the truth's projections, sorted per
+    direction as `_truth_on_device` sorts the truth's columns."""
+    import torch
+    theta = torch.as_tensor(slice_directions(directions, truth32.shape[1], direction_seed)).to('cuda')
+    tsorted, m_dev, m_host = _sorted_columns(project_rows(torch.as_tensor(truth32).to('cuda'), theta))
+    return dict(theta=theta, tsorted=tsorted, m_dev=m_dev, m_host=m_host, L=theta.shape[0], C=truth32.shape[1])
+
+
+def _reduce_columns(x, S, draws, truth, sliced=None):
+    """The statistics of x, device float32 (S draws, C'), against truth = (sorted columns, counts, T): (num, n) as host int64
+    (S, C') from one ``ssn_ks_columns_f32`` launch and one copy to the host.  With `sliced` (`_sliced_on_device`) the launch is
+    ``ssn_ks_w1_columns_f32`` instead, the raw columns are projected and the projections go through a second such launch:
+    (num, n, wnum, n of the projections, wnum of the projections, the projections on the device), still one copy."""
+    import torch
+    tsorted, m_dev, T = truth
+    Ct = x.shape[1]
+    out_n = torch.empty((S, Ct), device='cuda', dtype=torch.int32)
+    out_num = torch.empty((S, Ct), device='cuda', dtype=torch.int64)
+    if sliced is None:
+        clib.check(libssnode.ssn_ks_columns_f32(x.data_ptr(), tsorted.data_ptr(), m_dev.data_ptr(), S, draws, Ct, T,
+                                                out_n.data_ptr(), out_num.data_ptr(), clib.stream_ptr()), 'ssn_ks_columns_f32')
+        got = torch.stack([out_num, out_n.to(torch.int64)]).cpu().numpy() if S else np.zeros((2, 0, Ct), dtype='int64')
+        return got[0], got[1]
+    L = sliced['L']
+    out_w = torch.empty((S, Ct), device='cuda', dtype=torch.float64)
+    clib.check(libssnode.ssn_ks_w1_columns_f32(x.data_ptr(), tsorted.data_ptr(), m_dev.data_ptr(), S, draws, Ct, T, out_n.data_ptr(),
+                                               out_num.data_ptr(), out_w.data_ptr(), clib.stream_ptr()), 'ssn_ks_w1_columns_f32')
+    proj = project_rows(x, sliced['theta'], sliced['C'])
+    p_n = torch.empty((S, L), device='cuda', dtype=torch.int32)
+    p_num = torch.empty((S, L), device='cuda', dtype=torch.int64)
+    p_w = torch.empty((S, L), device='cuda', dtype=torch.float64)
+    clib.check(libssnode.ssn_ks_w1_columns_f32(proj.data_ptr(), sliced['tsorted'].data_ptr(), sliced['m_dev'].data_ptr(), S, draws, L,
+                                               sliced['tsorted'].shape[1], p_n.data_ptr(), p_num.data_ptr(), p_w.data_ptr(),
+                                               clib.stream_ptr()), 'ssn_ks_w1_columns_f32')
+    # (the doubles travel as their bits: one copy for everything)
+    got = torch.cat([out_num.reshape(-1), out_n.to(torch.int64).reshape(-1), out_w.view(torch.int64).reshape(-1),
+                     p_n.to(torch.int64).reshape(-1), p_w.view(torch.int64).reshape(-1)]).cpu().numpy()
+    a, b = S * Ct, S * L
+    return (got[:a].reshape(S, Ct), got[a:2 * a].reshape(S, Ct), got[2 * a:3 * a].view('float64').reshape(S, Ct),
+            got[3 * a:3 * a + b].reshape(S, L), got[3 * a + b:].view('float64').reshape(S, L), proj)
+
+
+def _wasserstein_keys(result, wnum, p_n, p_w, sliced, directions, direction_seed):
+    """The result keys of wasserstein=True from the sums of all chunks."""
+    result['wnum'] = wnum
+    result['W1'] = w1_from_sums(wnum, result['n'], result['m'][None, :])
+    per_direction = w1_from_sums(p_w, p_n, sliced['m_host'][None, :])
+    result['SW1'] = per_direction.mean(axis=1) if per_direction.shape[0] else np.zeros(0)
+    # (a row is finite in every direction or in none, and the truth is finite: one count per checkpoint, one for the truth)
+    result['sliced'] = dict(directions=int(directions), seed=direction_seed, n=p_n[:, 0].copy(), m=int(sliced['m_host'][0]))
+
+
 def _score_fixed_points(sampler_config, thetas, truth, draws, seed, max_draws_per_launch, return_samples, solver_options,
-                        max_candidates, solver_dtype):
+                        max_candidates, solver_dtype, wasserstein=False, directions=DEFAULT_DIRECTIONS, direction_seed=0):
     """`score_parameter_sets` with dynamics='fixed-point'."""
     _check_dynamics('fixed-point', sampler_config, solver_dtype)
     cfg, shape, truth32 = _check_config(dict(sampler_config, dtype='float32'), draws, truth)
+    if wasserstein:
+        slice_directions(directions, truth32.shape[1], direction_seed)   # (refuses before the device is touched)
     nc, nb, ct, npr, probes = shape
     draws = int(draws)
     N = int(cfg['num_sites'])
@@ -321,11 +457,8 @@ def _score_fixed_points(sampler_config, thetas, truth, draws, seed, max_draws_pe
     # (a row that was not accepted is NaN in every raw column; the feature kernel gives such a curve a finite prefbw)
     feat = torch.where(torch.isnan(tc[:, :1]), torch.full_like(feat, float('nan')), feat)
     x = torch.cat([tc, feat], dim=1).contiguous()
-    out_n = torch.empty((S, Ct), device='cuda', dtype=torch.int32)
-    out_num = torch.empty((S, Ct), device='cuda', dtype=torch.int64)
-    clib.check(libssnode.ssn_ks_columns_f32(x.data_ptr(), tsorted.data_ptr(), m_dev.data_ptr(), S, draws, Ct, truth32.shape[0],
-                                            out_n.data_ptr(), out_num.data_ptr(), clib.stream_ptr()), 'ssn_ks_columns_f32')
-    got = torch.stack([out_num, out_n.to(torch.int64)]).cpu().numpy() if S else np.zeros((2, 0, Ct), dtype='int64')
+    sliced = _sliced_on_device(truth32, directions, direction_seed) if wasserstein else None
+    got = _reduce_columns(x, S, draws, (tsorted, m_dev, truth32.shape[0]), sliced)
     num, n = got[0], got[1]
     result = dict(stat=stat, num=num, n=n, m=m_host, KSD=ksd_from_counts(num, n, m_host[None, :]), gen_kernel=None, chunk=chunk,
                   chunks=sizes, note=None, draws=draws, seed=seed, bandwidths=[float(b) for b in cfg['bandwidths']],
@@ -333,15 +466,20 @@ def _score_fixed_points(sampler_config, thetas, truth, draws, seed, max_draws_pe
                   accepted=tab.accepted, used=tab.used, rejections=tab.rejections, candidates=tab.candidates,
                   solver_variant=tab.variant, solver_options={k: (v if isinstance(v, (int, float, str)) else list(v))
                                                               for k, v in opts.items()}, solver_dtype=solver_dtype)
+    if wasserstein:
+        _wasserstein_keys(result, got[2], got[3], got[4], sliced, directions, direction_seed)
     if return_samples:
         xh = x.cpu().numpy().reshape(S, draws, Ct)
         result['tuning_curves'], result['features'] = xh[:, :, :C], xh[:, :, C:]
+        if wasserstein:
+            result['projections'] = got[5].cpu().numpy().reshape(S, draws, sliced['L'])
     return result
 
 
 def score_parameter_sets(sampler_config, thetas, truth, draws=DEFAULT_DRAWS, seed=0, gen_kernel=None,
                          max_draws_per_launch=DEFAULT_MAX_DRAWS_PER_LAUNCH, return_samples=False, dynamics='fixed-time',
-                         solver_options=None, max_candidates=None, solver_dtype='float64'):
+                         solver_options=None, max_candidates=None, solver_dtype='float64', wasserstein=False,
+                         directions=DEFAULT_DIRECTIONS, direction_seed=0):
     """KS statistics of `draws` tuning curves per parameter set against `truth`, all sets on the same noise.
 
     sampler_config: the fixed-time sampler -- num_sites, bandwidths, contrasts, smoothness, k, n, tau_E, tau_I, dt, io_type,
@@ -354,15 +492,22 @@ def score_parameter_sets(sampler_config, thetas, truth, draws=DEFAULT_DRAWS, see
       ``n`` is the accepted count.
     thetas: list of dicts J, D, S (2 x 2 or scalars) and V where the ssn_type has it.
     truth: (T, columns) array in the sampler's column order.
+    wasserstein: also the Wasserstein distances (both dynamics): wnum (S, C') float64, the weighted sums of
+      ``ssn_ks_w1_columns_f32`` that replaces the KS launch (num, n, KSD are the same arrays as without), W1 = wnum / (n m)
+      (NaN where n m = 0), SW1 (S,), the mean over `directions` directions (`slice_directions` with `direction_seed`) of the W1
+      of the projected raw columns, and sliced = dict(directions, seed, n (S,): finite rows per checkpoint, m); with
+      `return_samples` also projections (S, draws, directions).
 
     Returns a dict: stat (names, `stat_names`), num / n (S, C') and m (C',) integers, KSD (S, C'), gen_kernel (the kernel that
     ran), chunk, chunks, note; with `return_samples` also tuning_curves (S, draws, C) and features (S, draws, 4 curves)."""
     if dynamics != 'fixed-time':
         _check_dynamics(dynamics, sampler_config, solver_dtype)
         return _score_fixed_points(sampler_config, thetas, truth, draws, seed, max_draws_per_launch, return_samples,
-                                   solver_options, max_candidates, solver_dtype)
+                                   solver_options, max_candidates, solver_dtype, wasserstein, directions, direction_seed)
     kernel_name = gen_kernel or sampler_config.get('gen_kernel') or 'auto'
     cfg, shape, truth32 = _check_config(sampler_config, draws, truth)
+    if wasserstein:
+        slice_directions(directions, truth32.shape[1], direction_seed)   # (refuses before the device is touched)
     nc, nb, ct, npr, probes = shape
     draws = int(draws)
     chunk, sizes = plan_chunks(len(thetas), draws, max_draws_per_launch)
@@ -393,7 +538,10 @@ def score_parameter_sets(sampler_config, thetas, truth, draws=DEFAULT_DRAWS, see
     v_dev = to_device(vtab, torch.float32).contiguous() if vtab is not None else None
     S, Ct = len(thetas), len(stat)
     num, n = np.zeros((S, Ct), dtype='int64'), np.zeros((S, Ct), dtype='int64')
-    samples = ([], []) if return_samples else None
+    samples = ([], [], []) if return_samples else None
+    sliced = _sliced_on_device(truth32, directions, direction_seed) if wasserstein else None
+    if wasserstein:
+        wnum, p_n, p_w = np.zeros((S, Ct)), np.zeros((S, sliced['L']), dtype='int64'), np.zeros((S, sliced['L']))
     s0 = 0
     for ns in sizes:
         rows = ns * draws
@@ -410,23 +558,28 @@ def score_parameter_sets(sampler_config, thetas, truth, draws=DEFAULT_DRAWS, see
         ta = genops.gen_forward(W, ext, gp)['time_avg']
         tc = ta[:, :, pr].reshape(rows, C)                                  # ssn.py:846-848
         x = torch.cat([tc, _features(tc, nc, nb, Q)], dim=1)               # (ns draws, C + 4 curves)
-        out_n = torch.empty((ns, Ct), device='cuda', dtype=torch.int32)
-        out_num = torch.empty((ns, Ct), device='cuda', dtype=torch.int64)
-        clib.check(libssnode.ssn_ks_columns_f32(x.data_ptr(), tsorted.data_ptr(), m_dev.data_ptr(), ns, draws, Ct, T,
-                                                out_n.data_ptr(), out_num.data_ptr(), clib.stream_ptr()), 'ssn_ks_columns_f32')
-        got = torch.stack([out_num, out_n.to(torch.int64)]).cpu().numpy()  # the chunk's one copy to the host
+        got = _reduce_columns(x, ns, draws, (tsorted, m_dev, T), sliced)   # the chunk's one copy to the host
         num[s0:s0 + ns], n[s0:s0 + ns] = got[0], got[1]
+        if wasserstein:
+            wnum[s0:s0 + ns], p_n[s0:s0 + ns], p_w[s0:s0 + ns] = got[2], got[3], got[4]
         if return_samples:
             xh = x.cpu().numpy().reshape(ns, draws, Ct)
             samples[0].append(xh[:, :, :C])
             samples[1].append(xh[:, :, C:])
+            if wasserstein:
+                samples[2].append(got[5].cpu().numpy().reshape(ns, draws, sliced['L']))
         s0 += ns
     result = dict(stat=stat, num=num, n=n, m=m_host, KSD=ksd_from_counts(num, n, m_host[None, :]), gen_kernel=kernel, chunk=chunk,
                   chunks=sizes, note=note, draws=draws, seed=seed, bandwidths=[float(b) for b in cfg['bandwidths']],
                   contrasts=[float(c) for c in cfg['contrasts']], probes=probes, gen_step=np.arange(S))
+    if wasserstein:
+        _wasserstein_keys(result, wnum, p_n, p_w, sliced, directions, direction_seed)
     if return_samples:
         result['tuning_curves'] = np.concatenate(samples[0]) if samples[0] else np.zeros((0, draws, C), dtype='float32')
         result['features'] = np.concatenate(samples[1]) if samples[1] else np.zeros((0, draws, Ct - C), dtype='float32')
+        if wasserstein:
+            result['projections'] = (np.concatenate(samples[2]) if samples[2]
+                                     else np.zeros((0, draws, sliced['L']), dtype='float32'))
     return result
 
 
@@ -439,11 +592,13 @@ def _records(records_or_path):
 
 def calc_distdiff(records_or_path, steps=slice(None), draws=DEFAULT_DRAWS, seed=0, gen_kernel=None,
                   max_draws_per_launch=DEFAULT_MAX_DRAWS_PER_LAUNCH, return_samples=False, extra_thetas=(),
-                  dynamics='fixed-time', solver_options=None, max_candidates=None, solver_dtype='float64'):
+                  dynamics='fixed-time', solver_options=None, max_candidates=None, solver_dtype='float64', wasserstein=False,
+                  directions=DEFAULT_DIRECTIONS, direction_seed=0):
     """`score_parameter_sets` for the rows `steps` (a slice or a list of row positions) of a run's ``generator`` table, with the
     run's own sampler and ``truth.npy``.  `extra_thetas`: parameter sets scored in front of the rows (gen_step -1, -2, ...),
     e.g. the truth's own.  The result carries the rows' ``gen_step``.  `dynamics`, `solver_options`, `max_candidates`,
-    `solver_dtype`: see `score_parameter_sets` (the run's recorded ``true_ssn_options`` come before `solver_options`)."""
+    `solver_dtype`, `wasserstein`, `directions`, `direction_seed`: see `score_parameter_sets` (the run's recorded
+    ``true_ssn_options`` come before `solver_options`)."""
     rec = _records(records_or_path)
     try:
         table = rec.generator
@@ -456,7 +611,8 @@ def calc_distdiff(records_or_path, steps=slice(None), draws=DEFAULT_DRAWS, seed=
     gen_step = np.concatenate([-1 - np.arange(len(extra_thetas)), np.asarray(table['gen_step'], dtype='int64')[positions]]).astype('int64')
     result = score_parameter_sets(cfg, thetas, rec.truth, draws=draws, seed=seed, gen_kernel=gen_kernel,
                                   max_draws_per_launch=max_draws_per_launch, return_samples=return_samples, dynamics=dynamics,
-                                  solver_options=solver_options, max_candidates=max_candidates, solver_dtype=solver_dtype)
+                                  solver_options=solver_options, max_candidates=max_candidates, solver_dtype=solver_dtype,
+                                  wasserstein=wasserstein, directions=directions, direction_seed=direction_seed)
     result['gen_step'] = gen_step
     return result
 
@@ -480,7 +636,21 @@ def make_parser():
     parser.add_argument('--max-candidates', default=None, type=int,
                         help='fixed-point: candidate draws per checkpoint at most (default: max(4 draws, draws + 64)).')
     parser.add_argument('--solver-dtype', default='float64', choices=('float64', 'float32'), help='fixed-point: solver arithmetic.')
+    parser.add_argument('--wasserstein', action='store_true',
+                        help='Also the Wasserstein distances: W1 per statistic and the sliced W1 of the raw columns, written to '
+                             'wdist.csv and wdist.json.')
+    parser.add_argument('--directions', default=DEFAULT_DIRECTIONS, type=int,
+                        help='--wasserstein: directions of the sliced distance (at most {}).'.format(clib.W1_MAX_DIRECTIONS))
+    parser.add_argument('--direction-seed', default=0, type=int, help='--wasserstein: seed of the directions.')
     return parser
+
+
+def recorded_arguments(ns):
+    """The ``arguments`` of distdiff.json for parsed options: the keys the file always had in its mode, never the options of
+    --wasserstein (those are wdist.json's)."""
+    fixed_point = ns.dynamics == 'fixed-point'
+    return {k: v for k, v in vars(ns).items()
+            if (fixed_point and k not in _WASSERSTEIN_ARGUMENTS) or k in _FIXED_TIME_ARGUMENTS}
 
 
 def write_rejections(path, result):
@@ -496,11 +666,12 @@ def main(args=None):
     output = ns.output or ns.rundir
     result = calc_distdiff(ns.rundir, steps=parse_steps(ns.steps), draws=ns.draws, seed=ns.seed, gen_kernel=ns.gen_kernel,
                            max_draws_per_launch=ns.max_draws_per_launch, return_samples=ns.save_tuning_curves,
-                           dynamics=ns.dynamics, max_candidates=ns.max_candidates, solver_dtype=ns.solver_dtype)
+                           dynamics=ns.dynamics, max_candidates=ns.max_candidates, solver_dtype=ns.solver_dtype,
+                           wasserstein=ns.wasserstein, directions=ns.directions, direction_seed=ns.direction_seed)
     os.makedirs(output, exist_ok=True)
     write_long_table(os.path.join(output, 'distdiff.csv'), result)
     fixed_point = ns.dynamics == 'fixed-point'
-    arguments = {k: v for k, v in vars(ns).items() if fixed_point or k in _FIXED_TIME_ARGUMENTS}
+    arguments = recorded_arguments(ns)
     extra = {}
     if fixed_point:
         write_rejections(os.path.join(output, 'rejections.csv'), result)
@@ -513,6 +684,11 @@ def main(args=None):
                        chunks=result['chunks'], draws=result['draws'], bandwidths=result['bandwidths'],
                        contrasts=result['contrasts'], probes=result['probes'], features=list(FEATURES),
                        gen_steps=[int(s) for s in result['gen_step']], **extra), f, indent=1)
+    if ns.wasserstein:
+        write_wdist_table(os.path.join(output, 'wdist.csv'), result)
+        with open(os.path.join(output, 'wdist.json'), 'w') as f:
+            json.dump(dict(arguments={k: getattr(ns, k) for k in _WASSERSTEIN_ARGUMENTS}, directions=result['sliced']['directions'],
+                           gen_steps=[int(s) for s in result['gen_step']]), f, indent=1)
     if ns.save_tuning_curves:
         tcdir = os.path.join(output, 'tuning_curves')
         os.makedirs(tcdir, exist_ok=True)

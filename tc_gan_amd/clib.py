@@ -358,6 +358,7 @@ DECLARED_SYMBOLS = (
     'ssn_ens_record_doubles', 'ssn_ens_moments_f32', 'ssn_ens_jds_grad_f32', 'ssn_ens_gen_grads_f32', 'ssn_ens_apply_f32',
     'ssn_ens_stimulus_hetero_f32',
     'ssn_build_w_table_f32', 'ssn_tc_features_f32', 'ssn_ks_columns_f32',
+    'ssn_ks_w1_columns_f32', 'ssn_project_rows_f32',
     'ssn_build_w_table_f64', 'ssn_fp_select_max_candidates', 'ssn_fp_select_f64', 'ssn_fp_select_f32',
 )
 
@@ -400,6 +401,15 @@ libssnode.ssn_build_w_table_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int,
 libssnode.ssn_tc_features_f32.argtypes = [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p]
 libssnode.ssn_ks_columns_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
 for _name in ('ssn_build_w_table_f32', 'ssn_tc_features_f32', 'ssn_ks_columns_f32'):
+    getattr(libssnode, _name).restype = c_int
+
+#: most directions `ssn_project_rows_f32` takes (SSN_W1_MAX_DIRECTIONS of the header)
+W1_MAX_DIRECTIONS = 4096
+# x, truth_sorted, m, S, B, C, T, n, num, wnum, stream
+libssnode.ssn_ks_w1_columns_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+# x, rows, ldx, C, theta, L, out, stream
+libssnode.ssn_project_rows_f32.argtypes = [c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]
+for _name in ('ssn_ks_w1_columns_f32', 'ssn_project_rows_f32'):
     getattr(libssnode, _name).restype = c_int
 
 libssnode.ssn_build_w_table_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]

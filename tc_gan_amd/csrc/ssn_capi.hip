@@ -1188,6 +1188,31 @@ int ssn_ks_columns_f32(const float* x, const float* truth_sorted, const int* m, 
     SSN_TRY(ssn::launch_ks_columns(x, truth_sorted, m, S, B, C, T, n, num, (hipStream_t)stream));
     return 0;
 }
+int ssn_ks_w1_columns_f32(const float* x, const float* truth_sorted, const int* m, int S, int B, int C, int T, int* n,
+                          long long* num, double* wnum, void* stream) {
+    if (B > SSN_KS_MAX_DRAWS) {
+        g_last_error = "ssn_ks_w1_columns_f32: more than 16384 values per column (the sort runs in 64 KiB of LDS)";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if (S < 0 || B < 1 || C < 0 || T < 0 || ((long)S * C > 0 && (!x || !m || !n || !num || !wnum || (T > 0 && !truth_sorted)))) {
+        g_last_error = "ssn_ks_w1_columns_f32: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_ks_w1_columns(x, truth_sorted, m, S, B, C, T, n, num, wnum, (hipStream_t)stream));
+    return 0;
+}
+int ssn_project_rows_f32(const float* x, long rows, int ldx, int C, const float* theta, int L, float* out, void* stream) {
+    if (L > SSN_W1_MAX_DIRECTIONS) {
+        g_last_error = "ssn_project_rows_f32: more than 4096 directions";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if (rows < 0 || C < 0 || L < 0 || ldx < C || (rows * L > 0 && (!out || (C > 0 && (!x || !theta))))) {
+        g_last_error = "ssn_project_rows_f32: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_project_rows(x, rows, ldx, C, theta, L, out, (hipStream_t)stream));
+    return 0;
+}
 int ssn_build_w_table_f64(const double* z, const double* jds_table, double* W, int S, int B, int N, void* stream) {
     if (S < 0 || B < 0 || N < 1 || ((long)S * B > 0 && (!z || !jds_table || !W))) {
         g_last_error = "ssn_build_w_table_f64: invalid argument";

@@ -394,6 +394,11 @@ hipError_t launch_tc_features(const float* tc, float* feat, long R, int NC, int 
 hipError_t launch_ks_columns(const float* x, const float* t, const int* m, int S, int B, int C, int T, int* n_out,
                              long long* num_out, hipStream_t st);
 
+// ssn_wdist.hip (Wasserstein distances of the scored checkpoints: KS and W1 numerators per column, projections onto directions)
+hipError_t launch_ks_w1_columns(const float* x, const float* t, const int* m, int S, int B, int C, int T, int* n_out,
+                                long long* num_out, double* wnum_out, hipStream_t st);
+hipError_t launch_project_rows(const float* x, long rows, int ldx, int C, const float* theta, int L, float* out, hipStream_t st);
+
 // ssn_fpsample.hip (rejection sampling of fixed points on the device: W table in fp64, verdict per (set, candidate), selection)
 hipError_t launch_build_w_table_f64(const double* z, const double* table, double* W, int A, int B, int N, hipStream_t st);
 template <typename T>

@@ -5,6 +5,7 @@ rows.
 
     python tools/time_distdiff.py [--draws 30,128,1024] [--checkpoints 256,256,32] [--repeats 3] [--out FILE]
     python tools/time_distdiff.py --once 128          # one batched pass alone (for a kernel trace)
+    python tools/time_distdiff.py --wasserstein       # a fourth path: the batched scorer with wasserstein=True
 
 Both paths run the same generator kernel (what 'auto' resolves to for the batched chunk), are warmed, alternate, and every
 window ends in a device synchronise and holds as many passes over the checkpoints as make it --window-seconds long.  One JSON
@@ -76,8 +77,9 @@ def looped(cfg, sets, truth, draws, seed, kernel, score=True):
     return np.stack(nums) if score else None
 
 
-def batched(cfg, sets, truth, draws, seed, kernel, budget):
-    res = distdiff.score_parameter_sets(cfg, sets, truth, draws=draws, seed=seed, gen_kernel=kernel, max_draws_per_launch=budget)
+def batched(cfg, sets, truth, draws, seed, kernel, budget, **wasserstein):
+    res = distdiff.score_parameter_sets(cfg, sets, truth, draws=draws, seed=seed, gen_kernel=kernel, max_draws_per_launch=budget,
+                                        **wasserstein)
     torch.cuda.synchronize()
     return res
 
@@ -100,6 +102,9 @@ def main():
     ap.add_argument('--max-draws-per-launch', type=int, default=distdiff.DEFAULT_MAX_DRAWS_PER_LAUNCH)
     ap.add_argument('--num-sites', type=int, default=SHAPE['num_sites'])
     ap.add_argument('--once', type=int, default=None, help='one warmed batched pass at this many draws, nothing else')
+    ap.add_argument('--wasserstein', action='store_true',
+                    help='also time the batched scorer with wasserstein=True (alternating with the others; --once: that pass)')
+    ap.add_argument('--directions', type=int, default=distdiff.DEFAULT_DIRECTIONS)
     ap.add_argument('--out')
     ns = ap.parse_args()
     cfg = dict(SHAPE, num_sites=ns.num_sites)
@@ -108,11 +113,13 @@ def main():
     sizes = [int(d) for d in ns.draws.split(',')]
     counts = [int(c) for c in ns.checkpoints.split(',')]
     counts = counts * len(sizes) if len(counts) == 1 else counts
+    wkw = dict(wasserstein=True, directions=ns.directions) if ns.wasserstein else {}
     if ns.once is not None:
         sets = thetas(counts[0])
-        batched(cfg, sets[:2], truth, ns.once, 0, ns.gen_kernel, ns.max_draws_per_launch)
-        res = batched(cfg, sets, truth, ns.once, 0, ns.gen_kernel, ns.max_draws_per_launch)
-        print(json.dumps(dict(once=ns.once, checkpoints=len(sets), gen_kernel=res['gen_kernel'], chunks=res['chunks'])))
+        batched(cfg, sets[:2], truth, ns.once, 0, ns.gen_kernel, ns.max_draws_per_launch, **wkw)
+        res = batched(cfg, sets, truth, ns.once, 0, ns.gen_kernel, ns.max_draws_per_launch, **wkw)
+        print(json.dumps(dict(once=ns.once, checkpoints=len(sets), gen_kernel=res['gen_kernel'], chunks=res['chunks'],
+                              wasserstein=ns.wasserstein)))
         return
     rows = []
     for draws, S in zip(sizes, counts):
@@ -125,6 +132,10 @@ def main():
         paths = dict(batched=lambda: batched(cfg, sets, truth, draws, 0, kernel, ns.max_draws_per_launch),
                      loop=lambda: looped(cfg, sets, truth, draws, 0, kernel),
                      loop_forward_only=lambda: looped(cfg, sets, truth, draws, 0, kernel, score=False))
+        if ns.wasserstein:
+            on = batched(cfg, sets, truth, draws, 0, kernel, ns.max_draws_per_launch, **wkw)       # warm-up, and the same integers
+            assert (on['num'] == res['num']).all() and (on['n'] == res['n']).all()
+            paths['batched_wasserstein'] = lambda: batched(cfg, sets, truth, draws, 0, kernel, ns.max_draws_per_launch, **wkw)
         # passes per window: enough of them for a window of --window-seconds (a pass over S checkpoints may take milliseconds)
         passes = {name: max(1, int(np.ceil(ns.window_seconds / window(fn)))) for name, fn in paths.items()}
         secs = {name: [] for name in paths}
