@@ -777,6 +777,33 @@ int ssn_ks_w1_columns_f32(const float *x, const float *truth_sorted, const int *
                           long long *num, double *wnum, void *stream);
 int ssn_project_rows_f32(const float *x, long rows, int ldx, int C, const float *theta, int L, float *out, void *stream);
 
+/* ---- Sliced Wasserstein loss of a minibatch and its gradient (networks/sliced_wasserstein.py; csrc/ssn_swd.hip) ----
+ * px, py: device [B][L], the projections (ssn_project_rows_f32) of B generated rows and of B truth rows onto L directions.
+ * ssn_swd_match_f32: for every direction l the pairs (px[b][l], b) are sorted ascending by value, ties by row index b -- the
+ *   comparison is the float comparison, -0 counts as +0 (numpy's argsort(kind='stable')) -- and py[.][l] is sorted ascending.
+ *   With u_i, v_i the i-th sorted values and b_i the row that holds u_i, d_i = (double) u_i - (double) v_i, and for power p:
+ *     loss_l[l] = (sum_i |d_i|^p) / B        in fp64: |d_i| is exact, every product d_i d_i is rounded once, the sum runs in an
+ *                                            order the launch geometry fixes (per thread in index order, lanes 32, 16, ... 1
+ *                                            apart, the four waves in order), without atomics: two calls give the same bits.
+ *                                            All terms are non-negative: |loss_l - exact| <= (B + 2) 2^-52 exact, and the value
+ *                                            is exact where every term and partial sum is representable and B is a power of two;
+ *     coef[b_i][l] = (float) (sign(d_i) inv)     p = 1, sign(0) = 0
+ *     coef[b_i][l] = (float) ((2.0 d_i) inv)     p = 2,         with inv = 1.0 / ((double) L (double) B):
+ *   the derivative of (1/L) sum_l loss_l[l] by px[b][l].  For p = 1 loss_l[l] is the W1 of the two columns, the unit of
+ *   ssn_ks_w1_columns_f32's wnum / (n m).  A column of px or py that holds a value which is not finite gives loss_l[l] = NaN and
+ *   coef[.][l] = NaN (found before the sort).  coef: device [B][L], loss_l: device double[L].
+ *   B <= SSN_SWD_MAX_BATCH (one workgroup sorts 64-bit keys of px and the values of py in 48 KiB of LDS, padded to a power of
+ *   two) and L <= SSN_W1_MAX_DIRECTIONS; more, a negative size, a power other than 1 or 2 or a null pointer is refused; B == 0
+ *   or L == 0 is success and writes nothing.
+ * ssn_swd_backproject_f32: gx[b][c] = (float) acc with acc = 0 and, for l = 0 .. L - 1 in this order,
+ *   acc = fma((double) coef[b L + l], (double) theta[l D + c], acc): the products of two floats are exact in fp64, so this is the
+ *   sequential fp64 sum of exact products, rounded to float at the end -- the derivative of the loss by x[b][c] where
+ *   px = x theta^T.  theta: device [L][D], gx: device [B][D].  A NaN column of coef makes all of gx NaN.  L == 0 writes zeros;
+ *   B == 0 or D == 0 is success and writes nothing; L above the limit, a negative size or a null pointer is refused. */
+#define SSN_SWD_MAX_BATCH 4096
+int ssn_swd_match_f32(const float *px, const float *py, int B, int L, int power, float *coef, double *loss_l, void *stream);
+int ssn_swd_backproject_f32(const float *coef, const float *theta, int B, int L, int D, float *gx, void *stream);
+
 /* ---- Rejection sampling of fixed points on the device (ssnode.sample_tuning_curves_table; csrc/ssn_fpsample.hip) ----
  * A parameter sets see the same stream of candidate draws; every (set, candidate) pair is solved for NB stimuli by
  * ssn_solve_batch_* (the A R pairs as its batch, set-major), and the first NZ candidates of a set, in stream order, whose solves

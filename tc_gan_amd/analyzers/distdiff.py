@@ -158,6 +158,12 @@ def write_long_table(path, result):
 def slice_directions(directions, columns, seed=0):
     """The directions of the sliced distance, float32 (directions, columns): the rows of
     ``numpy.random.RandomState(seed).randn(directions, columns)``, each divided by its float64 norm, then rounded to float32."""
+    return draw_slice_directions(np.random.RandomState(seed), directions, columns)
+
+
+def draw_slice_directions(rng, directions, columns):
+    """`slice_directions` from the next ``rng.randn(directions, columns)`` of a RandomState that is continued: a trainer that
+    draws fresh directions every step calls this on one stream (the first call gives ``slice_directions(..., seed)``)."""
     directions, columns = int(directions), int(columns)
     if directions < 1:
         raise ValueError('directions must be at least 1, got {}'.format(directions))
@@ -165,7 +171,7 @@ def slice_directions(directions, columns, seed=0):
         raise ValueError('directions = {} is more than the {} the projection kernel takes'.format(directions, clib.W1_MAX_DIRECTIONS))
     if columns < 1:
         raise ValueError('directions need at least one column, got {}'.format(columns))
-    g = np.random.RandomState(seed).randn(directions, columns)
+    g = rng.randn(directions, columns)
     return np.ascontiguousarray(g / np.sqrt((g * g).sum(axis=1, keepdims=True)), dtype='float32')
 
 

@@ -359,6 +359,7 @@ DECLARED_SYMBOLS = (
     'ssn_ens_stimulus_hetero_f32',
     'ssn_build_w_table_f32', 'ssn_tc_features_f32', 'ssn_ks_columns_f32',
     'ssn_ks_w1_columns_f32', 'ssn_project_rows_f32',
+    'ssn_swd_match_f32', 'ssn_swd_backproject_f32',
     'ssn_build_w_table_f64', 'ssn_fp_select_max_candidates', 'ssn_fp_select_f64', 'ssn_fp_select_f32',
 )
 
@@ -410,6 +411,15 @@ libssnode.ssn_ks_w1_columns_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int,
 # x, rows, ldx, C, theta, L, out, stream
 libssnode.ssn_project_rows_f32.argtypes = [c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]
 for _name in ('ssn_ks_w1_columns_f32', 'ssn_project_rows_f32'):
+    getattr(libssnode, _name).restype = c_int
+
+#: most rows of a minibatch `ssn_swd_match_f32` takes (SSN_SWD_MAX_BATCH of the header)
+SWD_MAX_BATCH = 4096
+# px, py, B, L, power, coef, loss_l, stream
+libssnode.ssn_swd_match_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+# coef, theta, B, L, D, gx, stream
+libssnode.ssn_swd_backproject_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+for _name in ('ssn_swd_match_f32', 'ssn_swd_backproject_f32'):
     getattr(libssnode, _name).restype = c_int
 
 libssnode.ssn_build_w_table_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]

@@ -1213,6 +1213,34 @@ int ssn_project_rows_f32(const float* x, long rows, int ldx, int C, const float*
     SSN_TRY(ssn::launch_project_rows(x, rows, ldx, C, theta, L, out, (hipStream_t)stream));
     return 0;
 }
+int ssn_swd_match_f32(const float* px, const float* py, int B, int L, int power, float* coef, double* loss_l, void* stream) {
+    if (B > SSN_SWD_MAX_BATCH) {
+        g_last_error = "ssn_swd_match_f32: more than 4096 rows (keys and values are sorted in 48 KiB of LDS)";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if (L > SSN_W1_MAX_DIRECTIONS) {
+        g_last_error = "ssn_swd_match_f32: more than 4096 directions";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if (B < 0 || L < 0 || (power != 1 && power != 2) || ((long)B * L > 0 && (!px || !py || !coef || !loss_l))) {
+        g_last_error = "ssn_swd_match_f32: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_swd_match(px, py, B, L, power, coef, loss_l, (hipStream_t)stream));
+    return 0;
+}
+int ssn_swd_backproject_f32(const float* coef, const float* theta, int B, int L, int D, float* gx, void* stream) {
+    if (L > SSN_W1_MAX_DIRECTIONS) {
+        g_last_error = "ssn_swd_backproject_f32: more than 4096 directions";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if (B < 0 || L < 0 || D < 0 || ((long)B * D > 0 && (!gx || (L > 0 && (!coef || !theta))))) {
+        g_last_error = "ssn_swd_backproject_f32: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_swd_backproject(coef, theta, B, L, D, gx, (hipStream_t)stream));
+    return 0;
+}
 int ssn_build_w_table_f64(const double* z, const double* jds_table, double* W, int S, int B, int N, void* stream) {
     if (S < 0 || B < 0 || N < 1 || ((long)S * B > 0 && (!z || !jds_table || !W))) {
         g_last_error = "ssn_build_w_table_f64: invalid argument";

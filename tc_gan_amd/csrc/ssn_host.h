@@ -399,6 +399,10 @@ hipError_t launch_ks_w1_columns(const float* x, const float* t, const int* m, in
                                 long long* num_out, double* wnum_out, hipStream_t st);
 hipError_t launch_project_rows(const float* x, long rows, int ldx, int C, const float* theta, int L, float* out, hipStream_t st);
 
+// ssn_swd.hip (sliced Wasserstein loss of a minibatch: rank matching per direction, coefficients carried back to the rows)
+hipError_t launch_swd_match(const float* px, const float* py, int B, int L, int power, float* coef, double* loss_l, hipStream_t st);
+hipError_t launch_swd_backproject(const float* coef, const float* theta, int B, int L, int D, float* gx, hipStream_t st);
+
 // ssn_fpsample.hip (rejection sampling of fixed points on the device: W table in fp64, verdict per (set, candidate), selection)
 hipError_t launch_build_w_table_f64(const double* z, const double* table, double* W, int A, int B, int N, hipStream_t st);
 template <typename T>

@@ -7,7 +7,8 @@ import numpy as np
 
 from . import execution, param_file, ssnode
 from .recorders import (ConditionalTuningCurveStatsRecorder, DiscLearningRecorder, DiscParamStatsRecorder,
-                        FlexGenParamRecorder, GenMomentsRecorder, LearningRecorder, MMLearningRecorder, _host)
+                        FlexGenParamRecorder, GenMomentsRecorder, LearningRecorder, MMLearningRecorder, SWDLearningRecorder,
+                        _host)
 from .utils import Namespace
 
 logger = getLogger(__name__)
@@ -286,3 +287,20 @@ class MomentMatchingDriver(_GeneratorStepLoop):
             assert info.step == gen_step
             return info
         self.iterate(one_update)
+
+
+class SlicedWassersteinDriver(MomentMatchingDriver):
+    """Driver of `BPTTSlicedWasserstein`: the moment-matching loop with the `learning` table of the sliced loss and no
+    `gen_moments` table."""
+
+    def __init__(self, learner, datastore, iterations, quiet, quit_JDS_threshold=-1):
+        super(SlicedWassersteinDriver, self).__init__(learner, datastore, iterations, quiet, gen_moments_record_interval=-1,
+                                                      quit_JDS_threshold=quit_JDS_threshold)
+
+    def pre_loop(self):
+        self.learning_recorder = SWDLearningRecorder.from_driver(self)
+        self.generator_recorder = FlexGenParamRecorder.from_driver(self)
+
+    def post_update(self, gen_step, update_result):
+        self.learning_recorder.record(gen_step, update_result)
+        self.watch_generator(gen_step)

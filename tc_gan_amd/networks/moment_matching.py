@@ -53,18 +53,15 @@ def calc_moment_weights(data, moment_weight_type='mean', moment_weights_regulari
     return data_moments, np.array(weights, dtype='float64')
 
 
-class BPTTMomentMatcher(object):
-    """moment_matching.py:260-399 (with the trainer of 107-257 folded in)."""
+class GeneratorStepTrainer(object):
+    """What a critic-free BPTT trainer does whatever its loss is: the noise draw on `self.rng`, the saving forward, the adjoint
+    sweep from a loss gradient `gx` (B, D), the penalties, the update with parameter clipping.  A subclass gives
+    `train_generator(info)` its loss through `generator_step`."""
 
-    def __init__(self, gen, gen_updaters, bandwidths, contrasts, lam, moment_weights_regularization,
-                 include_inhibitory_neurons, rate_penalty_threshold, moment_weight_type, dynamics_cost, rate_cost,
-                 param_bounds, seed=0):
-        assert moment_weight_type in MOMENT_WEIGHT_TYPES
+    def _init_generator_step(self, gen, gen_updaters, bandwidths, contrasts, include_inhibitory_neurons,
+                             rate_penalty_threshold, dynamics_cost, rate_cost, param_bounds, seed=0):
         self.gen = gen
         self.gen_updaters = gen_updaters
-        self.lam = lam
-        self.moment_weights_regularization = moment_weights_regularization
-        self.moment_weight_type = moment_weight_type
         self.rng = as_randomstate(seed)          # (the reference's stream; device draws hand their state back lazily)
         self.bandwidths = bandwidths
         self.contrasts = contrasts
@@ -99,12 +96,6 @@ class BPTTMomentMatcher(object):
     def get_gen_param(self):
         return [self.gen.J.copy(), self.gen.D.copy(), self.gen.S.copy()]
 
-    def set_dataset(self, data):
-        self.data_moments, self.moment_weights = calc_moment_weights(
-            data, self.moment_weight_type, self.moment_weights_regularization, self.lam)
-        self._dm = torch.as_tensor(np.ascontiguousarray(self.data_moments), device='cuda', dtype=torch.float64)
-        self._w = torch.as_tensor(np.ascontiguousarray(self.moment_weights), device='cuda', dtype=torch.float64)
-
     def prepare(self):
         """Nothing to compile."""
 
@@ -116,6 +107,60 @@ class BPTTMomentMatcher(object):
             per = self.gen.batchsize
             rows = (self.reducer.rank * per, (self.reducer.rank + 1) * per)
         return self.gen.gen_noise(self.rng, stimulator_bandwidths=np.empty((self.global_batchsize, 1)), rows=rows)
+
+    def generator_step(self, info, loss_grad):
+        """One update: `loss_grad(x)` -> (gx, L0) for the tuning curves x (B_local, D) of this step's forward.  Fills
+        `info.dynamics_penalty`, `info.rate_penalty` and `info.loss` (L0 with the penalties) and returns L0."""
+        noise = self._draw_noise()
+        out = self.gen.forward(rng=self.rng, save=True, stimulator_bandwidths=self.stimulator_bandwidths,
+                               stimulator_contrasts=self.stimulator_contrasts,
+                               model_rate_penalty_threshold=self.rate_penalty_threshold, **noise)
+        gx, l0 = loss_grad(out.prober_tuning_curve)
+        # L0 is a function of the GLOBAL minibatch: the local adjoint sweeps add up over ranks, whereas the
+        # penalties are per-rank means -> scale gx so that the rank MEAN below is right for both
+        gdict = self.gen.backward(gx * self.reducer.world, self.dynamics_cost, self.rate_cost)
+        pens = torch.stack([out.model_dynamics_penalty.reshape(()).to(torch.float32),
+                            out.model_rate_penalty.reshape(()).to(torch.float32)])
+        grads = torch.as_tensor(np.concatenate([np.ravel(gdict[name]) for name in self._pnames]), device='cuda',
+                                dtype=torch.float32)
+        self.reducer.mean_(grads, pens)
+        off = 0
+        for name in self._pnames:                                  # moment_matching.py:245-257 (clip_params)
+            value = np.asarray(getattr(self.gen, name))
+            p = self._gparams[name]
+            p.copy_(torch.as_tensor(np.array(value).ravel(), dtype=torch.float32))
+            self.gen_updaters[name](p, grads[off:off + p.numel()], clip=self.param_bounds[name])
+            off += p.numel()
+            setattr(self.gen, name, p.cpu().numpy().astype('float64').reshape(value.shape))
+        info.dynamics_penalty = float(pens[0])
+        info.rate_penalty = float(pens[1])
+        info.loss = l0 + self.dynamics_cost * info.dynamics_penalty + self.rate_cost * info.rate_penalty
+        return l0
+
+    def learning(self):
+        for step in itertools.count():
+            self.train_watch = StopWatch()
+            yield self.train_generator(Namespace(step=step))
+
+
+class BPTTMomentMatcher(GeneratorStepTrainer):
+    """moment_matching.py:260-399 (with the trainer of 107-257 folded in)."""
+
+    def __init__(self, gen, gen_updaters, bandwidths, contrasts, lam, moment_weights_regularization,
+                 include_inhibitory_neurons, rate_penalty_threshold, moment_weight_type, dynamics_cost, rate_cost,
+                 param_bounds, seed=0):
+        assert moment_weight_type in MOMENT_WEIGHT_TYPES
+        self.lam = lam
+        self.moment_weights_regularization = moment_weights_regularization
+        self.moment_weight_type = moment_weight_type
+        self._init_generator_step(gen, gen_updaters, bandwidths, contrasts, include_inhibitory_neurons,
+                                  rate_penalty_threshold, dynamics_cost, rate_cost, param_bounds, seed)
+
+    def set_dataset(self, data):
+        self.data_moments, self.moment_weights = calc_moment_weights(
+            data, self.moment_weight_type, self.moment_weights_regularization, self.lam)
+        self._dm = torch.as_tensor(np.ascontiguousarray(self.data_moments), device='cuda', dtype=torch.float64)
+        self._w = torch.as_tensor(np.ascontiguousarray(self.moment_weights), device='cuda', dtype=torch.float64)
 
     def moment_loss_grad(self, x):
         """x (B_local, D) fp32 CUDA -> (gx, L0, gen_moments (2, D) numpy)."""
@@ -135,44 +180,18 @@ class BPTTMomentMatcher(object):
         return gx, float(host[0]), host[1:].reshape(2, D)
 
     def train_generator(self, info):
+        def loss_grad(x):
+            gx, l0, info.gen_moments = self.moment_loss_grad(x)
+            return gx, l0
         with self.train_watch:
-            noise = self._draw_noise()
-            out = self.gen.forward(rng=self.rng, save=True, stimulator_bandwidths=self.stimulator_bandwidths,
-                                   stimulator_contrasts=self.stimulator_contrasts,
-                                   model_rate_penalty_threshold=self.rate_penalty_threshold, **noise)
-            gx, l0, gen_moments = self.moment_loss_grad(out.prober_tuning_curve)
-            # L0 is a function of the GLOBAL minibatch: the local adjoint sweeps add up over ranks, whereas the
-            # penalties are per-rank means -> scale gx so that the rank MEAN below is right for both
-            gdict = self.gen.backward(gx * self.reducer.world, self.dynamics_cost, self.rate_cost)
-            pens = torch.stack([out.model_dynamics_penalty.reshape(()).to(torch.float32),
-                                out.model_rate_penalty.reshape(()).to(torch.float32)])
-            grads = torch.as_tensor(np.concatenate([np.ravel(gdict[name]) for name in self._pnames]), device='cuda',
-                                    dtype=torch.float32)
-            self.reducer.mean_(grads, pens)
-            off = 0
-            for name in self._pnames:                                  # moment_matching.py:245-257 (clip_params)
-                value = np.asarray(getattr(self.gen, name))
-                p = self._gparams[name]
-                p.copy_(torch.as_tensor(np.array(value).ravel(), dtype=torch.float32))
-                self.gen_updaters[name](p, grads[off:off + p.numel()], clip=self.param_bounds[name])
-                off += p.numel()
-                setattr(self.gen, name, p.cpu().numpy().astype('float64').reshape(value.shape))
-            info.dynamics_penalty = float(pens[0])
-            info.rate_penalty = float(pens[1])
-            info.loss = l0 + self.dynamics_cost * info.dynamics_penalty + self.rate_cost * info.rate_penalty
-            info.gen_moments = gen_moments
+            self.generator_step(info, loss_grad)
         info.train_time = self.train_watch.sum()
         return info
 
-    def learning(self):
-        for step in itertools.count():
-            self.train_watch = StopWatch()
-            yield self.train_generator(Namespace(step=step))
 
-
-def make_moment_matcher(config):
-    """make_moment_matcher(config: dict) -> (BPTTMomentMatcher, dict of unconsumed config) (moment_matching.py:437-472)."""
-    kwargs = dict(DEFAULT_PARAMS, **config)
+def generator_step_parts(kwargs):
+    """Takes from `kwargs` (a config over the defaults, consumed in place) what `GeneratorStepTrainer._init_generator_step`
+    needs -- the generator, one updater per parameter, the bounds, the costs -- and returns it as keyword arguments."""
     take = kwargs.pop
     bandwidths, contrasts, num_sites = take('bandwidths'), take('contrasts'), take('num_sites')
     include_inhibitory_neurons = take('include_inhibitory_neurons')
@@ -201,11 +220,16 @@ def make_moment_matcher(config):
     bounds['V'] = _v_bounds(take('V_min', 0), take('V_max', 1), ssn_type)
     upd_cfg = {k: take(k) for k in ('learning_rate', 'update_name', 'update_config', 'reg_l2_penalty', 'reg_l2_decay',
                                     'reg_l1_penalty', 'reg_l1_decay') if k in kwargs}
-    mm = BPTTMomentMatcher(
-        gen, {name: Updater(**upd_cfg) for name in 'VJDS'}, bandwidths, contrasts,
-        lam=take('lam'), moment_weights_regularization=take('moment_weights_regularization'),
-        include_inhibitory_neurons=include_inhibitory_neurons,
-        rate_penalty_threshold=take('rate_penalty_threshold'), moment_weight_type=take('moment_weight_type'),
-        dynamics_cost=take('dynamics_cost', 1.0), rate_cost=take('rate_cost'), param_bounds=bounds,
-        seed=take('seed', 0))
+    return dict(gen=gen, gen_updaters={name: Updater(**upd_cfg) for name in 'VJDS'}, bandwidths=bandwidths,
+                contrasts=contrasts, include_inhibitory_neurons=include_inhibitory_neurons,
+                rate_penalty_threshold=take('rate_penalty_threshold'), dynamics_cost=take('dynamics_cost', 1.0),
+                rate_cost=take('rate_cost'), param_bounds=bounds, seed=take('seed', 0))
+
+
+def make_moment_matcher(config):
+    """make_moment_matcher(config: dict) -> (BPTTMomentMatcher, dict of unconsumed config) (moment_matching.py:437-472)."""
+    kwargs = dict(DEFAULT_PARAMS, **config)
+    parts = generator_step_parts(kwargs)
+    mm = BPTTMomentMatcher(lam=kwargs.pop('lam'), moment_weights_regularization=kwargs.pop('moment_weights_regularization'),
+                           moment_weight_type=kwargs.pop('moment_weight_type'), **parts)
     return mm, kwargs

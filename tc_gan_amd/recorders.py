@@ -20,6 +20,8 @@ TABLES = {
                               ('rate_penalty', 'double'), ('dynamics_penalty', 'double')], ()),
     'mm_learning': ('learning', [('step', 'uint32'), ('loss', 'double'), ('rate_penalty', 'double'),
                                  ('dynamics_penalty', 'double'), ('train_time', 'double')], ()),
+    'swd_learning': ('learning', [('step', 'uint32'), ('loss', 'double'), ('swd', 'double'), ('dynamics_penalty', 'double'),
+                                  ('rate_penalty', 'double'), ('train_time', 'double')], ()),
     'gen_moments': ('gen_moments', [('step', 'uint32')], ('mean_{}', 'var_{}')),
     'disc_learning': ('disc_learning', [('gen_step', 'uint32'), ('disc_step', 'uint32'), ('Dloss', 'double'),
                                         ('Daccuracy', 'double'), ('SSsolve_time', 'double'), ('gradient_time', 'double'),
@@ -96,6 +98,21 @@ class MMLearningRecorder(HDF5Recorder):
     def record(self, gen_step, update_result):
         self._saverow([gen_step, update_result.loss, update_result.rate_penalty, update_result.dynamics_penalty,
                        update_result.train_time])
+
+    @classmethod
+    def from_driver(cls, driver):
+        return cls.make(driver.datastore, quiet=driver.quiet)
+
+
+class SWDLearningRecorder(HDF5Recorder):
+    """The `learning` table of the sliced Wasserstein trainer: loss is the total (with the penalties), swd the bare sliced loss."""
+
+    tablename = TABLES['swd_learning'][0]
+    dtype = table_dtype('swd_learning')
+
+    def record(self, gen_step, update_result):
+        self._saverow([gen_step, update_result.loss, update_result.swd, update_result.dynamics_penalty,
+                       update_result.rate_penalty, update_result.train_time])
 
     @classmethod
     def from_driver(cls, driver):

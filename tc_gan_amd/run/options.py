@@ -1,8 +1,8 @@
-"""The command-line surface of the three BPTT run modules as DATA.
+"""The command-line surface of the BPTT run modules as DATA.
 
 One table, `OPTIONS`: a row per option -- flags, default, value type, help, and the scripts that take it
 (`w` = tc_gan.run.bptt_wgan, `c` = bptt_cwgan, `m` = bptt_moments) -- from which `build_parser` makes each script's
-``argparse`` parser.  The names, aliases and defaults are the reference's (tc_gan/run/bptt_wgan.py:46-172,
+``argparse`` parser; `s` = bptt_swd (new) takes the rows of `m` that still apply and `SWD_OPTIONS`.  The names, aliases and defaults are the reference's (tc_gan/run/bptt_wgan.py:46-172,
 bptt_cwgan.py:17-53, bptt_moments.py:36-101, run/gan.py:1109-1152, execution.py:290-317); `run_config` keys follow from the
 first long flag as argparse derives them, and the CLI tests (tests/test_run_bptt_cwgan_gpu.py: option cases, the key set of
 the paper's run.json through --load-config) are the contract.  Options this build adds say "(new)".
@@ -128,7 +128,19 @@ OPTIONS = (
             help='A shorthand for --datastore-template=logfiles/debug.'),
        _opt('wcm', '--load-config', help='Load hyper parameters from a JSON/YAML/pickle file; they override the command line.')])
 
-DATASTORE_TEMPLATES = {'w': 'logfiles/BPTT_WGAN_{layers_str}', 'c': 'logfiles/BPTT_CWGAN_{layers_str}', 'm': 'logfiles/BPTT_MM_{lam}'}
+#: `s` = tc_gan.run.bptt_swd (new): the rows of `m` that do not speak of moments, then its own
+SWD_DROPPED = ('--lam', '--moment-weights-regularization', '--moment-weight-type', '--gen-moments-record-interval')
+SWD_OPTIONS = [
+    _opt('s', '--swd-directions', default=128, type='int',
+         help='Random unit directions of the sliced distance, drawn afresh every step (at most {}).'.format(clib.W1_MAX_DIRECTIONS)),
+    _opt('s', '--swd-power', default=2, type='int', choices=(1, 2),
+         help='Power p of the loss, the mean over directions and ranks of |difference of the sorted projections|^p.  2 '
+              '(default): a gradient that is continuous in the tuning curves; 1: the unit of distdiff --wasserstein\'s sliced_w1'),
+    _opt('s', '--swd-direction-seed', default=0, type='int',
+         help='Seed of the streams the directions and the truth minibatches are drawn from (apart from the noise stream).')]
+
+DATASTORE_TEMPLATES = {'w': 'logfiles/BPTT_WGAN_{layers_str}', 'c': 'logfiles/BPTT_CWGAN_{layers_str}', 'm': 'logfiles/BPTT_MM_{lam}',
+                       's': 'logfiles/BPTT_SWD_{swd_directions}_{swd_power}'}
 
 
 class _Formatter(argparse.RawDescriptionHelpFormatter, argparse.ArgumentDefaultsHelpFormatter):
@@ -136,7 +148,10 @@ class _Formatter(argparse.RawDescriptionHelpFormatter, argparse.ArgumentDefaults
 
 
 def options_of(script):
-    """The rows of `OPTIONS` the script takes ('w', 'c' or 'm'), in table order."""
+    """The rows of `OPTIONS` the script takes ('w', 'c' or 'm'), in table order; for 's' the rows of 'm' without `SWD_DROPPED`,
+    then `SWD_OPTIONS`."""
+    if script == 's':
+        return [o for o in options_of('m') if o['flags'][0] not in SWD_DROPPED] + SWD_OPTIONS
     return [o for o in OPTIONS if script in o['scripts']]
 
 
