@@ -804,6 +804,42 @@ int ssn_project_rows_f32(const float *x, long rows, int ldx, int C, const float 
 int ssn_swd_match_f32(const float *px, const float *py, int B, int L, int power, float *coef, double *loss_l, void *stream);
 int ssn_swd_backproject_f32(const float *coef, const float *theta, int B, int L, int D, float *gx, void *stream);
 
+/* ---- 6c. Ensembles of sliced Wasserstein runs (networks/sliced_wasserstein_ensemble.py; csrc/ssn_ens_swd.hip) ----
+ * K independent runs of the loss above in one launch each, whatever K is (ssn_ens_swd_match_f32: two, the match and the sum
+ * l0).  Member k owns rows [k B, (k + 1) B) of x[K B][D] (generated) and y[K B][D] (its truth minibatch), its own directions
+ * theta[k][L][D] and its own power[k] in {1, 2}; L, B and D are shared.  Every sum of a member runs over its own rows in the
+ * single run's order: the kernels call the device functions the single-run kernels call, so the outputs of member k are THE BITS
+ * ssn_project_rows_f32, ssn_swd_match_f32 and ssn_swd_backproject_f32 give for that member alone (B, L, D, its theta, its
+ * power), on every launch.  No atomics.
+ * ssn_ens_swd_project_f32: px, py: device [K B][L], the projections of x and of y on the member's theta; one launch for both
+ *   samples and all members.  D == 0 writes zeros.
+ * ssn_ens_swd_match_f32: coef: device [K B][L], loss_l: device double[K][L], l0: device double[K] with
+ *     l0[k] = (sum_l loss_l[k][l]) / L,   a sequential fp64 sum in index order, no contraction: numpy's cumsum(loss_l[k])[-1] / L;
+ *   inv = 1 / (L B) with B of ONE member.  power: HOST int[K], read before the call returns.  A value that is not finite in
+ *   member k's column l gives NaN for loss_l[k][l], coef[k B .. (k + 1) B)[l] and l0[k] and touches nothing of another member.
+ *   form: SSN_SWD_FORM_AUTO (the wave form where B <= SSN_SWD_WAVE_MAX_BATCH, else the general form), SSN_SWD_FORM_GENERAL (one
+ *   workgroup per (direction, member), the LDS bitonic network of ssn_swd_match_f32) or SSN_SWD_FORM_WAVE (one wave64 per
+ *   (member, direction) column, keys and values in registers, the same network over cross-lane moves; B <= 64 or refused).
+ *   Both forms give the same bits.
+ * ssn_ens_swd_backproject_f32: gx: device [K B][D] from coef and the member's theta.  L == 0 writes zeros.
+ * Refused (ssn_last_error names it): K > SSN_ENS_SWD_MAX_MEMBERS, B > SSN_SWD_MAX_BATCH, L > SSN_W1_MAX_DIRECTIONS, a power other
+ *   than 1 or 2, an unknown form, a negative size, a null pointer.  K, B or L == 0 is success and writes nothing.
+ * ssn_ens_gen_grads_l0_f32: ssn_ens_gen_grads_f32 with L0 of member k taken from l0[k] (device double[K]) instead of formed
+ *   from moments: a->D == 0, a->data_moments and a->weights NULL (else refused).  The record row of ssn_ens_record_doubles(0, P):
+ *   [0] L0, [1] dynamics_penalty, [2] rate_penalty, [3] loss = L0 + costs[k][0] dyn + costs[k][1] rate, [4 .. 4 + P) the new
+ *   parameters, then the P gradients.  Gradients and penalties are the bits of ssn_ens_gen_grads_f32. */
+#define SSN_ENS_SWD_MAX_MEMBERS 2048
+#define SSN_SWD_WAVE_MAX_BATCH 64
+#define SSN_SWD_FORM_AUTO 0
+#define SSN_SWD_FORM_GENERAL 1
+#define SSN_SWD_FORM_WAVE 2
+int ssn_ens_swd_project_f32(const float *x, const float *y, const float *theta, int K, int B, int L, int D, float *px, float *py,
+                            void *stream);
+int ssn_ens_swd_match_f32(const float *px, const float *py, const int *power, int K, int B, int L, int form, float *coef,
+                          double *loss_l, double *l0, void *stream);
+int ssn_ens_swd_backproject_f32(const float *coef, const float *theta, int K, int B, int L, int D, float *gx, void *stream);
+int ssn_ens_gen_grads_l0_f32(const ssn_ens_grads *a, const double *l0, void *stream);
+
 /* ---- Rejection sampling of fixed points on the device (ssnode.sample_tuning_curves_table; csrc/ssn_fpsample.hip) ----
  * A parameter sets see the same stream of candidate draws; every (set, candidate) pair is solved for NB stimuli by
  * ssn_solve_batch_* (the A R pairs as its batch, set-major), and the first NZ candidates of a set, in stream order, whose solves

@@ -360,6 +360,7 @@ DECLARED_SYMBOLS = (
     'ssn_build_w_table_f32', 'ssn_tc_features_f32', 'ssn_ks_columns_f32',
     'ssn_ks_w1_columns_f32', 'ssn_project_rows_f32',
     'ssn_swd_match_f32', 'ssn_swd_backproject_f32',
+    'ssn_ens_swd_project_f32', 'ssn_ens_swd_match_f32', 'ssn_ens_swd_backproject_f32', 'ssn_ens_gen_grads_l0_f32',
     'ssn_build_w_table_f64', 'ssn_fp_select_max_candidates', 'ssn_fp_select_f64', 'ssn_fp_select_f32',
 )
 
@@ -420,6 +421,21 @@ libssnode.ssn_swd_match_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int,
 # coef, theta, B, L, D, gx, stream
 libssnode.ssn_swd_backproject_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
 for _name in ('ssn_swd_match_f32', 'ssn_swd_backproject_f32'):
+    getattr(libssnode, _name).restype = c_int
+
+#: most members the `ssn_ens_swd_*` entries take, most rows of the match's wave form, its forms (the header's macros)
+ENS_SWD_MAX_MEMBERS = 2048
+SWD_WAVE_MAX_BATCH = 64
+SWD_FORM_AUTO, SWD_FORM_GENERAL, SWD_FORM_WAVE = 0, 1, 2
+# x, y, theta, K, B, L, D, px, py, stream
+libssnode.ssn_ens_swd_project_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+# px, py, power (HOST int[K]), K, B, L, form, coef, loss_l, l0, stream
+libssnode.ssn_ens_swd_match_f32.argtypes = [c_void_p, c_void_p, POINTER(c_int), c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]
+# coef, theta, K, B, L, D, gx, stream
+libssnode.ssn_ens_swd_backproject_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+libssnode.ssn_ens_gen_grads_l0_f32.argtypes = [POINTER(EnsGrads), c_void_p, c_void_p]
+for _name in ('ssn_ens_swd_project_f32', 'ssn_ens_swd_match_f32', 'ssn_ens_swd_backproject_f32', 'ssn_ens_gen_grads_l0_f32'):
     getattr(libssnode, _name).restype = c_int
 
 libssnode.ssn_build_w_table_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]

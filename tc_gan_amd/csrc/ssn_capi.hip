@@ -1136,6 +1136,22 @@ int ssn_ens_gen_grads_f32(const ssn_ens_grads* a, void* stream) {
     SSN_TRY(ssn::launch_ens_gen_grads(g, (hipStream_t)stream));
     return 0;
 }
+int ssn_ens_gen_grads_l0_f32(const ssn_ens_grads* a, const double* l0, void* stream) {
+    if (!a || a->K < 0 || a->B <= 0 || a->nv < 0 || a->nv > 2 || a->NB <= 0 || a->M <= 0 || (a->M & 1) || a->D != 0 ||
+        a->data_moments || a->weights || a->rstride < ssn_ens_record_doubles(0, a->nv + 12) ||
+        (a->K > 0 && (!l0 || !a->part || !a->dyn_row || !a->rate_row || !a->costs || !a->grads || !a->rec ||
+                      (a->nv > 0 && (!a->g_ext || !a->ext_base || !a->zin))))) {
+        g_last_error = "ssn_ens_gen_grads_l0: invalid argument (D must be 0, data_moments and weights null)";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    ssn::EnsGradsArgs g{};
+    g.K = a->K; g.B = a->B; g.nv = a->nv; g.NB = a->NB; g.M = a->M; g.D = 0;
+    g.part = a->part; g.g_ext = a->g_ext; g.ext_base = a->ext_base; g.zin = a->zin; g.dyn_row = a->dyn_row; g.rate_row = a->rate_row;
+    g.scale_dyn = a->scale_dyn; g.scale_rate = a->scale_rate;
+    g.costs = a->costs; g.grads = a->grads; g.rec = a->rec; g.rstride = a->rstride; g.l0 = l0;
+    SSN_TRY(ssn::launch_ens_gen_grads(g, (hipStream_t)stream));
+    return 0;
+}
 int ssn_ens_apply_f32(const ssn_ens_apply* a, void* stream) {
     if (!a || a->K < 0 || a->P <= 0 || a->kind < 0 || a->kind > 2 || a->rec_off < 0 || a->rstride < a->rec_off + 2 * a->P ||
         (a->K > 0 && (!a->hyp || !a->clip_lo || !a->clip_hi || !a->p || !a->g || !a->rec || (a->kind > 0 && !a->s1) ||
@@ -1239,6 +1255,71 @@ int ssn_swd_backproject_f32(const float* coef, const float* theta, int B, int L,
         return SSN_ERR_BASE + (int)hipErrorInvalidValue;
     }
     SSN_TRY(ssn::launch_swd_backproject(coef, theta, B, L, D, gx, (hipStream_t)stream));
+    return 0;
+}
+static_assert(SSN_ENS_SWD_MAX_MEMBERS == ssn::SWD_ENS_MAX_MEMBERS && SSN_SWD_WAVE_MAX_BATCH == ssn::SWD_WAVE_MAX_BATCH &&
+              SSN_SWD_FORM_AUTO == ssn::SWD_FORM_AUTO && SSN_SWD_FORM_GENERAL == ssn::SWD_FORM_GENERAL &&
+              SSN_SWD_FORM_WAVE == ssn::SWD_FORM_WAVE, "the header's macros are the library's constants");
+// the limits the three ssn_ens_swd_* entries share; 0 when none is passed
+static int ens_swd_limits(const char* name, int K, int B, int L) {
+    const char* what = K > SSN_ENS_SWD_MAX_MEMBERS ? "more than 2048 members"
+                       : B > SSN_SWD_MAX_BATCH ? "more than 4096 rows per member (keys and values are sorted in 48 KiB of LDS)"
+                       : L > SSN_W1_MAX_DIRECTIONS ? "more than 4096 directions" : nullptr;
+    if (!what) return 0;
+    g_last_error = std::string(name) + ": " + what;
+    return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+}
+int ssn_ens_swd_project_f32(const float* x, const float* y, const float* theta, int K, int B, int L, int D, float* px, float* py,
+                            void* stream) {
+    if (int err = ens_swd_limits("ssn_ens_swd_project_f32", K, B, L)) return err;
+    if (K < 0 || B < 0 || L < 0 || D < 0 || ((long)K * B * L > 0 && (!px || !py || (D > 0 && (!x || !y || !theta))))) {
+        g_last_error = "ssn_ens_swd_project_f32: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_ens_swd_project(x, y, theta, K, B, L, D, px, py, (hipStream_t)stream));
+    return 0;
+}
+int ssn_ens_swd_match_f32(const float* px, const float* py, const int* power, int K, int B, int L, int form, float* coef,
+                          double* loss_l, double* l0, void* stream) {
+    if (int err = ens_swd_limits("ssn_ens_swd_match_f32", K, B, L)) return err;
+    if (K < 0 || B < 0 || L < 0 || (K > 0 && !power)) {
+        g_last_error = "ssn_ens_swd_match_f32: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    ssn::SwdPowerBits bits{};
+    for (int k = 0; k < K; ++k) {
+        if (power[k] != 1 && power[k] != 2) {
+            g_last_error = "ssn_ens_swd_match_f32: a power other than 1 or 2";
+            return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+        }
+        if (power[k] == 2) bits.w[k >> 5] |= 1u << (k & 31);
+    }
+    if (form != SSN_SWD_FORM_AUTO && form != SSN_SWD_FORM_GENERAL && form != SSN_SWD_FORM_WAVE) {
+        g_last_error = "ssn_ens_swd_match_f32: unknown form";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if (form == SSN_SWD_FORM_WAVE && B > SSN_SWD_WAVE_MAX_BATCH) {
+        g_last_error = "ssn_ens_swd_match_f32: the wave form takes at most 64 rows per member";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if ((long)K * B * L > 0 && (!px || !py || !coef || !loss_l || !l0)) {
+        g_last_error = "ssn_ens_swd_match_f32: invalid argument (null pointer)";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    SSN_TRY(ssn::launch_ens_swd_match(px, py, bits, K, B, L, form, coef, loss_l, l0, (hipStream_t)stream));
+    return 0;
+}
+int ssn_ens_swd_backproject_f32(const float* coef, const float* theta, int K, int B, int L, int D, float* gx, void* stream) {
+    if (int err = ens_swd_limits("ssn_ens_swd_backproject_f32", K, B, L)) return err;
+    if (K < 0 || B < 0 || L < 0 || D < 0 || ((long)K * B * D > 0 && (!gx || (L > 0 && (!coef || !theta))))) {
+        g_last_error = "ssn_ens_swd_backproject_f32: invalid argument";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
+    if (L == 0) {                                             // (as the single-run entry: no direction, zeros)
+        if ((long)K * B * D > 0) SSN_TRY(hipMemsetAsync(gx, 0, (size_t)K * B * D * sizeof(float), (hipStream_t)stream));
+        return 0;
+    }
+    SSN_TRY(ssn::launch_ens_swd_backproject(coef, theta, K, B, L, D, gx, (hipStream_t)stream));
     return 0;
 }
 int ssn_build_w_table_f64(const double* z, const double* jds_table, double* W, int S, int B, int N, void* stream) {

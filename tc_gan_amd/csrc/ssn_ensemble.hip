@@ -14,7 +14,8 @@
 //   heterogeneous-input stimulus   stimulus_hetero_kernel (ssn_aux.hip) with V of the draw's member
 //
 // The record: one fp64 row of ssn_ens_record_doubles(D, P) per member -- [L0, m[D], s[D], dynamics_penalty, rate_penalty,
-// loss, new parameters[P], gradients[P]] -- is what the host reads back, once per step for the whole ensemble.
+// loss, new parameters[P], gradients[P]] -- is what the host reads back, once per step for the whole ensemble.  An ensemble whose
+// loss is not a function of moments (ssn_ens_swd.hip) has D = 0 in its record and hands the gradient assembly its L0 per member.
 #include <hip/hip_runtime.h>
 #include "ssn_host.h"
 
@@ -110,21 +111,26 @@ __global__ void __launch_bounds__(256) ens_jds_grad_kernel(const float* __restri
 }
 
 // grid (K): member k's flat gradient [dL/dV (nv), dL/dJ (4), dL/dD (4), dL/dS (4)] and its loss.  L0 is
-// moment_loss_sum_kernel's tree over the member's channels; the penalties are the means of the forward's per-draw rows over
+// moment_loss_sum_kernel's tree over the member's channels, or l0[k] where the caller has it; the penalties are the means of the forward's per-draw rows over
 // the member's draws, rounded to fp32 as the single run reads them; loss = L0 + dynamics_cost dyn + rate_cost rate.
 __global__ void __launch_bounds__(256) ens_gen_grads_kernel(EnsGradsArgs a) {
     __shared__ double red[256];
     const int k = blockIdx.x;
     const int P = a.nv + 12;
     double* rec = a.rec + (size_t)k * a.rstride;
-    const double* dm = a.data_moments + (size_t)k * 2 * a.D;
-    const double* wk = a.weights + (size_t)k * 2 * a.D;
-    double t = 0.0;
-    for (int d = threadIdx.x; d < a.D; d += 256) {
-        const double em = rec[1 + d] - dm[d], es = rec[1 + a.D + d] - dm[a.D + d];
-        t += wk[d] * em * em + wk[a.D + d] * es * es;
+    double L0;
+    if (a.l0) {                                       // (the loss kernels formed it: ssn_ens_gen_grads_l0_f32)
+        L0 = a.l0[k];
+    } else {
+        const double* dm = a.data_moments + (size_t)k * 2 * a.D;
+        const double* wk = a.weights + (size_t)k * 2 * a.D;
+        double t = 0.0;
+        for (int d = threadIdx.x; d < a.D; d += 256) {
+            const double em = rec[1 + d] - dm[d], es = rec[1 + a.D + d] - dm[a.D + d];
+            t += wk[d] * em * em + wk[a.D + d] * es * es;
+        }
+        L0 = ens_block_sum(t, red) / (2.0 * a.D);
     }
-    const double L0 = ens_block_sum(t, red) / (2.0 * a.D);
     const long per_member = (long)a.B * a.NB * a.M;
     const size_t row0 = (size_t)k * per_member;
     double sd = 0.0, sr = 0.0;

@@ -116,6 +116,7 @@ struct EnsGradsArgs {
     const double *data_moments, *weights, *costs;   // [K][2][D], [K][2][D], [K][2] = (dynamics_cost, rate_cost)
     float* grads;                        // [K][nv + 12]
     double* rec; int rstride;            // record rows
+    const double* l0;                    // null: L0 from the moments in the record; else L0 of member k is l0[k] and D == 0
 };
 struct EnsApplyArgs {
     int K, P, kind;
@@ -402,6 +403,17 @@ hipError_t launch_project_rows(const float* x, long rows, int ldx, int C, const 
 // ssn_swd.hip (sliced Wasserstein loss of a minibatch: rank matching per direction, coefficients carried back to the rows)
 hipError_t launch_swd_match(const float* px, const float* py, int B, int L, int power, float* coef, double* loss_l, hipStream_t st);
 hipError_t launch_swd_backproject(const float* coef, const float* theta, int B, int L, int D, float* gx, hipStream_t st);
+
+// ssn_ens_swd.hip (the sliced Wasserstein loss of K members: member k owns rows [k B, (k + 1) B), its theta[k][L][D], its power)
+constexpr int SWD_ENS_MAX_MEMBERS = 2048;
+struct SwdPowerBits { uint32_t w[SWD_ENS_MAX_MEMBERS / 32]; };          // bit k set: member k has power 2, else 1
+constexpr int SWD_FORM_AUTO = 0, SWD_FORM_GENERAL = 1, SWD_FORM_WAVE = 2;
+constexpr int SWD_WAVE_MAX_BATCH = 64;   // the wave form sorts one column in the registers of one wave64
+hipError_t launch_ens_swd_project(const float* x, const float* y, const float* theta, int K, int B, int L, int D, float* px, float* py,
+                                  hipStream_t st);
+hipError_t launch_ens_swd_match(const float* px, const float* py, const SwdPowerBits& powers, int K, int B, int L, int form, float* coef,
+                                double* loss_l, double* l0, hipStream_t st);
+hipError_t launch_ens_swd_backproject(const float* coef, const float* theta, int K, int B, int L, int D, float* gx, hipStream_t st);
 
 // ssn_fpsample.hip (rejection sampling of fixed points on the device: W table in fp64, verdict per (set, candidate), selection)
 hipError_t launch_build_w_table_f64(const double* z, const double* table, double* W, int A, int B, int N, hipStream_t st);

@@ -18,122 +18,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ssn_host.h"
+#include "ssn_swd_dev.h"
 
 namespace ssn {
 
-// the float as an unsigned word whose order is the float order (finite values and the infinities); -0 is taken as +0
-__device__ __forceinline__ uint32_t swd_ordered(float v) {
-    const uint32_t u = v == 0.f ? 0u : __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float swd_unordered(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
-}
-
-// grid (L); dynamic LDS: P keys of 8 bytes, then P floats.  px[B][L], py[B][L]; coef[B][L]; loss_l[L]; inv = 1 / (L B)
+// grid (L); dynamic LDS: P keys of 8 bytes, then P floats: swd_match_body (ssn_swd_dev.h) on direction blockIdx.x
 __global__ void __launch_bounds__(256) swd_match_kernel(const float* __restrict__ px, const float* __restrict__ py, int B, int L,
                                                         int P, int power, double inv, float* __restrict__ coef,
                                                         double* __restrict__ loss_l) {
-    extern __shared__ unsigned long long swd_lds[];
-    __shared__ double red[4];
-    __shared__ int bad;
-    unsigned long long* kx = swd_lds;
-    float* sy = reinterpret_cast<float*>(swd_lds + P);
-    const int l = blockIdx.x;
-    const float inf = __builtin_huge_valf();
-    if (threadIdx.x == 0) bad = 0;
-    __syncthreads();
-    bool mine = false;
-    for (int i = threadIdx.x; i < P; i += 256) {
-        unsigned long long key = ~0ull;                       // (above the key of +inf: the padding sorts last)
-        float v = inf;
-        if (i < B) {
-            const float u = px[(size_t)i * L + l];
-            v = py[(size_t)i * L + l];
-            mine |= !(fabsf(u) < inf) || !(fabsf(v) < inf);
-            key = ((unsigned long long)swd_ordered(u) << 32) | (unsigned)i;
-        }
-        kx[i] = key;
-        sy[i] = v;
-    }
-    if (mine) bad = 1;
-    __syncthreads();
-    if (bad) {                                                // NaN, +inf or -inf in either column: nothing is sorted
-        const float nan = __builtin_nanf("");
-        for (int i = threadIdx.x; i < B; i += 256) coef[(size_t)i * L + l] = nan;
-        if (threadIdx.x == 0) loss_l[l] = __builtin_nan("");
-        return;
-    }
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j >= 1; j >>= 1) {
-            for (int p = threadIdx.x; p < (P >> 1); p += 256) {
-                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-                const bool up = (i & k) == 0;
-                const unsigned long long a = kx[i], b = kx[i + j];
-                if ((a > b) == up) { kx[i] = b; kx[i + j] = a; }
-                const float c = sy[i], d = sy[i + j];
-                if ((c > d) == up) { sy[i] = d; sy[i + j] = c; }
-            }
-            __syncthreads();
-        }
-    }
-    double sum = 0.0;
-    for (int i = threadIdx.x; i < B; i += 256) {
-        const unsigned long long key = kx[i];
-        const int b = (int)(unsigned)key;
-        const double d = (double)swd_unordered((uint32_t)(key >> 32)) - (double)sy[i];
-        double term, cf;
-        {
-#pragma clang fp contract(off)
-            if (power == 1) {
-                term = fabs(d);
-                cf = (d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0)) * inv;
-            } else {
-                term = d * d;                                 // (rounded on its own: no FMA into the sum)
-                cf = (2.0 * d) * inv;
-            }
-        }
-        sum += term;
-        if (b < B) coef[(size_t)b * L + l] = (float)cf;       // (the first B ranks are rows: the padding sorts behind them)
-    }
-    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) sum += red[w];
-        loss_l[l] = sum / (double)B;
-    }
+    swd_match_body(px, py, B, L, P, power, inv, coef, loss_l, blockIdx.x);
 }
 
-constexpr int BP_ROWS = 16;                                   // rows of a workgroup
-constexpr int BP_COLS = 16;                                   // columns of a workgroup
-constexpr int BP_DIRS = 64;                                   // directions staged at a time
-
-// grid (column tiles, row tiles): 256 threads = 16 rows x 16 columns.  coef[B][L], theta[L][D], gx[B][D]
+// grid (column tiles, row tiles): swd_backproject_body (ssn_swd_dev.h)
 __global__ void __launch_bounds__(256) swd_backproject_kernel(const float* __restrict__ coef, const float* __restrict__ theta,
                                                               int B, int L, int D, float* __restrict__ gx) {
-    __shared__ float sc[BP_ROWS][BP_DIRS + 1];
-    __shared__ float sth[BP_DIRS][BP_COLS];
-    const int cc = threadIdx.x & (BP_COLS - 1), rr = threadIdx.x >> 4;
-    const int c0 = blockIdx.x * BP_COLS;
-    const int tiles = (B + BP_ROWS - 1) / BP_ROWS;
-    for (int tile = blockIdx.y; tile < tiles; tile += gridDim.y) {
-        const int r0 = tile * BP_ROWS;
-        double acc = 0.0;
-        for (int l0 = 0; l0 < L; l0 += BP_DIRS) {
-            const int ln = min(BP_DIRS, L - l0);
-            __syncthreads();                                  // the tile before this one has been read
-            for (int e = threadIdx.x; e < BP_ROWS * BP_DIRS; e += 256) {
-                const int row = e / BP_DIRS, ll = e - row * BP_DIRS;
-                sc[row][ll] = (ll < ln && r0 + row < B) ? coef[(size_t)(r0 + row) * L + l0 + ll] : 0.f;
-                const int tl = e / BP_COLS, tcol = e - tl * BP_COLS;
-                sth[tl][tcol] = (tl < ln && c0 + tcol < D) ? theta[(size_t)(l0 + tl) * D + c0 + tcol] : 0.f;
-            }
-            __syncthreads();
-            for (int ll = 0; ll < ln; ++ll) acc = __builtin_fma((double)sc[rr][ll], (double)sth[ll][cc], acc);
-        }
-        if (r0 + rr < B && c0 + cc < D) gx[(size_t)(r0 + rr) * D + c0 + cc] = (float)acc;
-    }
+    swd_backproject_body(coef, theta, B, L, D, gx, blockIdx.x * BP_COLS, blockIdx.y, gridDim.y);
 }
 
 hipError_t launch_swd_match(const float* px, const float* py, int B, int L, int power, float* coef, double* loss_l, hipStream_t st) {

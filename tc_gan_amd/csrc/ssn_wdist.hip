@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ssn_host.h"
+#include "ssn_swd_dev.h"
 
 namespace ssn {
 
@@ -115,47 +116,10 @@ __global__ void __launch_bounds__(256) ks_w1_columns_kernel(const float* __restr
     }
 }
 
-constexpr int PJ_DIRS = 32;                                   // directions of a workgroup
-constexpr int PJ_ROWS = 32;                                   // rows of a tile: 8 row slots x 4 rows per thread
-constexpr int PJ_COLS = 128;                                  // columns staged at a time
-static_assert(PJ_DIRS == PJ_ROWS, "one staging loop fills both tiles");
-
-// grid (direction tiles, row tiles up to a cap): 256 threads = 8 row slots x 32 directions.  x[rows][ldx] (the first C of a row
-// are used), theta[L][C], out[rows][L]
+// grid (direction tiles, row tiles up to a cap): project_rows_body (ssn_swd_dev.h) on one sample
 __global__ void __launch_bounds__(256) project_rows_kernel(const float* __restrict__ x, long rows, int ldx, int C,
                                                            const float* __restrict__ theta, int L, float* __restrict__ out) {
-    __shared__ float sth[PJ_DIRS][PJ_COLS + 1];
-    __shared__ float sxr[PJ_ROWS][PJ_COLS];
-    const int ll = threadIdx.x & (PJ_DIRS - 1), slot = threadIdx.x >> 5;
-    const int l0 = blockIdx.x * PJ_DIRS;
-    const long tiles = (rows + PJ_ROWS - 1) / PJ_ROWS;
-    for (long tile = blockIdx.y; tile < tiles; tile += gridDim.y) {
-        const long r0 = tile * PJ_ROWS;
-        double acc[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int c0 = 0; c0 < C; c0 += PJ_COLS) {
-            const int cn = min(PJ_COLS, C - c0);
-            __syncthreads();                                  // the tile before this one has been read
-            for (int e = threadIdx.x; e < PJ_DIRS * PJ_COLS; e += 256) {
-                const int row = e / PJ_COLS, col = e - row * PJ_COLS;
-                const bool in_cols = col < cn;
-                sth[row][col] = (in_cols && l0 + row < L) ? theta[(size_t)(l0 + row) * C + c0 + col] : 0.f;
-                sxr[row][col] = (in_cols && r0 + row < rows) ? x[(size_t)(r0 + row) * ldx + c0 + col] : 0.f;
-            }
-            __syncthreads();
-            for (int cc = 0; cc < cn; ++cc) {
-                const double th = (double)sth[ll][cc];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[k] = __builtin_fma((double)sxr[slot + 8 * k][cc], th, acc[k]);
-            }
-        }
-        if (l0 + ll < L) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const long r = r0 + slot + 8 * k;
-                if (r < rows) out[(size_t)r * L + l0 + ll] = (float)acc[k];
-            }
-        }
-    }
+    project_rows_body(x, rows, ldx, C, theta, L, out, blockIdx.x * PJ_DIRS, blockIdx.y, gridDim.y);
 }
 
 hipError_t launch_ks_w1_columns(const float* x, const float* t, const int* m, int S, int B, int C, int T, int* n_out,

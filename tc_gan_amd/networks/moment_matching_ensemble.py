@@ -12,6 +12,9 @@ share the launches of a generator step: member k owns the draws [k B, (k + 1) B)
     (`ssn_ens_apply_f32`): segmented kernels, one launch each, sums over each member's own rows;
   * ONE read of the record buffer (csrc/ssn_ensemble.hip) for all members.
 
+The part of a step that does not depend on the loss is `EnsembleGeneratorStep`, which the ensemble of sliced Wasserstein runs
+(networks/sliced_wasserstein_ensemble.py) shares; `EnsembleMomentMatcher` adds the moment loss and its gradient assembly.
+
 With a fixed generator kernel every draw is computed independently of the rest of the batch, so a member's step is its single
 run's step; the sums over a member's draws may add in another order (fp64).  `auto` is resolved once, for the ensemble's batch
 of K B draws (`resolve_gen_kernel`), and every member records the kernel that ran.
@@ -49,8 +52,8 @@ class MemberOptionError(ValueError):
     pass
 
 
-def validate_member_overrides(member_overrides):
-    """A list of dicts, one per member: every key must be one a member may set (`MEMBER_KEYS`); a shared key or an unknown
+def validate_member_overrides(member_overrides, member_keys=MEMBER_KEYS, shared_keys=SHARED_KEYS):
+    """A list of dicts, one per member: every key must be one a member may set (`member_keys`); a shared key or an unknown
     one is refused with an error that names it.  `z_device_seed` is given for all members or for none."""
     if not isinstance(member_overrides, (list, tuple)) or not member_overrides:
         raise MemberOptionError('members: a non-empty list of dicts of per-member options is needed')
@@ -58,10 +61,10 @@ def validate_member_overrides(member_overrides):
         if not isinstance(over, dict):
             raise MemberOptionError('member {}: a dict of options is needed, got {!r}'.format(i, over))
         for key in over:
-            if key in SHARED_KEYS:
+            if key in shared_keys:
                 raise MemberOptionError('member {}: {!r} is shared by all members of an ensemble and may not be set per member'
                                         .format(i, key))
-            if key not in MEMBER_KEYS:
+            if key not in member_keys:
                 raise MemberOptionError('member {}: unknown option {!r}'.format(i, key))
     with_seed = [('z_device_seed' in over and over['z_device_seed'] is not None) for over in member_overrides]
     if any(with_seed) and not all(with_seed):
@@ -107,10 +110,16 @@ def _jds16(J, D, S):
                            one / (two * s * s), one / (s * s * s)]).astype(np.float32)
 
 
-class EnsembleMomentMatcher(object):
-    """K `BPTTMomentMatcher`s (`members`) trained by one loop.  `learning()` yields, per step, the list of one `Namespace` per
-    ACTIVE member (fields of a single run's `info`: step, loss, rate_penalty, dynamics_penalty, gen_moments, train_time, plus
-    `member`, the member's index).  `remove(i)` takes member i out of the later steps (its run has ended)."""
+class EnsembleGeneratorStep(object):
+    """What an ensemble of K critic-free BPTT trainers (`members`, each a `GeneratorStepTrainer`) does per step whatever its loss
+    is: the draw, the stimulus, the forward over the K B draws, the scatter of the loss gradient `gx`, the adjoint sweep per run
+    of equal costs, dL/dW, `ssn_ens_jds_grad_f32`, the update (`ssn_ens_apply_f32`), the ONE read of the record buffer, and
+    `remove`.  A subclass gives two hooks -- `_loss` (tuning curves -> gx, and what it writes to the record) and `_assemble`
+    (the gradient assembly that puts L0, the penalties and the loss into the record) -- and says what its record holds:
+    `record_moments` (the D of `ssn_ens_record_doubles`), `_record_extra` (doubles appended to a row), `_member_state`
+    (per-member device arrays rebuilt when a member leaves) and `_info_fields` (a member's row -> the fields of its `info`).
+    `learning()` yields, per step, the list of one `Namespace` per ACTIVE member; `remove(i)` takes member i out of the later
+    steps (its run has ended)."""
 
     def __init__(self, members, gen_kernel, dynamics_costs, rate_costs, rests=None):
         self.members = list(members)
@@ -125,8 +134,9 @@ class EnsembleMomentMatcher(object):
         self.heteroin = g0.heteroin
         self.nv = 0 if not self.heteroin else (2 if g0.ssn_type == 'heteroin' else 1)
         self.P = self.nv + 12
-        self.D = self.members[0].num_mom_conds
-        self.R = int(libssnode.ssn_ens_record_doubles(self.D, self.P))
+        self.D = self.record_moments()
+        self.R0 = int(libssnode.ssn_ens_record_doubles(self.D, self.P))
+        self.R = self.R0 + self._record_extra()
         self._state = None
         self._inputs = {}
         self.step_count = 0
@@ -150,7 +160,6 @@ class EnsembleMomentMatcher(object):
         st = dict(p=torch.as_tensor(params, **dev).contiguous(),
                   clip_lo=torch.as_tensor(np.asarray(lo, dtype=np.float32), **dev).contiguous(),
                   clip_hi=torch.as_tensor(np.asarray(hi, dtype=np.float32), **dev).contiguous(),
-                  dm=torch.stack([mm._dm for mm in mms]).contiguous(), w=torch.stack([mm._w for mm in mms]).contiguous(),
                   costs=torch.as_tensor(np.asarray([[self.dynamics_costs[i], self.rate_costs[i]] for i in self.active]),
                                         dtype=torch.float64, **dev).contiguous())
         if self._state is not None and self._state['index'] is not None:
@@ -160,6 +169,7 @@ class EnsembleMomentMatcher(object):
         else:
             st['s1'], st['s2'] = torch.zeros_like(st['p']), torch.zeros_like(st['p'])
         st['index'] = list(self.active)
+        st.update(self._member_state(mms))
         self._state = st
 
     def remove(self, i):
@@ -269,12 +279,9 @@ class EnsembleMomentMatcher(object):
         tc, _, probes = gen0._probe(ta3[0])
         tc = tc.contiguous()
         self.last_tuning_curves = tc
-        # moment loss and its gradient, member by member
+        # the loss and its gradient, member by member
         rec = torch.empty((K, R), device='cuda', dtype=torch.float64)
-        sums = torch.empty((K, 2, D), device='cuda', dtype=torch.float64)
-        gx = torch.empty_like(tc)
-        clib.check(libssnode.ssn_ens_moments_f32(tc.data_ptr(), K, B, D, sums.data_ptr(), st['dm'].data_ptr(), st['w'].data_ptr(),
-                                                 gx.data_ptr(), rec.data_ptr(), R, stream), 'ssn_ens_moments_f32')
+        gx = self._loss(tc, rec, K)
         g_ta = torch.zeros((K * B, NB, M), **f32)
         g_ta[:, :, probes] = gx.reshape(K * B, NB, -1)
         # adjoint sweep: one launch per run of adjacent members with equal costs
@@ -300,9 +307,8 @@ class EnsembleMomentMatcher(object):
                           g_ext=g_ext.data_ptr() if self.heteroin else None, ext_base=ext_base.data_ptr() if self.heteroin else None,
                           zin=zin.data_ptr() if self.heteroin else None, dyn_row=ta3[1].data_ptr(), rate_row=ta3[2].data_ptr(),
                           scale_dyn=(1.0 / n_dyn) if n_dyn > 0 else float('nan'), scale_rate=1.0 / n_rate,
-                          data_moments=st['dm'].data_ptr(), weights=st['w'].data_ptr(), costs=st['costs'].data_ptr(),
-                          grads=grads.data_ptr(), rec=rec.data_ptr(), rstride=R)
-        clib.check(libssnode.ssn_ens_gen_grads_f32(ctypes.byref(a), stream), 'ssn_ens_gen_grads_f32')
+                          costs=st['costs'].data_ptr(), grads=grads.data_ptr(), rec=rec.data_ptr(), rstride=R)
+        self._assemble(a)
         # the optimizer over all members' parameter vectors
         t = step + 1
         hyp = np.zeros((K, 8), dtype=np.float32)
@@ -332,8 +338,8 @@ class EnsembleMomentMatcher(object):
             for u in mm.gen_updaters.values():
                 u.step = t
             infos.append(Namespace(step=step, member=i, loss=float(row[3 + 2 * D]), dynamics_penalty=float(row[1 + 2 * D]),
-                                   rate_penalty=float(row[2 + 2 * D]), gen_moments=row[1:1 + 2 * D].reshape(2, D).copy(),
-                                   gradients=row[off + P:off + 2 * P].copy()))
+                                   rate_penalty=float(row[2 + 2 * D]), gradients=row[off + P:off + 2 * P].copy(),
+                                   **self._info_fields(row)))
         return infos
 
     def prepare(self):
@@ -345,15 +351,68 @@ class EnsembleMomentMatcher(object):
                 return
             yield self.train_step(step)
 
+    # -- what a loss gives -----------------------------------------------------------------------------------------------------
+    def record_moments(self):
+        """The D of `ssn_ens_record_doubles(D, P)`: the moments a record row holds between L0 and the penalties."""
+        raise NotImplementedError
 
-def ensemble_from_member_configs(configs):
-    """The `EnsembleMomentMatcher` of fully resolved member configs (each what `make_moment_matcher` takes, all naming the
-    same explicit `gen_kernel`)."""
+    def _record_extra(self):
+        """Doubles a record row holds behind the `ssn_ens_record_doubles(D, P)` of the library."""
+        return 0
+
+    def _member_state(self, mms):
+        """dict of device arrays over the active members `mms`, rebuilt whenever a member leaves (into `self._state`)."""
+        return {}
+
+    def _loss(self, tc, rec, K):
+        """tc (K B, D) device float32, the tuning curves of the K active members -> gx of the same shape; may write to `rec`."""
+        raise NotImplementedError
+
+    def _assemble(self, a):
+        """`a`: the `clib.EnsGrads` of the step without the loss's own fields.  Launches the gradient assembly."""
+        raise NotImplementedError
+
+    def _info_fields(self, row):
+        """The loss's own fields of a member's `info` from its record row (numpy fp64)."""
+        return {}
+
+
+class EnsembleMomentMatcher(EnsembleGeneratorStep):
+    """K `BPTTMomentMatcher`s (`members`) trained by one loop (`EnsembleGeneratorStep`).  The fields of a member's `info` are a
+    single run's: step, loss, rate_penalty, dynamics_penalty, gen_moments, train_time, plus `member`, the member's index."""
+
+    def record_moments(self):
+        return self.members[0].num_mom_conds
+
+    def _member_state(self, mms):
+        return dict(dm=torch.stack([mm._dm for mm in mms]).contiguous(), w=torch.stack([mm._w for mm in mms]).contiguous())
+
+    def _loss(self, tc, rec, K):
+        st, B, D = self._state, self.B, self.D
+        sums = torch.empty((K, 2, D), device='cuda', dtype=torch.float64)
+        gx = torch.empty_like(tc)
+        clib.check(libssnode.ssn_ens_moments_f32(tc.data_ptr(), K, B, D, sums.data_ptr(), st['dm'].data_ptr(), st['w'].data_ptr(),
+                                                 gx.data_ptr(), rec.data_ptr(), self.R, clib.stream_ptr()), 'ssn_ens_moments_f32')
+        return gx
+
+    def _assemble(self, a):
+        a.data_moments, a.weights = self._state['dm'].data_ptr(), self._state['w'].data_ptr()
+        clib.check(libssnode.ssn_ens_gen_grads_f32(ctypes.byref(a), clib.stream_ptr()), 'ssn_ens_gen_grads_f32')
+
+    def _info_fields(self, row):
+        D = self.D
+        return dict(gen_moments=row[1:1 + 2 * D].reshape(2, D).copy())
+
+
+def members_from_configs(configs, make_member):
+    """One trainer per fully resolved member config through `make_member(config) -> (trainer, unconsumed config)`, with what an
+    ensemble refuses: several ranks, z drawn on the host, a generator that is not float32, members on different kernels or on
+    none by name.  Returns (members, rests, dynamics costs, rate costs, the kernel)."""
     members, rests, dcosts, rcosts = [], [], [], []
     for cfg in configs:
         if cfg.get('gen_dtype', 'float32') != 'float32':
             raise ValueError('ensembles run the float32 generator only')
-        mm, rest = make_moment_matcher(dict(cfg))
+        mm, rest = make_member(dict(cfg))
         if mm.reducer.on:
             raise ValueError('ensembles run in one process (no data-parallel ranks)')
         if mm.gen.z_host_draw:
@@ -365,7 +424,14 @@ def ensemble_from_member_configs(configs):
     kernels = set(mm.gen.gen_kernel for mm in members)
     if len(kernels) != 1 or 'auto' in kernels:
         raise ValueError('the members of an ensemble run one explicit generator kernel, got {}'.format(sorted(kernels)))
-    return EnsembleMomentMatcher(members, kernels.pop(), dcosts, rcosts, rests=rests)
+    return members, rests, dcosts, rcosts, kernels.pop()
+
+
+def ensemble_from_member_configs(configs):
+    """The `EnsembleMomentMatcher` of fully resolved member configs (each what `make_moment_matcher` takes, all naming the
+    same explicit `gen_kernel`)."""
+    members, rests, dcosts, rcosts, kernel = members_from_configs(configs, make_moment_matcher)
+    return EnsembleMomentMatcher(members, kernel, dcosts, rcosts, rests=rests)
 
 
 def make_moment_matcher_ensemble(shared_config, member_overrides):

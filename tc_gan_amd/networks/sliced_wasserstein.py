@@ -77,7 +77,8 @@ class BPTTSlicedWasserstein(GeneratorStepTrainer):
         kwargs.setdefault('seed', self.minibatch_rng)
         data = np.ascontiguousarray(data, dtype='float32')
         self.truth = torch.as_tensor(data).to('cuda')
-        rows = random_minibatches(self.gen.batchsize, np.arange(len(data)), **kwargs)
+        # (an ensemble takes the row indices themselves from `minibatch_rows`, one gather for all its members)
+        self.minibatch_rows = rows = random_minibatches(self.gen.batchsize, np.arange(len(data)), **kwargs)
         self.dataset = (self.truth[torch.as_tensor(idx).to('cuda')] for idx in rows)
 
     def next_minibatch(self):

@@ -35,10 +35,11 @@ def make_parser():
     return parser
 
 
-def member_run_configs(run_config, member_overrides):
+def member_run_configs(run_config, member_overrides, validate=validate_member_overrides):
     """The run_config of every member as a single ``bptt_moments`` run with the same options would write it to info.json: the
-    shared options with the member's over them, pre-processed (bptt_wgan.preprocess), and gen_kernel resolved for the ensemble."""
-    overrides = validate_member_overrides(member_overrides)
+    shared options with the member's over them, pre-processed (bptt_wgan.preprocess), and gen_kernel resolved for the ensemble.
+    `validate`: the ensemble's check of the members' keys."""
+    overrides = validate(member_overrides)
     configs = []
     for over in overrides:
         cfg = copy.deepcopy(run_config)
@@ -51,18 +52,20 @@ def member_run_configs(run_config, member_overrides):
     return overrides, configs
 
 
-def prepare_datastores(run_config, member_overrides, script_file=__file__):
+def prepare_datastores(run_config, member_overrides, script_file=__file__, template='logfiles/BPTT_MM_ensemble_{lam}',
+                       module=__name__, configs_of=None):
     """Merge --load-config, resolve the members and write DATASTORE/members.json and DATASTORE/<i>/info.json (no GPU needed).
-    Returns (datastore directory, member directories, member configs)."""
+    Returns (datastore directory, member directories, member configs).  Another ensemble script gives its own default
+    `template`, its `module` name and `configs_of`, its `member_run_configs`."""
     run_config = dict(run_config)
     load_config = run_config.pop('load_config', None)
     if load_config:
         run_config.update(execution.load_any_file(load_config))
     datastore = run_config.pop('datastore', None)
-    template = run_config.pop('datastore_template', 'logfiles/BPTT_MM_ensemble_{lam}')
+    template = run_config.pop('datastore_template', template)
     extra_info = dict(n_bandwidths=run_config['n_bandwidths'], load_gen_param=run_config['load_gen_param'], data_version=1,
-                      script_file=script_file, learn='{}.{}'.format(__name__, 'learn'), init_driver='{}.{}'.format(__name__, 'learn'))
-    overrides, configs = member_run_configs(run_config, member_overrides)
+                      script_file=script_file, learn='{}.{}'.format(module, 'learn'), init_driver='{}.{}'.format(module, 'learn'))
+    overrides, configs = (configs_of or member_run_configs)(run_config, member_overrides)
     if not datastore:
         datastore = execution.format_datastore(template, configs[0])
     execution.makedirs_exist_ok(datastore)
