@@ -22,6 +22,11 @@ int fail(hipError_t e, const char* where) {
     g_last_error = std::string(where) + ": " + hipGetErrorString(e);
     return SSN_ERR_BASE + (int)e;
 }
+// the entry point `fn` refuses its arguments: "fn: why" is the error string, hipErrorInvalidValue the code
+int refuse(const char* fn, const char* why) {
+    g_last_error = std::string(fn) + ": " + why;
+    return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+}
 #define SSN_TRY(expr)                                     \
     do {                                                  \
         hipError_t e__ = (expr);                          \
@@ -469,7 +474,6 @@ ssn::IoConsts<T> gen_io_consts(const ssn_gen_params& g) {
 // gen_forward_path and gen_backward_path are the ONLY places that decide which kernels run a generator pass.  Both validate all
 // but the pointers, fill the arg struct and answer in the numbering of ssn_gen_forward_variant (1 tile / stream, 2 / 3 fp32 MFMA,
 // 4 - 7 fp16-split MFMA, 8 two draws per workgroup), or refuse: >= SSN_ERR_BASE with the error string set.
-int gen_refuse(const char* who, const char* why) { g_last_error = std::string(who) + ": " + why; return SSN_ERR_BASE + (int)hipErrorInvalidValue; }
 const char* const kGenInvalid = "invalid argument, unsupported size or kernel not one of 0 (automatic), 1 (tile), 2 / 3 (fp32 MFMA), "
                                 "4 / 5 / 6 (fp16-split), 8 (two-draw)";
 const char* const kGenMfma = "the MFMA kernels need fp32, NB >= 4, 2N <= 208 and NB T 2N < 2^29";
@@ -493,16 +497,16 @@ int gen_groups(int kernel, int B, int NB) {
 // save: the call stores trajectory and f' (their stores address one draw's block with 32-bit byte offsets)
 template <typename T>
 int gen_forward_path(ssn::GenFwdArgs<T>& a, int B, int NB, int M, bool save, const ssn_gen_params* g) {
-    if (!gen_call_ok<T>(M, g) || g->io_type < 0 || g->io_type > 2) return gen_refuse("ssn_gen_forward", kGenInvalid);
+    if (!gen_call_ok<T>(M, g) || g->io_type < 0 || g->io_type > 2) return refuse("ssn_gen_forward", kGenInvalid);
     gen_fill<T>(a, B, NB, M, *g);
     a.io = gen_io_consts<T>(*g);
     if constexpr (sizeof(T) == 4) {
         const int k = g->kernel;
         const bool mfma_ok = ssn::gen_mfma_supported(M, NB) && (!save || (long)NB * g->seqlen * M < (1L << 29));
         const bool split_ok = mfma_ok && ssn::gen_split_rshift(a) >= 0;
-        if (k >= 2 && !mfma_ok) return gen_refuse("ssn_gen_forward", kGenMfma);
+        if (k >= 2 && !mfma_ok) return refuse("ssn_gen_forward", kGenMfma);
         if (k >= 4 && !split_ok)
-            return gen_refuse("ssn_gen_forward", "the fp16-split MFMA kernels need asym_tanh, rate_hard_bound < 3e4 and dt <= tau");
+            return refuse("ssn_gen_forward", "the fp16-split MFMA kernels need asym_tanh, rate_hard_bound < 3e4 and dt <= tau");
         const int groups = mfma_ok ? gen_groups(k, B, NB) : 0;
         if (!groups) return 1;
         a.mfma_groups = groups;
@@ -519,12 +523,12 @@ int gen_forward_path(ssn::GenFwdArgs<T>& a, int B, int NB, int M, bool save, con
 // split or two-draw sweep behind an fp32 MFMA forward.
 template <typename T>
 int gen_backward_path(ssn::GenBwdArgs<T>& a, int B, int NB, int M, const ssn_gen_params* g) {
-    if (!gen_call_ok<T>(M, g)) return gen_refuse("ssn_gen_backward", kGenInvalid);
+    if (!gen_call_ok<T>(M, g)) return refuse("ssn_gen_backward", kGenInvalid);
     gen_fill<T>(a, B, NB, M, *g);
     if constexpr (sizeof(T) == 4) {
         const int k = g->kernel;
         const bool mfma_ok = ssn::gen_mfma_supported(M, NB) && (long)NB * g->seqlen * M < (1L << 29);
-        if (k >= 2 && !mfma_ok) return gen_refuse("ssn_gen_backward", kGenMfma);
+        if (k >= 2 && !mfma_ok) return refuse("ssn_gen_backward", kGenMfma);
         const int groups = mfma_ok ? gen_groups(k, B, NB) : 0;
         if (!groups) return 1;
         a.mfma_groups = groups;
@@ -540,7 +544,7 @@ int gen_forward_impl(const T* W, const T* ext, T* time_avg, T* dyn_row, T* rate_
                      int M, const ssn_gen_params* g, void* stream) {
     if (B == 0 || NB == 0) return 0;
     if (!W || !ext || !time_avg || !dyn_row || !rate_row || (traj == nullptr) != (df == nullptr))
-        return gen_refuse("ssn_gen_forward", kGenInvalid);
+        return refuse("ssn_gen_forward", kGenInvalid);
     ssn::GenFwdArgs<T> a;
     a.W = W; a.ext = ext; a.time_avg = time_avg; a.dyn_row = dyn_row; a.rate_row = rate_row; a.traj = traj; a.df = df;
     const int variant = gen_forward_path(a, B, NB, M, traj != nullptr, g);
@@ -560,7 +564,7 @@ int gen_backward_impl(const T* W, const T* traj, T* delta, const T* gta, T* g_ex
                       int NB, int M, const ssn_gen_params* g, void* stream, float* dmax = nullptr, int* tracked = nullptr) {
     if (tracked) *tracked = 0;
     if (B == 0 || NB == 0) return 0;
-    if (!W || !traj || !delta || !gta) return gen_refuse("ssn_gen_backward", kGenInvalid);
+    if (!W || !traj || !delta || !gta) return refuse("ssn_gen_backward", kGenInvalid);
     ssn::GenBwdArgs<T> a;
     a.W = W; a.traj = traj; a.delta = delta; a.g_time_avg = gta; a.g_ext = g_ext; a.c_dyn = (T)c_dyn; a.c_rate = (T)c_rate;
     const int variant = gen_backward_path(a, B, NB, M, g);
@@ -664,13 +668,9 @@ int critic_net_accuracy_forwards(const CriticSpec& n, const float* xg, const flo
 
 // One helper per family of entry points (include/ssnode_mi355x.h): the family's arguments as a CriticSpec, or a refusal under
 // the name `fn` of the entry point that was called.  What every family refuses is what ssn::critic_layout refuses.
-int critic_refuse(const char* fn, const char* why) {
-    g_last_error = std::string(fn) + ": " + why;
-    return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-}
 int checked_spec(const char* fn, const CriticSpec& s) {
     ssn::CriticLayout lay;
-    return ssn::critic_layout(s, lay) ? 0 : critic_refuse(fn, "invalid layer flags / activation / slope, or more than 8 layers");
+    return ssn::critic_layout(s, lay) ? 0 : refuse(fn, "invalid layer flags / activation / slope, or more than 8 layers");
 }
 // -- norm: rectify, per-layer normalisation flags 0 / 1 -- and, for the accuracy and the one-call step, a slope next to plain
 //    layers (a slope next to a normalisation is a critic in its general form: the _act entry points)
@@ -679,10 +679,10 @@ int norm_spec(const char* fn, const float* params, const int* dims, const int* l
     bool norm = false;
     for (int l = 0; layer_norm && l < nlayers; ++l) {
         if (layer_norm[l] != 0 && layer_norm[l] != 1)
-            return critic_refuse(fn, "layer_norm flags are 0 / 1 (scaled layers: the _act entry points)");
+            return refuse(fn, "layer_norm flags are 0 / 1 (scaled layers: the _act entry points)");
         norm = norm || layer_norm[l] != 0;
     }
-    if (leak != 0.f && norm) return critic_refuse(fn, "leak with layer-normalised layers (that critic: the _act entry points)");
+    if (leak != 0.f && norm) return refuse(fn, "leak with layer-normalised layers (that critic: the _act entry points)");
     s = CriticSpec{params, dims, layer_norm, nlayers, 0, leak, hide_cell_type, precision == 0};
     return checked_spec(fn, s);
 }
@@ -700,7 +700,7 @@ int plain_spec(const char* fn, const float* params, const int* dims, int nlayers
 int act_spec(const char* fn, const float* params, const int* dims, const int* layer_flags, int nlayers, int act, int hide_cell_type,
              int precision, CriticSpec& s) {
     ssn::ActSpec a{};
-    if (!ssn::act_from_code(act, a)) return critic_refuse(fn, "invalid layer flags / activation");
+    if (!ssn::act_from_code(act, a)) return refuse(fn, "invalid layer flags / activation");
     s = CriticSpec{params, dims, layer_flags, nlayers, act, a.leak, hide_cell_type, precision == 0};
     return checked_spec(fn, s);
 }
@@ -954,7 +954,7 @@ int ssn_gen_apply_f32(float* params, const float* grads, float* s1, float* s2, i
 static int critic_step_impl(const ssn_critic_step* a, const double* gate, double gate_bound, void* stream) {
     if (!a || !a->params || !a->dims || !a->xg || !a->xd || !a->eps || !a->xp || !a->grads || !a->stats || !a->dvals ||
         !a->workspace || !a->opt || !a->acc_dvals || !a->tail || a->n <= 0 || a->nseg < 0)
-        return critic_refuse("ssn_critic_step_run", "invalid argument");
+        return refuse("ssn_critic_step_run", "invalid argument");
     CriticSpec net;
     if (int rc = norm_spec("ssn_critic_step_run", a->params, a->dims, a->layer_norm, a->nlayers, a->leak, a->hide_cell_type,
                            a->precision, net)) return rc;
@@ -975,7 +975,7 @@ static int critic_step_impl(const ssn_critic_step* a, const double* gate, double
     // stacked forward of the accuracy builds it: same rows, same conditions -- not built again)
     if ((rc = critic_net_accuracy_forwards(net, a->xg, a->cond, a->xd, a->cond, n, n, a->acc_dvals, a->workspace, st, one_launch_inputs)))
         return rc;
-    if (a->nseg > 0 && (!a->seg_bounds || !a->seg_ws)) return critic_refuse("ssn_critic_step_run", "invalid argument");
+    if (a->nseg > 0 && (!a->seg_bounds || !a->seg_ws)) return refuse("ssn_critic_step_run", "invalid argument");
     // accuracy, sums of squares and the head of the record: the chunk sums, then ONE finishing launch (same bits as
     // ssn_critic_accuracy + ssn_segment_sqnorms2_f32 + the head kernel)
     SSN_TRY(ssn::launch_step_finish(a->params, a->seg_bounds, a->nseg, a->seg_ws, a->acc_dvals, n, n, a->pens64, a->stats, a->tail, st));
@@ -1183,77 +1183,52 @@ int ssn_build_w_table_f32(const float* z, const float* jds_table, float* W, int 
     SSN_TRY(ssn::launch_build_w_table(z, jds_table, W, S, B, N, (hipStream_t)stream));
     return 0;
 }
+// ---- the scorer's and the sliced Wasserstein loss's entries: every refusal is refuse(entry, why) ---------------------------------
+static const char* const kInvalid = "invalid argument";
+static const char* const kTooManyDirections = "more than 4096 directions";
 int ssn_tc_features_f32(const float* tc, float* feat, long rows, int NC, int NB, int Q, void* stream) {
-    if (rows < 0 || NC < 0 || NB < 1 || Q < 0 || (rows * NC * Q > 0 && (!tc || !feat))) {
-        g_last_error = "ssn_tc_features_f32: invalid argument";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
+    if (rows < 0 || NC < 0 || NB < 1 || Q < 0 || (rows * NC * Q > 0 && (!tc || !feat))) return refuse("ssn_tc_features_f32", kInvalid);
     SSN_TRY(ssn::launch_tc_features(tc, feat, rows, NC, NB, Q, (hipStream_t)stream));
+    return 0;
+}
+// the two KS entries: `wnum` is the W1 entry's (required there), null for the plain one
+static int ks_columns(const char* fn, bool w1, const float* x, const float* truth_sorted, const int* m, int S, int B, int C, int T,
+                      int* n, long long* num, double* wnum, void* stream) {
+    if (B > SSN_KS_MAX_DRAWS) return refuse(fn, "more than 16384 values per column (the sort runs in 64 KiB of LDS)");
+    if (S < 0 || B < 1 || C < 0 || T < 0 ||
+        ((long)S * C > 0 && (!x || !m || !n || !num || (w1 && !wnum) || (T > 0 && !truth_sorted))))
+        return refuse(fn, kInvalid);
+    if (w1) SSN_TRY(ssn::launch_ks_w1_columns(x, truth_sorted, m, S, B, C, T, n, num, wnum, (hipStream_t)stream));
+    else    SSN_TRY(ssn::launch_ks_columns(x, truth_sorted, m, S, B, C, T, n, num, (hipStream_t)stream));
     return 0;
 }
 int ssn_ks_columns_f32(const float* x, const float* truth_sorted, const int* m, int S, int B, int C, int T, int* n,
                        long long* num, void* stream) {
-    if (B > SSN_KS_MAX_DRAWS) {
-        g_last_error = "ssn_ks_columns_f32: more than 16384 values per column (the sort runs in 64 KiB of LDS)";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    if (S < 0 || B < 1 || C < 0 || T < 0 || ((long)S * C > 0 && (!x || !m || !n || !num || (T > 0 && !truth_sorted)))) {
-        g_last_error = "ssn_ks_columns_f32: invalid argument";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    SSN_TRY(ssn::launch_ks_columns(x, truth_sorted, m, S, B, C, T, n, num, (hipStream_t)stream));
-    return 0;
+    return ks_columns("ssn_ks_columns_f32", false, x, truth_sorted, m, S, B, C, T, n, num, nullptr, stream);
 }
 int ssn_ks_w1_columns_f32(const float* x, const float* truth_sorted, const int* m, int S, int B, int C, int T, int* n,
                           long long* num, double* wnum, void* stream) {
-    if (B > SSN_KS_MAX_DRAWS) {
-        g_last_error = "ssn_ks_w1_columns_f32: more than 16384 values per column (the sort runs in 64 KiB of LDS)";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    if (S < 0 || B < 1 || C < 0 || T < 0 || ((long)S * C > 0 && (!x || !m || !n || !num || !wnum || (T > 0 && !truth_sorted)))) {
-        g_last_error = "ssn_ks_w1_columns_f32: invalid argument";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    SSN_TRY(ssn::launch_ks_w1_columns(x, truth_sorted, m, S, B, C, T, n, num, wnum, (hipStream_t)stream));
-    return 0;
+    return ks_columns("ssn_ks_w1_columns_f32", true, x, truth_sorted, m, S, B, C, T, n, num, wnum, stream);
 }
 int ssn_project_rows_f32(const float* x, long rows, int ldx, int C, const float* theta, int L, float* out, void* stream) {
-    if (L > SSN_W1_MAX_DIRECTIONS) {
-        g_last_error = "ssn_project_rows_f32: more than 4096 directions";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    if (rows < 0 || C < 0 || L < 0 || ldx < C || (rows * L > 0 && (!out || (C > 0 && (!x || !theta))))) {
-        g_last_error = "ssn_project_rows_f32: invalid argument";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
+    if (L > SSN_W1_MAX_DIRECTIONS) return refuse("ssn_project_rows_f32", kTooManyDirections);
+    if (rows < 0 || C < 0 || L < 0 || ldx < C || (rows * L > 0 && (!out || (C > 0 && (!x || !theta)))))
+        return refuse("ssn_project_rows_f32", kInvalid);
     SSN_TRY(ssn::launch_project_rows(x, rows, ldx, C, theta, L, out, (hipStream_t)stream));
     return 0;
 }
 int ssn_swd_match_f32(const float* px, const float* py, int B, int L, int power, float* coef, double* loss_l, void* stream) {
-    if (B > SSN_SWD_MAX_BATCH) {
-        g_last_error = "ssn_swd_match_f32: more than 4096 rows (keys and values are sorted in 48 KiB of LDS)";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    if (L > SSN_W1_MAX_DIRECTIONS) {
-        g_last_error = "ssn_swd_match_f32: more than 4096 directions";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    if (B < 0 || L < 0 || (power != 1 && power != 2) || ((long)B * L > 0 && (!px || !py || !coef || !loss_l))) {
-        g_last_error = "ssn_swd_match_f32: invalid argument";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
+    if (B > SSN_SWD_MAX_BATCH) return refuse("ssn_swd_match_f32", "more than 4096 rows (keys and values are sorted in 48 KiB of LDS)");
+    if (L > SSN_W1_MAX_DIRECTIONS) return refuse("ssn_swd_match_f32", kTooManyDirections);
+    if (B < 0 || L < 0 || (power != 1 && power != 2) || ((long)B * L > 0 && (!px || !py || !coef || !loss_l)))
+        return refuse("ssn_swd_match_f32", kInvalid);
     SSN_TRY(ssn::launch_swd_match(px, py, B, L, power, coef, loss_l, (hipStream_t)stream));
     return 0;
 }
 int ssn_swd_backproject_f32(const float* coef, const float* theta, int B, int L, int D, float* gx, void* stream) {
-    if (L > SSN_W1_MAX_DIRECTIONS) {
-        g_last_error = "ssn_swd_backproject_f32: more than 4096 directions";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    if (B < 0 || L < 0 || D < 0 || ((long)B * D > 0 && (!gx || (L > 0 && (!coef || !theta))))) {
-        g_last_error = "ssn_swd_backproject_f32: invalid argument";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
+    if (L > SSN_W1_MAX_DIRECTIONS) return refuse("ssn_swd_backproject_f32", kTooManyDirections);
+    if (B < 0 || L < 0 || D < 0 || ((long)B * D > 0 && (!gx || (L > 0 && (!coef || !theta)))))
+        return refuse("ssn_swd_backproject_f32", kInvalid);
     SSN_TRY(ssn::launch_swd_backproject(coef, theta, B, L, D, gx, (hipStream_t)stream));
     return 0;
 }
@@ -1264,57 +1239,37 @@ static_assert(SSN_ENS_SWD_MAX_MEMBERS == ssn::SWD_ENS_MAX_MEMBERS && SSN_SWD_WAV
 static int ens_swd_limits(const char* name, int K, int B, int L) {
     const char* what = K > SSN_ENS_SWD_MAX_MEMBERS ? "more than 2048 members"
                        : B > SSN_SWD_MAX_BATCH ? "more than 4096 rows per member (keys and values are sorted in 48 KiB of LDS)"
-                       : L > SSN_W1_MAX_DIRECTIONS ? "more than 4096 directions" : nullptr;
-    if (!what) return 0;
-    g_last_error = std::string(name) + ": " + what;
-    return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+                       : L > SSN_W1_MAX_DIRECTIONS ? kTooManyDirections : nullptr;
+    return what ? refuse(name, what) : 0;
 }
 int ssn_ens_swd_project_f32(const float* x, const float* y, const float* theta, int K, int B, int L, int D, float* px, float* py,
                             void* stream) {
     if (int err = ens_swd_limits("ssn_ens_swd_project_f32", K, B, L)) return err;
-    if (K < 0 || B < 0 || L < 0 || D < 0 || ((long)K * B * L > 0 && (!px || !py || (D > 0 && (!x || !y || !theta))))) {
-        g_last_error = "ssn_ens_swd_project_f32: invalid argument";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
+    if (K < 0 || B < 0 || L < 0 || D < 0 || ((long)K * B * L > 0 && (!px || !py || (D > 0 && (!x || !y || !theta)))))
+        return refuse("ssn_ens_swd_project_f32", kInvalid);
     SSN_TRY(ssn::launch_ens_swd_project(x, y, theta, K, B, L, D, px, py, (hipStream_t)stream));
     return 0;
 }
 int ssn_ens_swd_match_f32(const float* px, const float* py, const int* power, int K, int B, int L, int form, float* coef,
                           double* loss_l, double* l0, void* stream) {
-    if (int err = ens_swd_limits("ssn_ens_swd_match_f32", K, B, L)) return err;
-    if (K < 0 || B < 0 || L < 0 || (K > 0 && !power)) {
-        g_last_error = "ssn_ens_swd_match_f32: invalid argument";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
+    const char* const fn = "ssn_ens_swd_match_f32";
+    if (int err = ens_swd_limits(fn, K, B, L)) return err;
+    if (K < 0 || B < 0 || L < 0 || (K > 0 && !power)) return refuse(fn, kInvalid);
     ssn::SwdPowerBits bits{};
     for (int k = 0; k < K; ++k) {
-        if (power[k] != 1 && power[k] != 2) {
-            g_last_error = "ssn_ens_swd_match_f32: a power other than 1 or 2";
-            return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-        }
+        if (power[k] != 1 && power[k] != 2) return refuse(fn, "a power other than 1 or 2");
         if (power[k] == 2) bits.w[k >> 5] |= 1u << (k & 31);
     }
-    if (form != SSN_SWD_FORM_AUTO && form != SSN_SWD_FORM_GENERAL && form != SSN_SWD_FORM_WAVE) {
-        g_last_error = "ssn_ens_swd_match_f32: unknown form";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    if (form == SSN_SWD_FORM_WAVE && B > SSN_SWD_WAVE_MAX_BATCH) {
-        g_last_error = "ssn_ens_swd_match_f32: the wave form takes at most 64 rows per member";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
-    if ((long)K * B * L > 0 && (!px || !py || !coef || !loss_l || !l0)) {
-        g_last_error = "ssn_ens_swd_match_f32: invalid argument (null pointer)";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
+    if (form != SSN_SWD_FORM_AUTO && form != SSN_SWD_FORM_GENERAL && form != SSN_SWD_FORM_WAVE) return refuse(fn, "unknown form");
+    if (form == SSN_SWD_FORM_WAVE && B > SSN_SWD_WAVE_MAX_BATCH) return refuse(fn, "the wave form takes at most 64 rows per member");
+    if ((long)K * B * L > 0 && (!px || !py || !coef || !loss_l || !l0)) return refuse(fn, "invalid argument (null pointer)");
     SSN_TRY(ssn::launch_ens_swd_match(px, py, bits, K, B, L, form, coef, loss_l, l0, (hipStream_t)stream));
     return 0;
 }
 int ssn_ens_swd_backproject_f32(const float* coef, const float* theta, int K, int B, int L, int D, float* gx, void* stream) {
     if (int err = ens_swd_limits("ssn_ens_swd_backproject_f32", K, B, L)) return err;
-    if (K < 0 || B < 0 || L < 0 || D < 0 || ((long)K * B * D > 0 && (!gx || (L > 0 && (!coef || !theta))))) {
-        g_last_error = "ssn_ens_swd_backproject_f32: invalid argument";
-        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
-    }
+    if (K < 0 || B < 0 || L < 0 || D < 0 || ((long)K * B * D > 0 && (!gx || (L > 0 && (!coef || !theta)))))
+        return refuse("ssn_ens_swd_backproject_f32", kInvalid);
     if (L == 0) {                                             // (as the single-run entry: no direction, zeros)
         if ((long)K * B * D > 0) SSN_TRY(hipMemsetAsync(gx, 0, (size_t)K * B * D * sizeof(float), (hipStream_t)stream));
         return 0;

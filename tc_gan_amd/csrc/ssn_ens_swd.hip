@@ -61,7 +61,7 @@ __device__ __forceinline__ uint32_t swd_lane_xor(uint32_t v) {
 }
 
 // one compare-exchange stage of the bitonic network (block size K, distance J) on the pair (lane & ~J, lane | J): the rule of
-// swd_match_body, a = the value at the lower index, b = at the upper, exchanged where (a > b) == up
+// cmp_exchange (ssn_sortcol_dev.h), a = the value at the lower index, b = at the upper, exchanged where (a > b) == up
 template <int K, int J>
 __device__ __forceinline__ void swd_wave_stage(uint32_t& hi, uint32_t& lo, float& y, int lane) {
     const uint32_t ohi = swd_lane_xor<J>(hi), olo = swd_lane_xor<J>(lo);
@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(256) ens_swd_match_wave_kernel(const float* __
         sum += term;
         if ((int)lo < B) coef[o + (size_t)lo * L + l] = (float)cf;       // (the first B ranks are rows)
     }
-    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);  // (wave_sum_in_order's text: through the call, 23 VGPRs)
     if (lane == 0) loss_l[col] = sum / (double)B;
 }
 
@@ -157,8 +157,7 @@ hipError_t launch_ens_swd_match(const float* px, const float* py, const SwdPower
         hipLaunchKernelGGL(ens_swd_match_wave_kernel, dim3((columns + 3) / 4), dim3(256), 0, st, px, py, B, L, columns, powers, inv, coef,
                            loss_l);
     } else {
-        int P = 64;
-        while (P < B) P <<= 1;
+        const int P = sort_slots(B);
         hipLaunchKernelGGL(ens_swd_match_kernel, dim3(L, K), dim3(256), (size_t)P * (sizeof(unsigned long long) + sizeof(float)), st, px,
                            py, B, L, P, powers, inv, coef, loss_l);
     }

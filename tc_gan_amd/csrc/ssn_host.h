@@ -280,6 +280,8 @@ inline bool critic_layout(const CriticSpec& c, CriticLayout& net) {
 // grid of a grid-stride kernel of 256-thread blocks over n elements; the next n floats of a workspace
 inline int blocks_for(long n) { long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
 inline float* carve(float*& p, long n) { float* r = p; p += n; return r; }
+// LDS slots of a bitonic sort of B elements on 256 threads: the power of two >= max(B, 64)
+inline int sort_slots(int B) { int P = 64; while (P < B) P <<= 1; return P; }
 
 // ssn_critic.hip: plain layers, any slope (the layer-by-layer MFMA GEMM chain)
 // (deterministic split-K of the weight-gradient GEMMs: between begin and flush every split GEMM of the calling thread writes slabs

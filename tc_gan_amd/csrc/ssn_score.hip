@@ -9,24 +9,14 @@
 //   per-curve features                tc_features_kernel: maxrate, suppression index, preferred bandwidth (first index of the
 //                                     maximum) and inverse participation ratio of every curve over its NB bandwidths, fp32, sums
 //                                     in bandwidth order.
-//   KS statistic per (set, column)    ks_columns_kernel: one workgroup per (s, column).  The B values go to LDS (non-finite ones
-//                                     as +inf, the padding up to a power of two as +inf too), a bitonic sort puts the n finite
-//                                     values first, and every pooled point v -- the n values and the column's m truth values --
-//                                     gets #{x <= v} and #{t <= v} by binary search (x in LDS, the sorted truth column in
-//                                     global memory: 4 T bytes that stay in cache for the workgroup).  The statistic is kept as
-//                                     the integer num = max |#{x <= v} m - #{t <= v} n| (KSD = num / (n m)): exact whatever the
-//                                     ties, and what scipy.stats.ks_2samp(...).statistic computes in floating point.
-//
-// LDS banks of the sort (MI355X: ds_read_b32 / ds_write_b32 are served per 32-lane half on 32 banks of 4 bytes): a step with
-// partner distance j handles pair p as elements i = 2 (p - p % j) + p % j and i + j.  For j >= 32 the 32 lanes of a half read 32
-// consecutive dwords: no conflict.  For j < 32 they read j consecutive dwords out of every 2 j: 2-way on the i's, and the i + j's
-// fill the other banks' second turn, so a step costs two LDS cycles per half and instruction where a conflict-free one costs
-// one; the stores' 2-way costs nothing (a store's time is its register transfer).  The sort is log2(P) (log2(P) + 1) / 2 such
-// steps of P / 2 pairs, the walk (n + m) (log2 n + log2 m) search steps; at the sizes the scorer runs (tens to a few thousand
-// draws per set against a few thousand truth rows) the walk is the larger part.
+//   KS statistic per (set, column)    ks_columns_kernel: one workgroup per (s, column) sorts the column in LDS and walks the
+//                                     pooled sample: ks_column_body (ssn_sortcol_dev.h).  The statistic is kept as the integer
+//                                     num = max |#{x <= v} m - #{t <= v} n| (KSD = num / (n m)): exact whatever the ties, and
+//                                     what scipy.stats.ks_2samp(...).statistic computes in floating point.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ssn_host.h"
+#include "ssn_sortcol_dev.h"
 
 namespace ssn {
 
@@ -107,70 +97,12 @@ __global__ void __launch_bounds__(256) tc_features_kernel(const float* __restric
     }
 }
 
-// #{a[0 .. n) <= v} of an ascending array
-__device__ __forceinline__ int count_le(const float* a, int n, float v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] <= v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// grid (C, S); dynamic LDS: P floats, P = the power of two >= max(B, 64).  x[S][B][C]; t[C][T] ascending with the m[c] finite
-// values first; n_out[S][C] (int), num_out[S][C] (long long)
+// grid (C, S); dynamic LDS: P floats, P = sort_slots(B): ks_column_body (ssn_sortcol_dev.h) without the W1 sum
 __global__ void __launch_bounds__(256) ks_columns_kernel(const float* __restrict__ x, const float* __restrict__ t,
                                                          const int* __restrict__ m_of, int B, int C, int T, int P,
                                                          int* __restrict__ n_out, long long* __restrict__ num_out) {
     extern __shared__ float score_lds[];
-    float* sx = score_lds;
-    const int c = blockIdx.x, s = blockIdx.y;
-    const float inf = __builtin_huge_valf();
-    const float* xs = x + (size_t)s * B * C + c;
-    for (int i = threadIdx.x; i < P; i += 256) {
-        float v = inf;
-        if (i < B) {
-            v = xs[(size_t)i * C];
-            if (!(fabsf(v) < inf)) v = inf;                   // NaN, +inf, -inf: left out of the column
-        }
-        sx[i] = v;
-    }
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j >= 1; j >>= 1) {
-            for (int p = threadIdx.x; p < (P >> 1); p += 256) {
-                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-                const float a = sx[i], b = sx[i + j];
-                const bool up = (i & k) == 0;
-                if ((a > b) == up) { sx[i] = b; sx[i + j] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    const int n = count_le(sx, P, 3.4028234663852886e38f);    // the finite values: everything below +inf
-    const int m = min(max(m_of[c], 0), T);
-    const float* tc = t + (size_t)c * T;
-    long long best = 0;
-    for (int i = threadIdx.x; i < n + m; i += 256) {
-        const float v = i < n ? sx[i] : tc[i - n];
-        const long long cx = count_le(sx, n, v), ct = count_le(tc, m, v);
-        long long d = cx * m - ct * n;
-        if (d < 0) d = -d;
-        if (d > best) best = d;
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        const long long o = __shfl_xor(best, off);
-        if (o > best) best = o;
-    }
-    __syncthreads();                                          // every wave is done with sx: its first words carry the reduction
-    long long* red = reinterpret_cast<long long*>(sx);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) if (red[w] > best) best = red[w];
-        n_out[(size_t)s * C + c] = n;
-        num_out[(size_t)s * C + c] = best;
-    }
+    ks_column_body<false>(x, t, m_of, B, C, T, P, n_out, num_out, nullptr, score_lds);
 }
 
 hipError_t launch_build_w_table(const float* z, const float* table, float* W, int S, int B, int N, hipStream_t st) {
@@ -202,15 +134,7 @@ hipError_t launch_tc_features(const float* tc, float* feat, long R, int NC, int 
 
 hipError_t launch_ks_columns(const float* x, const float* t, const int* m, int S, int B, int C, int T, int* n_out,
                              long long* num_out, hipStream_t st) {
-    if (S == 0 || C == 0) return hipSuccess;
-    int P = 64;
-    while (P < B) P <<= 1;
-    for (int s0 = 0; s0 < S; s0 += 65535) {                   // (grid.y is a 16-bit count)
-        const int ns = S - s0 < 65535 ? S - s0 : 65535;
-        hipLaunchKernelGGL(ks_columns_kernel, dim3(C, ns), dim3(256), (size_t)P * sizeof(float), st, x + (size_t)s0 * B * C, t, m,
-                           B, C, T, P, n_out + (size_t)s0 * C, num_out + (size_t)s0 * C);
-    }
-    return hipGetLastError();
+    return launch_ks_kernel(ks_columns_kernel, x, t, m, S, B, C, T, st, n_out, num_out);
 }
 
 }  // namespace ssn

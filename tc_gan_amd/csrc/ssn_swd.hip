@@ -5,12 +5,12 @@
 //   match        swd_match_kernel: one workgroup per direction l.  The column px[.][l] becomes 64-bit keys -- high word an
 //                order-preserving transform of the float with -0 taken as +0, low word the row index -- so that an integer sort
 //                IS the stable sort by value (ties by row); py[.][l] stays floats.  Both are padded to P, the power of two
-//                >= max(B, 64), with keys above every finite value, and sorted by one bitonic network (the two arrays share
-//                its barriers).  A value that is not finite is found while loading: the workgroup then writes NaN to loss_l[l]
-//                and to coef[.][l] and leaves, the sort never sees it.  Rank i: d = (double) u_i - (double) v_i, the term
-//                |d| or d d (rounded on its own), the coefficient sign(d) inv or (2 d) inv scattered to coef[b_i][l].  A thread
-//                sums its terms in index order, a wave adds lanes 32, 16, ... 1 apart, thread 0 adds the four waves in order and
-//                divides by B: no atomics, the same bits every launch.
+//                >= max(B, 64), with keys above every finite value, and sorted by one call of bitonic_sort_lds
+//                (ssn_sortcol_dev.h).  A value that is not finite is found while loading: the workgroup then writes NaN to
+//                loss_l[l] and to coef[.][l] and leaves, the sort never sees it.  Rank i: d = (double) u_i - (double) v_i, the
+//                term |d| or d d (rounded on its own), the coefficient sign(d) inv or (2 d) inv scattered to coef[b_i][l].
+//                The terms go through the ordered block sum of that header and are divided by B: no atomics, the same bits
+//                every launch.
 //   backproject  swd_backproject_kernel: gx[b][c] = (float) sum_l coef[b][l] theta[l][c], an fp64 FMA chain over l in order (the
 //                products of two floats are exact in fp64).  A workgroup owns 16 rows x 16 columns and stages 64 directions of
 //                coef and theta at a time in LDS; coef's rows are padded to 65 words (the 4 rows of a wave's half read one
@@ -37,8 +37,7 @@ __global__ void __launch_bounds__(256) swd_backproject_kernel(const float* __res
 
 hipError_t launch_swd_match(const float* px, const float* py, int B, int L, int power, float* coef, double* loss_l, hipStream_t st) {
     if (B == 0 || L == 0) return hipSuccess;
-    int P = 64;
-    while (P < B) P <<= 1;
+    const int P = sort_slots(B);
     const double inv = 1.0 / ((double)L * (double)B);
     hipLaunchKernelGGL(swd_match_kernel, dim3(L), dim3(256), (size_t)P * (sizeof(unsigned long long) + sizeof(float)), st, px, py, B,
                        L, P, power, inv, coef, loss_l);

@@ -1,10 +1,12 @@
 // Device bodies of the sliced Wasserstein loss kernels, shared by the single-run kernels (ssn_wdist.hip: project_rows_kernel;
 // ssn_swd.hip: swd_match_kernel, swd_backproject_kernel) and the grid-over-members kernels of ssn_ens_swd.hip.  A body takes the
 // base pointers of ONE problem (one sample, one member) and the part of the grid that works on it; the kernels differ only in how
-// they find those from blockIdx, so a member's values are the bits of its single run by construction.
+// they find those from blockIdx, so a member's values are the bits of its single run by construction.  The sort and the ordered
+// sum of the match are ssn_sortcol_dev.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ssn_sortcol_dev.h"
 
 namespace ssn {
 
@@ -106,19 +108,7 @@ __device__ __forceinline__ void swd_match_body(const float* __restrict__ px, con
         if (threadIdx.x == 0) loss_l[l] = __builtin_nan("");
         return;
     }
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j >= 1; j >>= 1) {
-            for (int p = threadIdx.x; p < (P >> 1); p += 256) {
-                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-                const bool up = (i & k) == 0;
-                const unsigned long long a = kx[i], b = kx[i + j];
-                if ((a > b) == up) { kx[i] = b; kx[i + j] = a; }
-                const float c = sy[i], d = sy[i + j];
-                if ((c > d) == up) { sy[i] = d; sy[i + j] = c; }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_lds(P, kx, sy);
     double sum = 0.0;
     for (int i = threadIdx.x; i < B; i += 256) {
         const unsigned long long key = kx[i];
@@ -129,13 +119,8 @@ __device__ __forceinline__ void swd_match_body(const float* __restrict__ px, con
         sum += term;
         if (b < B) coef[(size_t)b * L + l] = (float)cf;       // (the first B ranks are rows: the padding sorts behind them)
     }
-    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) sum += red[w];
-        loss_l[l] = sum / (double)B;
-    }
+    sum = block_sum_in_order(sum, red);
+    if (threadIdx.x == 0) loss_l[l] = sum / (double)B;
 }
 
 constexpr int BP_ROWS = 16;                                   // rows of a workgroup

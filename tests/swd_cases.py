@@ -6,14 +6,15 @@ For float32 projections px, py (B, L) and every direction l: the pairs (px[b][l]
 loss_l = (sum_i |d_i|^p) / B -- here in exact rational arithmetic -- and the coefficient of the row b_i that holds u_i:
 (float) (sign(d_i) inv) for p = 1, (float) ((2 d_i) inv) for p = 2 with inv = 1 / (L B), every operation an fp64 operation
 numpy performs elementwise as the kernel does.  A column of px or py with a value that is not finite gives NaN for its loss and
-its coefficients.  The back-projection is the sequential fp64 sum of exact products it is defined as.
+its coefficients.  `loss_in_kernel_order` restates loss_l with the kernels' roundings in the kernels' order of additions, for
+equality of bits.  The back-projection is the sequential fp64 sum of exact products it is defined as.
 
 `match` takes three deliberate errors (`ties='reversed'`, `drop_last=True`, `scatter='rank'`) for the sensitivity test."""
 from fractions import Fraction
 
 import numpy as np
 
-from wasserstein_cases import project_rows
+from wasserstein_cases import block_sum_in_order, project_rows
 
 
 def match(px, py, power, ties='row', drop_last=False, scatter='row'):
@@ -42,6 +43,18 @@ def match(px, py, power, ties='row', drop_last=False, scatter='row'):
         else:                                                     # the deliberate error: the coefficient stays at its rank
             coef[:, l] = c
     return coef, loss_l
+
+
+def loss_in_kernel_order(px_col, py_col, power):
+    """loss_l of one direction as the match kernels compute it, operation by operation (a numpy float64; NaN where a value is
+    not finite): rank i has the term |d_i| or fl(d_i d_i) with d_i = (double) u_i - (double) v_i, the terms are summed by
+    `wasserstein_cases.block_sum_in_order` over the ranks (rank i on thread i % 256) and the sum is divided by B."""
+    px, py = np.asarray(px_col, dtype='float32').reshape(-1), np.asarray(py_col, dtype='float32').reshape(-1)
+    if not (np.isfinite(px).all() and np.isfinite(py).all()):
+        return np.float64('nan')
+    col = px + np.float32(0.0)                                    # (-0 becomes +0)
+    d = col[np.argsort(col, kind='stable')].astype('float64') - np.sort(py).astype('float64')
+    return block_sum_in_order(np.abs(d) if power == 1 else d * d) / np.float64(len(px))
 
 
 def loss_floats(loss_l):

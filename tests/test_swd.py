@@ -132,6 +132,32 @@ def test_ties_zero_differences_and_non_finite_columns():
             assert np.isnan(sc.backproject(coef, np.ones((2, 3), dtype='float32'))).all()
 
 
+@pytest.mark.parametrize('power', [1, 2])
+def test_loss_in_kernel_order_is_exact_on_a_lattice_and_within_the_bound_elsewhere(power):
+    """The restatement of the order of additions against the exact loss of `match`: equal where every operation is exact, inside
+    `loss_bound` on generic values; NaN for a column that is not finite.  B below, at and above one term per thread."""
+    for B, L, D in ((1, 1, 1), (64, 2, 6), (1024, 4, 6)):
+        x, y, theta = sc.lattice_inputs(np.random.RandomState(200 + B), B, L, D)
+        want = sc.swd(x, y, theta, power)
+        got = [sc.loss_in_kernel_order(want['px'][:, l], want['py'][:, l], power) for l in range(L)]
+        assert [Fraction(float(v)) for v in got] == want['loss_l']
+    worst = Fraction(0)
+    for B, L, D in ((2, 3, 6), (65, 5, 6), (300, 5, 40), (1000, 3, 6)):
+        x, y, theta = sc.generic_inputs(np.random.RandomState(100 + B), B, L, D)
+        want = sc.swd(x, y, theta, power)
+        for l in range(L):
+            exact = want['loss_l'][l]
+            err = abs(Fraction(float(sc.loss_in_kernel_order(want['px'][:, l], want['py'][:, l], power))) - exact)
+            assert err <= sc.loss_bound(exact, B), (B, l)
+            if exact:
+                worst = max(worst, err / sc.loss_bound(exact, B))
+    print('largest error of the restatement: {:.3g} of the bound'.format(float(worst)))
+    assert worst > 0                                              # (generic values do round: the order is exercised)
+    px = np.array([1.0, np.inf, 2.0], dtype='float32')
+    assert np.isnan(sc.loss_in_kernel_order(px, np.ones(3, dtype='float32'), power))
+    assert np.isnan(sc.loss_in_kernel_order(np.ones(3, dtype='float32'), [0.0, np.nan, 1.0], power))
+
+
 # ---- 2. sensitivity: what a wrong restatement would move ---------------------------------------------------------------
 
 def test_deliberate_errors_move_the_checked_quantities_far_beyond_their_tolerances():

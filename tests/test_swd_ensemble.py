@@ -212,6 +212,6 @@ def test_no_kernel_of_the_new_file_spills_or_uses_scratch(tmp_path):
     # the wave form sorts in registers: cross-lane moves, no LDS traffic but the moves' own, no barrier
     body = re.search(r'^_ZN\w*ens_swd_match_wave_kernel\w*:.*?^\.Lfunc_end', text, re.S | re.M).group(0)
     assert 'dpp' in body and 's_barrier' not in body and 'ds_read' not in body and 'ds_write' not in body
-    for name in ('ssn_ens_swd.hip', 'ssn_swd_dev.h'):
+    for name in ('ssn_ens_swd.hip', 'ssn_swd_dev.h', 'ssn_sortcol_dev.h'):
         source = open(os.path.join(CSRC, name)).read()
         assert 'asm' not in source and 'atomic' not in source.lower().replace('no atomics', '')

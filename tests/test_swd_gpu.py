@@ -78,6 +78,10 @@ def test_generic_inputs_bit_for_bit_and_loss_within_the_bound(B, L, D, power):
         if exact:
             worst = max(worst, err / exact)
     print('B, L, D, p =', (B, L, D, power), 'largest relative error of loss_l:', float(worst), 'bound', (B + 2) * 2.0 ** -52)
+    # the order of the additions: loss_l is the restatement of the thread, wave and block sums bit for bit
+    assert np.isfinite(got['loss_l']).all()
+    ordered = np.array([sc.loss_in_kernel_order(want['px'][:, l], want['py'][:, l], power) for l in range(L)])
+    np.testing.assert_array_equal(got['loss_l'].view(np.uint64), ordered.view(np.uint64))
     # the whole chain as the trainer calls it: the same gradient, the mean of the directions
     gx, loss, loss_l = swd_loss_grad(_dev(x), _dev(y), _dev(theta), power)
     _same_bits(gx.cpu().numpy(), want['gx'])

@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from test_distdiff import CFG, THETA, ks_numerators
-from wasserstein_cases import lattice, project_rows, w1_columns, w1_distance, w1_exact
+from wasserstein_cases import (block_sum_in_order, lattice, project_rows, w1_columns, w1_distance, w1_exact, wnum_bound,
+                               wnum_in_kernel_order)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'tc_gan_amd', 'csrc')
@@ -71,6 +72,53 @@ def test_w1_tells_apart_what_ks_cannot():
     assert w_far - w_near == 5
     # (all of x above all of t: W1 is the difference of the means; the sums of multiples of 1/8 are exact in fp64)
     assert w_near == Fraction(float(near.astype('float64').sum())) / 30 - Fraction(float(t.astype('float64').sum())) / 50
+
+
+def test_block_sum_in_order_adds_in_the_stated_order():
+    """Powers of two that differ by more than 53 bits show who is added to whom: 1 + 2^-53 rounds back to 1 (ties to even), so a
+    small term survives only where it meets another small term first."""
+    tiny = 2.0 ** -53
+    assert block_sum_in_order([]) == 0 and block_sum_in_order([3.0]) == 3
+    assert block_sum_in_order(np.ones(1000)) == 1000
+    one_thread = np.zeros(513)
+    one_thread[[0, 256, 512]] = [1, tiny, tiny]                                   # thread 0: (1 + tiny) + tiny
+    assert block_sum_in_order(one_thread) == 1
+    one_thread[[0, 256, 512]] = [tiny, tiny, 1]                                   # (tiny + tiny) + 1
+    assert block_sum_in_order(one_thread) == 1 + 2 * tiny
+    lanes = np.zeros(64)
+    lanes[[0, 32, 33]] = [1, tiny, tiny]                                          # off = 32 first: lane 0 takes lane 32 alone
+    assert block_sum_in_order(lanes) == 1
+    lanes[[0, 32, 33]] = [0, 0, 0]
+    lanes[[0, 1, 33]] = [1, tiny, tiny]                                           # off = 32 joins lanes 1 and 33 before off = 1
+    assert block_sum_in_order(lanes) == 1 + 2 * tiny
+    lanes[[0, 1, 33]] = [0, 0, 0]
+    lanes[[0, 1, 3]] = [1, tiny, tiny]                                            # off = 2 joins lanes 1 and 3 before off = 1
+    assert block_sum_in_order(lanes) == 1 + 2 * tiny
+    waves = np.zeros(256)
+    waves[[0, 64, 128]] = [1, tiny, tiny]                                         # (wave 0 + wave 1) + wave 2
+    assert block_sum_in_order(waves) == 1
+    waves[[0, 64, 128]] = [tiny, tiny, 1]
+    assert block_sum_in_order(waves) == 1 + 2 * tiny
+
+
+@pytest.mark.parametrize('B,T', [(1, 1), (64, 7), (65, 50), (257, 50), (300, 7), (300, 700)])
+def test_wnum_in_kernel_order_is_exact_on_a_lattice_and_within_the_bound_elsewhere(B, T):
+    rs = np.random.RandomState(B + T)
+    x, t = lattice(rs, (B,)), lattice(rs, (T,))
+    if B >= 4:
+        x[[0, B // 2, B - 1]] = [np.nan, np.inf, -np.inf]
+    exact, n, m = w1_exact(x, t)
+    assert n == (B - 3 if B >= 4 else B) and Fraction(float(wnum_in_kernel_order(x, t))) == exact
+    assert wnum_in_kernel_order(t, t) == 0 and wnum_in_kernel_order(x, [np.nan]) == 0 and wnum_in_kernel_order([np.nan], t) == 0
+    worst = Fraction(0)
+    for _ in range(5):
+        x, t = (rs.rand(B) * 40).astype('float32'), (rs.rand(T) * 40).astype('float32')
+        x[rs.randint(B)] = t[rs.randint(T)]                                       # a value both hold
+        exact, n, m = w1_exact(x, t)
+        err, bound = abs(Fraction(float(wnum_in_kernel_order(x, t))) - exact), wnum_bound(exact, n, m)
+        assert err <= bound
+        worst = max(worst, err / bound if bound else 0)
+    print('largest error of the restatement: {:.3g} of the bound'.format(float(worst)))
 
 
 def test_projection_restatement_is_the_sequential_sum():

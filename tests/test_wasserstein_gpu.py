@@ -19,7 +19,7 @@ from tc_gan_amd.clib import libssnode
 from tc_gan_amd.networks.fixed_time_sampler import FixedTimeTuningCurveSampler, new_JDS
 from test_distdiff import CFG as SMALL_CFG
 from test_distdiff_gpu import GAN, TRUE_JDS, _ks_device, _run, _thetas
-from wasserstein_cases import lattice, project_rows, w1_columns, w1_exact, wnum_bound
+from wasserstein_cases import lattice, project_rows, w1_columns, w1_exact, wnum_bound, wnum_in_kernel_order
 
 pytestmark = pytest.mark.gpu
 
@@ -113,6 +113,9 @@ def test_w1_kernel_holds_the_derived_bound_on_generic_values(B, T):
                 worst = max(worst, err / bound)
             assert err <= bound, (s, c, float(err), float(bound))
     print('largest error of wnum: {:.3g} of the bound'.format(float(worst)))
+    # the order of the additions: wnum is the restatement of the thread, wave and block sums bit for bit
+    ordered = np.array([[wnum_in_kernel_order(x[s, :, c], t[:, c]) for c in range(C)] for s in range(S)])
+    np.testing.assert_array_equal(wnum.view(np.uint64), ordered.view(np.uint64))
 
 
 def test_w1_kernel_refuses_more_than_16384_values():
