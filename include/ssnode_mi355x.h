@@ -518,6 +518,7 @@ int ssn_moment_loss_grad_f32(const float *x, const double *sums, double global_b
  * ssn_ens_gen_grads_f32: grads[K][nv + 12] = ssn_gen_grads_f32's dL/dV, dL/dJ, dL/dD, dL/dS per member; the penalty means of the
  *   forward's rows dyn_row / rate_row over the member's draws (scale_*: 1 / element count of ONE member); L0 and
  *   loss = L0 + costs[k][0] dyn + costs[k][1] rate into the record.  One workgroup per member, fp64 sums in a fixed order.
+ *   D >= 1 (L0 is a mean over the 2 D moments); D = 0 is refused: a loss without moments takes ssn_ens_gen_grads_l0_f32.
  * ssn_ens_apply_f32: ssn_optimizer_step's update of all K parameter vectors p[K][P] (states s1, s2 [K][P]) with
  *   hyp[k][8] = (learning_rate, a_t, reg_l2_penalty, reg_l1_penalty, reg_l2_decay, reg_l1_decay, -, -) per member (a_t: Adam's
  *   lr sqrt(1 - beta2^t) / (1 - beta1^t), formed by the caller) and per-element clip bounds [K][P]; a NaN value stays NaN.

@@ -1121,6 +1121,10 @@ int ssn_ens_jds_grad_f32(const float* gW, const float* z, const float* p16, doub
     return 0;
 }
 int ssn_ens_gen_grads_f32(const ssn_ens_grads* a, void* stream) {
+    if (a && a->D == 0) {                      // (L0 would be 0 / 0: a loss without moments hands its own L0 in)
+        g_last_error = "ssn_ens_gen_grads: D must be at least 1 (a loss that is not a function of moments takes ssn_ens_gen_grads_l0_f32)";
+        return SSN_ERR_BASE + (int)hipErrorInvalidValue;
+    }
     if (!a || a->K < 0 || a->B <= 0 || a->nv < 0 || a->nv > 2 || a->NB <= 0 || a->M <= 0 || (a->M & 1) || a->D < 0 ||
         a->rstride < ssn_ens_record_doubles(a->D, a->nv + 12) ||
         (a->K > 0 && (!a->part || !a->dyn_row || !a->rate_row || !a->data_moments || !a->weights || !a->costs || !a->grads ||
