@@ -16,6 +16,7 @@ import torch
 
 from . import clib
 from .clib import libssnode
+from .networks.gen_state import flat_bounds
 
 PRECISION = {'bf16': 0, 'fp32': 1}
 
@@ -368,6 +369,7 @@ class Updater(object):
         self.reg = (reg_l2_penalty, reg_l1_penalty, reg_l2_decay, reg_l1_decay)
         self.step = 0
         self._state = None
+        self._clip_cache = (None,)        # (key, lo, hi): the device copies of the last per-element bounds
 
     def state_dict(self):
         """Optimizer state for checkpoints (step counter and the two moment buffers)."""
@@ -400,12 +402,16 @@ class Updater(object):
         runs once its launch has been accepted -- a library call that returns an error leaves the updater where it was."""
         if self._state is None or self._state[0].shape != params.shape:
             self._state = (torch.zeros_like(params), torch.zeros_like(params))
-        o = clib.OptParams(kind=self.kind, step=self.step + 1, clip=0, reserved=0,
-                           learning_rate=self.learning_rate, beta1=self.cfg['beta1'], beta2=self.cfg['beta2'],
-                           epsilon=self.cfg['epsilon'], rho=self.cfg['rho'],
-                           reg_l2_penalty=self.reg[0], reg_l1_penalty=self.reg[1],
-                           reg_l2_decay=self.reg[2], reg_l1_decay=self.reg[3], clip_lo=0.0, clip_hi=0.0)
-        return self._state[0], self._state[1], o
+        return self._state[0], self._state[1], self._opt_params(None)
+
+    def _opt_params(self, clip):
+        """The `ssn_opt_params` of the update numbered step + 1; `clip` = (lo, hi) scalars, or None for no clipping."""
+        return clib.OptParams(kind=self.kind, step=self.step + 1, clip=int(clip is not None), reserved=0,
+                              learning_rate=self.learning_rate, beta1=self.cfg['beta1'], beta2=self.cfg['beta2'],
+                              epsilon=self.cfg['epsilon'], rho=self.cfg['rho'],
+                              reg_l2_penalty=self.reg[0], reg_l1_penalty=self.reg[1],
+                              reg_l2_decay=self.reg[2], reg_l1_decay=self.reg[3],
+                              clip_lo=clip[0] if clip else 0.0, clip_hi=clip[1] if clip else 0.0)
 
     def commit_step(self, opt):
         self.step = int(opt.step)
@@ -422,19 +428,13 @@ class Updater(object):
             self._state = (torch.zeros_like(params), torch.zeros_like(params))
         elementwise = None
         if clip is not None and (np.ndim(clip[0]) > 0 or np.ndim(clip[1]) > 0):
-            lo = np.broadcast_to(np.asarray(clip[0], dtype='float32').ravel(), (params.numel(),))
-            hi = np.broadcast_to(np.asarray(clip[1], dtype='float32').ravel(), (params.numel(),))
+            lo, hi = flat_bounds([params.numel()], [clip])
             key = (lo.tobytes(), hi.tobytes())
-            if getattr(self, '_clip_cache', (None,))[0] != key:
-                self._clip_cache = (key, torch.as_tensor(np.array(lo)).to(params.device), torch.as_tensor(np.array(hi)).to(params.device))
+            if self._clip_cache[0] != key:
+                self._clip_cache = (key, torch.as_tensor(lo).to(params.device), torch.as_tensor(hi).to(params.device))
             elementwise = self._clip_cache[1:]
             clip = (float(lo.min()), float(hi.max()))
-        o = clib.OptParams(kind=self.kind, step=self.step + 1, clip=int(clip is not None), reserved=0,
-                           learning_rate=self.learning_rate, beta1=self.cfg['beta1'], beta2=self.cfg['beta2'],
-                           epsilon=self.cfg['epsilon'], rho=self.cfg['rho'],
-                           reg_l2_penalty=self.reg[0], reg_l1_penalty=self.reg[1],
-                           reg_l2_decay=self.reg[2], reg_l1_decay=self.reg[3],
-                           clip_lo=clip[0] if clip else 0.0, clip_hi=clip[1] if clip else 0.0)
+        o = self._opt_params(clip)
         clib.check(libssnode.ssn_optimizer_step(params.data_ptr(), grads.data_ptr(), self._state[0].data_ptr(),
                                                 self._state[1].data_ptr(), params.numel(), ctypes.byref(o), _stream()),
                    'ssn_optimizer_step')

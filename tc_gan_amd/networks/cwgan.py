@@ -18,23 +18,25 @@ rank keeps a replica of the critic and of (J, D, S), works on its contiguous sli
 ``num_models`` weight draws, and ONE all-reduce per update (flat buffer: critic grads | 12 generator
 grads | loss scalars) makes the replicas take identical optimizer steps.
 """
-from logging import getLogger
-
+import ctypes
+import itertools
 import os
-
+import pickle
 import time
+from logging import getLogger
 
 import numpy as np
 import torch
 
-from .. import clib
-from ..critic import Critic, Updater
+from .. import clib, genops
+from ..critic import Critic
 from ..execution import KnownError
 from ..gradient_expressions.utils import sample_sites_from_stim_space
 from ..utils import Namespace, StopWatch, as_randomstate, cartesian_product, to_device, to_device_packed
-from .ssn import TuningCurveGenerator
 from .utils import gridify_tc_samples
-from ._common import DEFAULT_PARAMS as _WGAN_DEFAULTS
+from ._common import (DEFAULT_PARAMS as _WGAN_DEFAULTS, GradientAllReducer, _v_bounds,  # noqa: F401  (`_v_bounds` re-exported)
+                      build_generator, generator_trainer_parts, updater_from)
+from .gen_state import GeneratorParamState, HostRecord
 
 # (A/B switch: TCGAN_PREQUEUE=0 queues the first critic forward of an iteration only after the generator step's record was read)
 _PREQUEUE = os.environ.get('TCGAN_PREQUEUE', '1') != '0'
@@ -172,71 +174,15 @@ class RandomChoiceSampler(object):
             yield self.select_minibatch(*args, **kwargs)
 
 
-class GradientAllReducer(object):
-    """One flat-buffer all-reduce (mean over ranks) per update; identity without torch.distributed."""
+# (the carried accuracy of data-parallel runs: see `_launch_disc`)
+def _with_carry(tensors, carry):
+    """`tensors` with the carried accuracy behind them, when there is one."""
+    return tensors + [carry] if carry is not None else tensors
 
-    def __init__(self):
-        import torch.distributed as dist
-        self.dist = dist
-        # (TCGAN_DIST_SINGLE_RANK=1: run the collectives in a one-rank group as well -- the mean over one rank is the
-        # identity; bench.py uses it to put the all-reduce path through RCCL on a one-GPU box)
-        self.on = dist.is_available() and dist.is_initialized() and (
-            dist.get_world_size() > 1 or os.environ.get('TCGAN_DIST_SINGLE_RANK') == '1')
-        self.world = dist.get_world_size() if self.on else 1
-        self.rank = dist.get_rank() if self.on else 0
-        # per-phase timing for multi-GPU diagnosis (bench.py --gpus N): device time between two events around every
-        # collective, summed on demand; off by default (two event records per update)
-        self.timed = False
-        self._events = []
-        self.calls = 0                         # collectives issued so far
 
-    def collective_ms(self):
-        """Device milliseconds spent in the all-reduces since the last call (synchronises)."""
-        if not self._events:
-            return 0.0
-        torch.cuda.synchronize()
-        total = sum(a.elapsed_time(b) for a, b in self._events)
-        self._events = []
-        return total
-
-    def _sum(self, t):
-        """One all-reduce (sum) of `t`, in stream order; timed between two events when `self.timed`."""
-        self.calls += 1
-        if self.timed and t.is_cuda:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-            self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM)
-            ev[1].record()
-            self._events.append(ev)
-        else:
-            self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM)
-        if self.world > 1:
-            t /= self.world
-
-    def mean_(self, *tensors):
-        """In-place mean over ranks of several tensors through ONE collective.  A single contiguous fp32 tensor is reduced
-        where it is; several go through a persistent flat fp32 buffer (one per total size: a step alternates between a
-        few sizes, nothing is allocated per update)."""
-        if not self.on:
-            return
-        if len(tensors) == 1 and tensors[0].dtype == torch.float32 and tensors[0].is_contiguous():
-            self._sum(tensors[0])
-            return
-        n = sum(t.numel() for t in tensors)
-        flats = self.__dict__.setdefault('_flats', {})
-        key = (n, tensors[0].device)
-        flat = flats.get(key)
-        if flat is None:
-            flat = flats[key] = torch.empty(n, device=tensors[0].device, dtype=torch.float32)
-        off = 0
-        for t in tensors:
-            flat[off:off + t.numel()].copy_(t.reshape(-1))
-            off += t.numel()
-        self._sum(flat)
-        off = 0
-        for t in tensors:
-            t.copy_(flat[off:off + t.numel()].reshape(t.shape))
-            off += t.numel()
+def _split_carry(host, carried):
+    """(the accuracy that arrived as the last word of the host record, or None; the record without it)"""
+    return (float(host[-1]), host[:-1]) if carried else (None, host)
 
 
 class ConditionalBPTTWassersteinGAN(object):
@@ -273,18 +219,20 @@ class ConditionalBPTTWassersteinGAN(object):
 
     def _init_loop_state(self, seed):
         """What the update loop keeps between steps (shared with the unconditional GAN of networks/wgan.py)."""
-        gen = self.gen
         self.rng = as_randomstate(seed)
         self._predrawn = None          # host draws of the NEXT critic step, made early (see train_generator)
         self._next_ctx = None          # ... and that step itself, its forward queued behind the generator update (`_prequeue_next_disc`)
-        self._gparams_host = {}        # host values the device copies of the generator parameters correspond to
         self._rng_before_predraw = None
         self._acc_carry = None         # data-parallel runs: this rank's accuracy of the last critic step, waiting for a collective
         self._arrived_with_gen = None
+        self._warned_host_noise = False
+        self.host_draw_seconds = 0.0   # host time spent in the RNG draws of the critic steps (bench.py reads and resets it)
         self.reducer = GradientAllReducer()
-        self._pnames = [name for name, _ in gen.get_all_params()]        # ['V',] 'J', 'D', 'S'
-        self._gparams = {name: torch.zeros(int(np.size(value)), device='cuda', dtype=torch.float32)
-                         for name, value in gen.get_all_params()}
+        self.gen_state = GeneratorParamState(self.gen, self.param_bounds)    # the generator's parameters on the device
+        self._pnames = self.gen_state.names                              # ['V',] 'J', 'D', 'S'
+        self._disc_records = HostRecord(4)      # a step is read before the ring comes round: at most two steps are in flight
+        self._gen_records = HostRecord(1)
+        self.gen_forward_watch, self.gen_train_watch, self.disc_train_watch = StopWatch(), StopWatch(), StopWatch()
 
     batchsize = property(lambda self: self.num_models * self.probes_per_model)
     num_sites = property(lambda self: self.gen.num_sites)
@@ -330,7 +278,7 @@ class ConditionalBPTTWassersteinGAN(object):
         if self.reducer.on:
             per = batch.num_models // self.reducer.world
             rows = (self.reducer.rank * per, (self.reducer.rank + 1) * per)
-            if self.gen.z_host_draw and not getattr(self, '_warned_host_noise', False):
+            if self.gen.z_host_draw and not self._warned_host_noise:
                 # host draw under data parallelism: EVERY rank draws the global (num_models, 2N, 2N) fp64 tensor on the host
                 # and keeps 1/world of it, so the host cost per step grows with the job.  Meant for equivalence tests.
                 self._warned_host_noise = True
@@ -358,7 +306,7 @@ class ConditionalBPTTWassersteinGAN(object):
         batch = self.next_minibatch()
         eps_full = self.rng.rand(batch.batchsize, 1)
         noise = self._draw_noise(batch, keep_z=None if early else False)
-        self.host_draw_seconds = getattr(self, 'host_draw_seconds', 0.0) + (time.perf_counter() - t0)
+        self.host_draw_seconds += time.perf_counter() - t0
         return batch, eps_full, noise
 
     def _prepare_disc(self, params_dev=None):
@@ -378,20 +326,11 @@ class ConditionalBPTTWassersteinGAN(object):
     # longer idles through the host's way from the record to the next launch (0.16 - 0.24 ms per iteration).  The draws were
     # made early anyway (`train_generator`); `_predrawn` stays set until the prepared step is taken up, so a checkpoint in
     # between still stores the RandomState from before them and a resumed run repeats them.
-    def _prequeue_next_disc(self, st):
-        if self._predrawn is None or not _PREQUEUE or self.gen.dtype != 'float32':
+    def _prequeue_next_disc(self):
+        pd = self.gen_state.jds_v_slices()
+        if (self._predrawn is None or not _PREQUEUE or self.gen.dtype != 'float32' or pd is None
+                or not self.gen.accepts_params_dev(self._predrawn[2].get('model_zs'))):
             return None
-        noise = self._predrawn[2]
-        if not self.gen.accepts_params_dev(noise.get('model_zs')):
-            return None
-        names, offs = self._pnames, st['offs']
-        j = names.index('J')
-        if names[j:j + 3] != ['J', 'D', 'S'] or offs[j + 3] - offs[j] != 12:
-            return None
-        pd = dict(JDS=st['flat'][offs[j]:offs[j] + 12])
-        if 'V' in names:
-            v = names.index('V')
-            pd['V'] = st['flat'][offs[v]:offs[v + 1]]
         ctx = self._prepare_disc(params_dev=pd)
         ctx.prequeued_time = self.gen_forward_watch.times.pop()       # (booked on the iteration that uses the step)
         return ctx
@@ -399,13 +338,9 @@ class ConditionalBPTTWassersteinGAN(object):
     def _take_prequeued(self):
         """The critic step `_prequeue_next_disc` prepared, unless the generator's attributes were changed from outside since
         the record of the update was read (then it is prepared again from the same draws, with the attributes' values)."""
-        ctx, self._next_ctx = self.__dict__.get('_next_ctx'), None
-        if ctx is None:
+        ctx, self._next_ctx = self._next_ctx, None
+        if ctx is None or not self.gen_state.matches(self.gen):
             return None
-        for name in self._pnames:
-            cached = self._gparams_host.get(name)
-            if cached is None or not np.array_equal(cached, np.asarray(getattr(self.gen, name))):
-                return None
         self._predrawn = self._rng_before_predraw = None
         self.gen_forward_watch.times.append(ctx.prequeued_time)
         return ctx
@@ -421,10 +356,8 @@ class ConditionalBPTTWassersteinGAN(object):
             (xd, eps), cd = to_device_packed([local.tuning_curves, ctx.eps_full[r0:r0 + per]], torch.float32), None
         else:
             xd, cd, eps = to_device_packed([local.tuning_curves, local.conditions, ctx.eps_full[r0:r0 + per]], torch.float32)
-        ctx.skipped = False
+        ctx.skipped = ctx.gated = ctx.acc_deferred = False
         ctx.snapshot = None
-        ctx.gated = False
-        ctx.acc_deferred = False
         if not self.reducer.on and xg.dtype == torch.float32 and self.disc.has_step:
             # single process: the whole step is one library call (same kernels, same order); the skip rule of cwgan.py:493-498
             # is honoured by the optimizer kernel itself, which reads the rate penalty where the forward left it
@@ -432,11 +365,9 @@ class ConditionalBPTTWassersteinGAN(object):
             with self.disc_train_watch:
                 xp, tail = self.disc.step(self.disc_updater, xg, xd, cd, eps, self.lipschitz_cost, pens64=ctx.pens64,
                                           rate_penalty_bound=self.disc_rate_penalty_bound if ctx.gated else None)
-            ctx.xd, ctx.xg, ctx.xp, ctx.cd = xd, xg, xp, cd
         else:
             pens = ctx.pens64.to(torch.float32)      # [dynamics_penalty, rate_penalty] of this step's forward (averaged over ranks below)
             xp = self.disc.interpolate(eps, xd, xg)                               # cwgan.py:481
-            ctx.xd, ctx.xg, ctx.xp, ctx.cd = xd, xg, xp, cd
             # cwgan.py:493-498 skips the critic update when the rate penalty of the batch exceeds `disc_rate_penalty_bound`.
             # Waiting for that value here would stall the queue at every critic step, so the update is made
             # speculatively and rolled back in `_read_disc` (which learns the value before the next update is queued)
@@ -447,40 +378,28 @@ class ConditionalBPTTWassersteinGAN(object):
             # of the updated critic, so it only exists after this step's collective has gone; instead of its own one-float
             # all-reduce it travels in the next flat buffer (the next critic step's, or the generator's), and the step's
             # record is handed to the driver once it has arrived (`_single_gen_step`).
-            carry = self._acc_carry if self.reducer.on else None
+            carry = self._take_carry()
             with self.disc_train_watch:
                 stats = self.disc.loss_grad(xg, cd, xd, cd, xp, cd, self.lipschitz_cost)
-                self.reducer.mean_(self.disc.grads, stats, pens, *([carry] if carry is not None else []))
+                self.reducer.mean_(*_with_carry([self.disc.grads, stats, pens], carry))
                 self.disc_updater(self.disc.params, self.disc.grads)
             acc = self.disc.accuracy_device(xg, cd, xd, cd)
+            arrived = None
             if self.reducer.on:
                 self._acc_carry = acc            # this rank's share; averaged by the next collective
                 ctx.acc_deferred = True
                 arrived = carry if carry is not None else torch.full_like(acc, float('nan'))
-                tail = torch.cat([pens, stats[3:4], acc, self.disc.param_sqnorms_device(), arrived])
-            else:
-                tail = torch.cat([pens, stats[3:4], acc, self.disc.param_sqnorms_device()])
+            tail = torch.cat(_with_carry([pens, stats[3:4], acc, self.disc.param_sqnorms_device()], arrived))
         # `tail`: the four scalars of the step [dynamics penalty, rate penalty, loss, accuracy] + the per-tensor sums of squares
-        # of the updated critic (disc_param_stats); pinned buffers and events come from a small ring (a step is read before the
-        # ring comes round: at most two steps are in flight)
-        ring = self.__dict__.setdefault('_host_ring', [])
-        if not ring or ring[0][0].numel() != tail.numel():
-            ring[:] = [(torch.empty(tail.numel(), dtype=torch.float32, pin_memory=True), torch.cuda.Event()) for _ in range(4)]
-        self._host_ring_pos = (getattr(self, '_host_ring_pos', -1) + 1) % len(ring)
-        ctx.host, ctx.event = ring[self._host_ring_pos]
-        ctx.host.copy_(tail, non_blocking=True)
-        ctx.event.record()
+        # of the updated critic (disc_param_stats)
+        ctx.xd, ctx.xg, ctx.xp, ctx.cd = xd, xg, xp, cd
+        ctx.ticket = self._disc_records.post(tail)
         ctx.disc_time = self.disc_train_watch.times[-1]
 
     def _read_disc(self, info, ctx):
         """Wait for the scalars of a launched step (only for its own kernels: later launches are not waited for)."""
-        if ctx.event is not None:
-            ctx.event.synchronize()
-        host = ctx.host.numpy().copy()               # (the pinned buffer goes back to the ring)
-        ctx.arrived_accuracy = None
-        if ctx.acc_deferred:
-            # last word: the job-wide accuracy of the PREVIOUS critic step, which travelled in this step's collective
-            ctx.arrived_accuracy, host = float(host[-1]), host[:-1]
+        # (deferred: the last word is the job-wide accuracy of the PREVIOUS critic step, which travelled in this step's collective)
+        ctx.arrived_accuracy, host = _split_carry(ctx.ticket.wait(), ctx.acc_deferred)
         if (ctx.snapshot is not None or ctx.gated) and np.float32(host[1]) > np.float32(self.disc_rate_penalty_bound):
             if ctx.gated:
                 self.disc_updater.uncommit_step()                                # (the kernel made no update: same test, same value)
@@ -504,6 +423,11 @@ class ConditionalBPTTWassersteinGAN(object):
         info.disc_time = np.nan if ctx.skipped else ctx.disc_time
         return info
 
+    def _take_carry(self):
+        """The accuracy waiting for a collective (data-parallel runs), handed to the caller whose collective takes it along."""
+        carry, self._acc_carry = (self._acc_carry if self.reducer.on else None), None
+        return carry
+
     def _flush_accuracy(self):
         """The job-wide mean of the accuracy still waiting for a collective, through one of its own (outside the loop's
         schedule: `train_discriminator` called by hand, the end of a run)."""
@@ -525,11 +449,6 @@ class ConditionalBPTTWassersteinGAN(object):
     def train_discriminator(self, info):
         return self._finish_disc(info, self._prepare_disc())
 
-    def _mean_scalar(self, t):
-        t = t.reshape(1).to(torch.float32).clone()
-        self.reducer.mean_(t)
-        return float(t[0])
-
     def _prepare_gen(self, batch):
         """Noise draw + generator forward with the trajectory kept (independent of the critic: may be queued before
         the last critic step of the iteration has finished)."""
@@ -547,57 +466,18 @@ class ConditionalBPTTWassersteinGAN(object):
         if self.critic_iters > 0 and self._predrawn is None:
             self._rng_before_predraw = self.rng.get_state()
             self._predrawn = self._draw_disc(early=True)
-        fused = self._gen_tail_fused()
+        st = self._gen_tail_fused()
         with self.gen_train_watch:
             cd = None if local.conditions is None else to_device(np.ascontiguousarray(local.conditions), torch.float32)
             xg = gen_out.prober_tuning_curve.to(torch.float32)
-            nb = xg.shape[0]
-            gx, dmean = self.disc.input_grad(xg, cd, scale=-1.0 / nb)           # d(-mean D)/d tuning curve
-            if fused is not None:
-                self._gen_step_now = getattr(info, 'gen_step', '?')
-                host = self._train_generator_tail(fused, gx, dmean)
-                info.gen_loss = float(host[-1])
-                if not np.isfinite(host).all():
-                    self._report_poisoned(info, gen_out)
-        if fused is not None:
-            info.gen_forward_time = self.gen_forward_watch.sum()
-            info.gen_train_time = self.gen_train_watch.sum()
-            info.gen_time = info.gen_train_time + info.gen_forward_time
-            info.disc_time = self.disc_train_watch.sum()
-            return info
-        with self.gen_train_watch:
-            gdict = self.gen.backward(gx, self.dynamics_cost, self.rate_cost, as_tensor=True)
-            loss = (-dmean.to(torch.float64) + self.dynamics_cost * gen_out.model_dynamics_penalty
-                    + self.rate_cost * gen_out.model_rate_penalty).reshape(1).to(torch.float32)
-            grads = torch.cat([gdict[name].reshape(-1) for name in self._pnames]).to(torch.float32)
-            # (the accuracy of the last critic step rides in the generator's collective: see `_launch_disc`)
-            carry, self._acc_carry = (self._acc_carry if self.reducer.on else None), None
-            self.reducer.mean_(grads, loss, *([carry] if carry is not None else []))
-            # Everything up to here is queued without a host wait; the device copies of the parameters are the
-            # working values (re-uploaded only when somebody changed the generator's attributes from outside), and ONE
-            # device-to-host copy at the end returns the new parameter values together with the loss.
-            off = 0
-            for name in self._pnames:                                            # wgan.py:218-260
-                value = np.asarray(getattr(self.gen, name))
-                p = self._gparams[name]
-                cached = self._gparams_host.get(name)
-                if cached is None or cached.shape != value.shape or not np.array_equal(cached, value):
-                    p.copy_(to_device(np.ascontiguousarray(value, dtype='float32').ravel()))
-                self.gen_updaters[name](p, grads[off:off + p.numel()], clip=self.param_bounds[name])
-                off += p.numel()
-            host = torch.cat([self._gparams[name] for name in self._pnames] + [loss]
-                             + ([carry.to(torch.float32)] if carry is not None else [])).cpu().numpy()
-            self._arrived_with_gen = None
-            if carry is not None:
-                self._arrived_with_gen, host = float(host[-1]), host[:-1]
-            off = 0
-            for name in self._pnames:
-                shape = np.shape(getattr(self.gen, name))
-                n = int(np.prod(shape, dtype=int))
-                new = host[off:off + n].astype('float64').reshape(shape)
-                setattr(self.gen, name, new)
-                self._gparams_host[name] = new.copy()
-                off += n
+            gx, dmean = self.disc.input_grad(xg, cd, scale=-1.0 / xg.shape[0])           # d(-mean D)/d tuning curve
+            # Everything up to the record is queued without a host wait; the device copies of the parameters are the working
+            # values, and ONE device-to-host copy at the end returns the new values together with the loss.
+            if st is None:
+                host = self._gen_tail_by_parameter(gen_out, gx, dmean)
+            else:
+                host = self._gen_tail_one_launch(st, info, gx, dmean)
+            self.gen_state.write_back(self.gen, host)
             info.gen_loss = float(host[-1])
             if not np.isfinite(host).all():
                 self._report_poisoned(info, gen_out)
@@ -614,88 +494,64 @@ class ConditionalBPTTWassersteinGAN(object):
             logger.warning('generator step %s: %d of %d draws have an adjoint that grew by more than 2^8 within one '
                            'Euler step -- beyond the lagged scale of the fp16-split sweep, so their gradient is NaN; '
                            '--gen-kernel mfma-fp32 has no such limit', getattr(info, 'gen_step', '?'), bad,
-                           gen_out.prober_tuning_curve.shape[0] // max(getattr(self, 'probes_per_model', 1), 1))
+                           gen_out.prober_tuning_curve.shape[0] // max(self.probes_per_model, 1))
 
-    # -- the end of a generator step in two library calls (`ssn_gen_grads_f32`, `ssn_gen_apply_f32`) --------------------------
+    # -- the end of a generator step: both tails return the record on the host (new values in `_pnames` order, loss) -----------
     def _gen_tail_fused(self):
-        """The flat device state of the generator's update (parameters, optimizer moments, clip bounds in `_pnames` order), or
+        """The flat device state of the generator's update (`GeneratorParamState`) with the updaters' moments bound to it, or
         None when the step has to go parameter by parameter: a generator in float64, or updaters that are not in step with
-        each other (same rule, hyper-parameters and step count: `make_gan` builds them that way)."""
-        ups = [self.gen_updaters[name] for name in self._pnames]
-        sig = {(u.kind, u.learning_rate, tuple(sorted(u.cfg.items())), tuple(u.reg), u.step) for u in ups}
-        if len(sig) != 1 or self.gen.dtype != 'float32':
+        each other."""
+        st = self.gen_state
+        if not st.in_step(self.gen_updaters, self.gen.dtype):
             return None
-        st = self.__dict__.get('_gflat')
-        if st is None:
-            sizes = [int(self._gparams[name].numel()) for name in self._pnames]
-            offs = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
-            n = int(offs[-1])
-            flat = torch.cat([self._gparams[name] for name in self._pnames])
-            lo = np.concatenate([np.broadcast_to(np.asarray(self.param_bounds[name][0], dtype='float32').ravel(), (k,))
-                                 for name, k in zip(self._pnames, sizes)])
-            hi = np.concatenate([np.broadcast_to(np.asarray(self.param_bounds[name][1], dtype='float32').ravel(), (k,))
-                                 for name, k in zip(self._pnames, sizes)])
-            st = self._gflat = dict(n=n, offs=offs, flat=flat, m=torch.zeros_like(flat), v=torch.zeros_like(flat),
-                                    lo=to_device(lo), hi=to_device(hi), record=torch.empty(n + 1, device='cuda', dtype=torch.float32))
-            for i, name in enumerate(self._pnames):          # the per-name device copies become views of the flat vector
-                self._gparams[name] = flat[offs[i]:offs[i + 1]]
-        for i, name in enumerate(self._pnames):               # ... and so do the updaters' moments (checkpoints read them there)
-            u, a, b = self.gen_updaters[name], st['offs'][i], st['offs'][i + 1]
-            mine = (st['m'][a:b], st['v'][a:b])
-            if u._state is None:
-                mine[0].zero_(); mine[1].zero_()
-                u._state = mine
-            elif u._state[0].data_ptr() != mine[0].data_ptr():           # (restored from a checkpoint: take the values over)
-                mine[0].copy_(u._state[0].reshape(-1)); mine[1].copy_(u._state[1].reshape(-1))
-                u._state = mine
+        st.bind_moments(self.gen_updaters)
         return st
 
-    def _train_generator_tail(self, st, gx, dmean):
-        """Adjoint sweep, dL/dW, chain rule; then gradient vector + loss in one launch, the job's all-reduce, and the update of
-        all parameters with their bounds + the record in one more.  Returns the record on the host: new values, loss."""
-        import ctypes
-        pieces = self.gen.backward(gx, self.dynamics_cost, self.rate_cost, raw=True)
-        from .. import genops
-        gl = genops.gen_grads(pieces['parts'], dmean, self.gen.last_penalties, self.dynamics_cost, self.rate_cost,
-                              nv=pieces['nv'], g_ext=pieces.get('g_ext'), ext_base=pieces.get('ext_base'), zin=pieces.get('zin'))
-        # (the accuracy of the last critic step rides in the generator's collective: see `_launch_disc`)
-        carry, self._acc_carry = (self._acc_carry if self.reducer.on else None), None
-        self.reducer.mean_(gl, *([carry] if carry is not None else []))
-        for name in self._pnames:                                                # wgan.py:218-260
-            value = np.asarray(getattr(self.gen, name))
-            cached = self._gparams_host.get(name)
-            if cached is None or cached.shape != value.shape or not np.array_equal(cached, value):
-                self._gparams[name].copy_(to_device(np.ascontiguousarray(value, dtype='float32').ravel()))
-        u0 = self.gen_updaters[self._pnames[0]]
+    def _gen_tail_by_parameter(self, gen_out, gx, dmean):
+        """Gradients and loss with torch, the job's all-reduce, one optimizer launch per parameter."""
+        st = self.gen_state
+        gdict = self.gen.backward(gx, self.dynamics_cost, self.rate_cost, as_tensor=True)
+        loss = (-dmean.to(torch.float64) + self.dynamics_cost * gen_out.model_dynamics_penalty
+                + self.rate_cost * gen_out.model_rate_penalty).reshape(1).to(torch.float32)
+        grads = torch.cat([gdict[name].reshape(-1) for name in st.names]).to(torch.float32)
+        carry = self._take_carry()
+        self.reducer.mean_(*_with_carry([grads, loss], carry))
+        st.upload_changed(self.gen)
+        for name, (a, b) in zip(st.names, st.ranges()):                          # wgan.py:218-260
+            self.gen_updaters[name](st.params[name], grads[a:b], clip=self.param_bounds[name])
+        host = torch.cat(_with_carry([st.flat, loss], carry)).cpu().numpy()
+        self._arrived_with_gen, host = _split_carry(host, carry is not None)
+        return host
+
+    def _gen_tail_one_launch(self, st, info, gx, dmean):
+        """Adjoint sweep, dL/dW, chain rule; then gradient vector + loss in one launch (`ssn_gen_grads_f32`), the job's
+        all-reduce, and the update of all parameters with their bounds + the record in one more (`ssn_gen_apply_f32`)."""
+        pens = self.gen.last_penalties
+
+        def grads_and_loss(pieces):
+            return genops.gen_grads(pieces['parts'], dmean, pens, self.dynamics_cost, self.rate_cost, nv=pieces['nv'],
+                                    g_ext=pieces.get('g_ext'), ext_base=pieces.get('ext_base'), zin=pieces.get('zin'))
 
         def apply(gl, gate):
-            _, _, opt = u0.begin_step(st['flat'][:self._gparams[self._pnames[0]].numel()])
-            opt.clip = 0
+            _, _, opt = self.gen_updaters[st.names[0]].begin_step(st.params[st.names[0]])
             opt.reserved = int(gate)          # bit 0: no update at all when a gradient element is not finite (record[n] = NaN)
-            clib.check(clib.libssnode.ssn_gen_apply_f32(st['flat'].data_ptr(), gl.data_ptr(), st['m'].data_ptr(), st['v'].data_ptr(),
-                                                        st['n'], ctypes.byref(opt), st['lo'].data_ptr(), st['hi'].data_ptr(),
-                                                        st['record'].data_ptr(), clib.stream_ptr()), 'ssn_gen_apply_f32')
+            clib.check(clib.libssnode.ssn_gen_apply_f32(st.flat.data_ptr(), gl.data_ptr(), st.m.data_ptr(), st.v.data_ptr(),
+                                                        st.n, ctypes.byref(opt), st.lo.data_ptr(), st.hi.data_ptr(),
+                                                        st.record.data_ptr(), clib.stream_ptr()), 'ssn_gen_apply_f32')
             return opt
 
+        pieces = self.gen.backward(gx, self.dynamics_cost, self.rate_cost, raw=True)
+        gl = grads_and_loss(pieces)
+        carry = self._take_carry()
+        self.reducer.mean_(*_with_carry([gl], carry))
+        st.upload_changed(self.gen)
         opt = apply(gl, gate=True)
-        pens = self.gen.last_penalties
-        tail = [st['record']] + ([carry.to(torch.float32)] if carry is not None else [])
-        rec = torch.cat(tail) if len(tail) > 1 else tail[0]
         # the record's copy is queued BEFORE the next step's forward and waited for by its own event: a plain .cpu() behind the
         # forward would wait for the forward too
-        pin = self.__dict__.get('_gen_record_pin')
-        if pin is None or pin[0].numel() != rec.numel():
-            pin = self._gen_record_pin = (torch.empty(rec.numel(), dtype=torch.float32, pin_memory=True),
-                                          torch.cuda.Event())
-        pin[0].copy_(rec, non_blocking=True)
-        pin[1].record()
-        self._next_ctx = self._prequeue_next_disc(st)
-        pin[1].synchronize()
-        host = pin[0].numpy().copy()
-        arrived = None
-        if carry is not None:
-            arrived, host = float(host[-1]), host[:-1]
-        if np.isnan(host[-1]) and np.isfinite(host[:-1]).all() and self.gen.__dict__.get('_retry') is not None:
+        ticket = self._gen_records.post(st.record if carry is None else torch.cat([st.record, carry]))
+        self._next_ctx = self._prequeue_next_disc()
+        self._arrived_with_gen, host = _split_carry(ticket.wait(), carry is not None)
+        if np.isnan(host[-1]) and np.isfinite(host[:-1]).all() and self.gen.can_retry:
             # The update was withheld: the summed gradient is not finite.  With the fp16-split adjoint that is what a draw whose
             # adjoint grows by more than 2^8 within one Euler step gives (unstable dynamics: NaN by construction, never a
             # clamped value); the reference's fp32 arithmetic carries such a draw's large finite gradient.  So does the fp32
@@ -704,7 +560,7 @@ class ConditionalBPTTWassersteinGAN(object):
             bad = self.gen.poisoned_draws()
             logger.warning('generator step %s: %d draws have an adjoint that grew by more than 2^8 within one Euler step, beyond '
                            'the lagged scale of the fp16-split sweep; they are recomputed on the fp32 kernels (gen_kernel '
-                           'mfma-fp32 runs every step there)', getattr(self, '_gen_step_now', '?'), bad)
+                           'mfma-fp32 runs every step there)', getattr(info, 'gen_step', '?'), bad)
             self._next_ctx = None          # (prepared with the parameters the withheld update left: prepared again later)
             idx = self.gen.poisoned_draw_indices()
             nb = int(pieces['parts'].shape[0])
@@ -722,28 +578,16 @@ class ConditionalBPTTWassersteinGAN(object):
                 pieces = dict(pieces, parts=parts, g_ext=g_ext)
             else:
                 pieces = self.gen.backward(gx, self.dynamics_cost, self.rate_cost, raw=True, exact=True)
-            gl = genops.gen_grads(pieces['parts'], dmean, pens, self.dynamics_cost, self.rate_cost,
-                                  nv=pieces['nv'], g_ext=pieces.get('g_ext'), ext_base=pieces.get('ext_base'), zin=pieces.get('zin'))
+            gl = grads_and_loss(pieces)
             self.reducer.mean_(gl)
             opt = apply(gl, gate=False)
-            host = st['record'].cpu().numpy()
-        for name in self._pnames:
+            host = st.record.cpu().numpy()
+        for name in st.names:
             self.gen_updaters[name].commit_step(opt)
-        self._arrived_with_gen = arrived
-        off = 0
-        for name in self._pnames:
-            shape = np.shape(getattr(self.gen, name))
-            n = int(np.prod(shape, dtype=int))
-            new = host[off:off + n].astype('float64').reshape(shape)
-            setattr(self.gen, name, new)
-            self._gparams_host[name] = new.copy()
-            off += n
         return host
 
     def _single_gen_step(self, gen_step, critic_iters):
-        self.gen_forward_watch = StopWatch()
-        self.gen_train_watch = StopWatch()
-        self.disc_train_watch = StopWatch()
+        self.gen_forward_watch, self.gen_train_watch, self.disc_train_watch = StopWatch(), StopWatch(), StopWatch()
         ctx = (self._take_prequeued() or self._prepare_disc()) if critic_iters > 0 else None
         prepared_gen = None
         self._acc_carry = None
@@ -790,13 +634,10 @@ class ConditionalBPTTWassersteinGAN(object):
     def learning(self, start_step=0):
         """wgan.py:439-444: `critic_iters_init` critic steps before generator step 0, then `critic_iters`.
         `start_step` > 0 continues a run restored with `load_state_dict` (no second initial critic phase)."""
-        import itertools
         if start_step == 0:
-            for info in self._single_gen_step(0, self.critic_iters_init):
-                yield info
+            yield from self._single_gen_step(0, self.critic_iters_init)
         for gen_step in itertools.count(max(start_step, 1)):
-            for info in self._single_gen_step(gen_step, self.critic_iters):
-                yield info
+            yield from self._single_gen_step(gen_step, self.critic_iters)
 
     # -- checkpoints (not in the reference: its runs cannot be resumed) -------------------------------------
     def state_dict(self):
@@ -842,7 +683,6 @@ class ConditionalBPTTWassersteinGAN(object):
     CHECKPOINT_VERSION = 2          # 2: Philox (seed, position) device-noise state, gen_kernel and world recorded
 
     def save_checkpoint(self, path, gen_step):
-        import pickle
         tmp = path + '.tmp'
         with open(tmp, 'wb') as f:
             pickle.dump(dict(version=self.CHECKPOINT_VERSION, gen_step=int(gen_step), state=self.state_dict()), f, protocol=4)
@@ -850,7 +690,6 @@ class ConditionalBPTTWassersteinGAN(object):
 
     def load_checkpoint(self, path):
         """Restore a checkpoint (after `set_dataset`); returns the generator step to continue WITH."""
-        import pickle
         with open(path, 'rb') as f:
             ck = pickle.load(f)
         if not isinstance(ck, dict) or ck.get('version') not in (1, self.CHECKPOINT_VERSION) or 'state' not in ck:
@@ -859,15 +698,6 @@ class ConditionalBPTTWassersteinGAN(object):
                              exit_code=5)
         self.load_state_dict(ck['state'])
         return ck['gen_step'] + 1
-
-
-def _v_bounds(v_min, v_max, ssn_type):
-    """Clip bounds of the input-variability parameter V (wgan.py:244-251, 263-283): one (V_E, V_I) pair each for
-    'heteroin' -- per element, like numpy's broadcasting clip in the reference -- a scalar each for 'deg-heteroin'."""
-    if ssn_type == 'heteroin':
-        return (np.broadcast_to(np.asarray(v_min, dtype='float64'), (2,)).copy(),
-                np.broadcast_to(np.asarray(v_max, dtype='float64'), (2,)).copy())
-    return float(np.min(v_min)), float(np.max(v_max))
 
 
 def make_gan(config):
@@ -886,35 +716,14 @@ def make_gan(config):
     probes_per_model = take('probes_per_model')
     bandwidths = take('bandwidths')
     contrasts = take('contrasts')
-    num_sites = take('num_sites')
-    ssn_type = take('ssn_type', 'default')
-    ssn_impl = take('ssn_impl', 'default')
-    if ssn_impl not in ('default', 'mapclone'):     # 'mapclone' is the same arithmetic organised differently (ssn.py:25-30)
-        raise ValueError('Unknown ssn_impl: {}'.format(ssn_impl))
-    if 'V0' in kwargs:                              # cwgan.py:570-571
-        kwargs['V'] = kwargs.pop('V0')
-    V = kwargs.pop('V', 0)
-    dist_in = kwargs.pop('dist_in', 'bernoulli')
-    for key in ('V_min', 'V_max'):
-        kwargs.pop(key, None)
-    reducer = GradientAllReducer()
-    local_models = num_models // reducer.world
     # (the command line's --gen-kernel arrives as gen['kernel']: run scripts group their gen_* options; configs written
     # by hand may also say gen_kernel at the top level)
     gen_kernel = gen_cfg.pop('kernel', None) or take('gen_kernel', 'auto')
     kwargs.pop('gen_kernel', None)
-    gen = TuningCurveGenerator(
-        num_sites=num_sites, num_tcdom=len(bandwidths), smoothness=take('smoothness'),
-        J=take('J0'), D=take('D0'), S=take('S0'), k=take('k'), n=take('n'),
-        tau_E=take('tau_E'), tau_I=take('tau_I'), dt=take('dt'), io_type=take('io_type'),
-        seqlen=take('seqlen'), skip_steps=take('skip_steps'),
-        batchsize=local_models * probes_per_model,
-        include_rate_penalty=take('include_rate_penalty', True),
-        include_time_avg=take('include_time_avg', False),
-        unroll_scan=take('unroll_scan', False),
-        dtype=take('gen_dtype', 'float32'),
-        z_device_seed=take('z_device_seed', None), shard=(reducer.rank, reducer.world),
-        ssn_type=ssn_type, V=V, dist_in=dist_in, gen_kernel=gen_kernel, z_host_draw=take('z_host_draw', False))
+    gen, ssn_type = build_generator(kwargs, gen_kernel, len(bandwidths),
+                                    num_models // GradientAllReducer().world * probes_per_model)
+    for key in ('V_min', 'V_max'):
+        kwargs.pop(key, None)
     rate_penalty_threshold = gen_cfg.pop('rate_penalty_threshold')
     disc_rate_penalty_bound = disc_cfg.pop('rate_penalty_bound')
     seed = take('seed', 0)
@@ -924,29 +733,16 @@ def make_gan(config):
                   hide_cell_type=take('hide_cell_type'),
                   precision=disc_cfg.pop('precision', 'fp32'),
                   seed=disc_cfg.pop('init_seed', seed), net_options=disc_cfg.pop('net_options', None))
-
-    def updater_from(cfg):
-        return Updater(**{k: cfg.pop(k) for k in ('learning_rate', 'update_name', 'update_config', 'reg_l2_penalty',
-                                                   'reg_l2_decay', 'reg_l1_penalty', 'reg_l1_decay') if k in cfg})
-
-    dynamics_cost = gen_cfg.pop('dynamics_cost', 1.0)
-    rate_cost = gen_cfg.pop('rate_cost')
-    bounds = {name: (gen_cfg.pop(name + '_min', 1e-3), gen_cfg.pop(name + '_max', 10.0)) for name in 'JDS'}
-    bounds['V'] = _v_bounds(gen_cfg.pop('V_min', 0), gen_cfg.pop('V_max', 1), ssn_type)   # wgan.py:263-283
-    gen_upd_cfg = {k: gen_cfg.pop(k) for k in list(gen_cfg) if k in ('learning_rate', 'update_name', 'update_config',
-                                                                     'reg_l2_penalty', 'reg_l2_decay',
-                                                                     'reg_l1_penalty', 'reg_l1_decay')}
-    gen_updaters = {name: Updater(**gen_upd_cfg) for name in 'VJDS'}
+    parts = generator_trainer_parts(gen_cfg, ssn_type)
     disc_updater = updater_from(disc_cfg)
     if gen_cfg or disc_cfg:
         raise ValueError('Unknown trainer options: gen={} disc={}'.format(sorted(gen_cfg), sorted(disc_cfg)))
     gan = ConditionalBPTTWassersteinGAN(
-        gen, disc, gen_updaters, disc_updater, bandwidths, contrasts,
+        gen=gen, disc=disc, disc_updater=disc_updater, bandwidths=bandwidths, contrasts=contrasts,
         norm_probes=take('norm_probes'), e_ratio=take('e_ratio'),
         include_inhibitory_neurons=take('include_inhibitory_neurons'),
         rate_penalty_threshold=rate_penalty_threshold,
         num_models=num_models, probes_per_model=probes_per_model,
         critic_iters_init=take('critic_iters_init'), critic_iters=take('critic_iters'),
-        lipschitz_cost=take('lipschitz_cost'), disc_rate_penalty_bound=disc_rate_penalty_bound,
-        dynamics_cost=dynamics_cost, rate_cost=rate_cost, param_bounds=bounds, seed=seed)
+        lipschitz_cost=take('lipschitz_cost'), disc_rate_penalty_bound=disc_rate_penalty_bound, seed=seed, **parts)
     return gan, kwargs

@@ -14,11 +14,10 @@ import torch
 
 from .. import clib
 from ..clib import libssnode
-from ..critic import Updater
 from ..utils import Namespace, StopWatch, as_randomstate
-from .cwgan import _v_bounds, GradientAllReducer
-from .ssn import TuningCurveGenerator
-from .wgan import DEFAULT_PARAMS as _WGAN_DEFAULTS, grid_stimulator_inputs, probes_from_stim_space
+from ._common import (DEFAULT_PARAMS as _WGAN_DEFAULTS, GradientAllReducer, build_generator, generator_trainer_parts,
+                      grid_stimulator_inputs, probes_from_stim_space)
+from .gen_state import GeneratorParamState
 
 # moment_matching.py:17-23
 DEFAULT_PARAMS = dict(_WGAN_DEFAULTS, moment_weight_type='mean', **_WGAN_DEFAULTS['gen'])
@@ -75,9 +74,8 @@ class GeneratorStepTrainer(object):
         self.dynamics_cost = dynamics_cost
         self.rate_cost = rate_cost
         self.param_bounds = param_bounds
-        self._pnames = [name for name, _ in gen.get_all_params()]
-        self._gparams = {name: torch.zeros(int(np.size(value)), device='cuda', dtype=torch.float32)
-                         for name, value in gen.get_all_params()}
+        self.gen_state = GeneratorParamState(gen, param_bounds)
+        self._pnames = self.gen_state.names
 
     batchsize = property(lambda self: self.global_batchsize)
     num_neurons = property(lambda self: self.gen.num_neurons)
@@ -124,14 +122,13 @@ class GeneratorStepTrainer(object):
         grads = torch.as_tensor(np.concatenate([np.ravel(gdict[name]) for name in self._pnames]), device='cuda',
                                 dtype=torch.float32)
         self.reducer.mean_(grads, pens)
-        off = 0
-        for name in self._pnames:                                  # moment_matching.py:245-257 (clip_params)
-            value = np.asarray(getattr(self.gen, name))
-            p = self._gparams[name]
-            p.copy_(torch.as_tensor(np.array(value).ravel(), dtype=torch.float32))
-            self.gen_updaters[name](p, grads[off:off + p.numel()], clip=self.param_bounds[name])
-            off += p.numel()
-            setattr(self.gen, name, p.cpu().numpy().astype('float64').reshape(value.shape))
+        st = self.gen_state
+        st.upload_changed(self.gen)
+        host = []
+        for name, (a, b) in zip(st.names, st.ranges()):           # moment_matching.py:245-257 (clip_params)
+            self.gen_updaters[name](st.params[name], grads[a:b], clip=self.param_bounds[name])
+            host.append(st.params[name].cpu().numpy())
+        st.write_back(self.gen, np.concatenate(host))
         info.dynamics_penalty = float(pens[0])
         info.rate_penalty = float(pens[1])
         info.loss = l0 + self.dynamics_cost * info.dynamics_penalty + self.rate_cost * info.rate_penalty
@@ -193,37 +190,18 @@ def generator_step_parts(kwargs):
     """Takes from `kwargs` (a config over the defaults, consumed in place) what `GeneratorStepTrainer._init_generator_step`
     needs -- the generator, one updater per parameter, the bounds, the costs -- and returns it as keyword arguments."""
     take = kwargs.pop
-    bandwidths, contrasts, num_sites = take('bandwidths'), take('contrasts'), take('num_sites')
+    bandwidths, contrasts = take('bandwidths'), take('contrasts')
     include_inhibitory_neurons = take('include_inhibitory_neurons')
-    probes = probes_from_stim_space(take('sample_sites'), num_sites, include_inhibitory_neurons)
-    ssn_type = take('ssn_type', 'default')
-    ssn_impl = take('ssn_impl', 'default')
-    if ssn_impl not in ('default', 'mapclone'):
-        raise ValueError('Unknown ssn_impl: {}'.format(ssn_impl))
-    if 'V0' in kwargs:
-        kwargs['V'] = kwargs.pop('V0')
-    V = kwargs.pop('V', 0)
-    dist_in = kwargs.pop('dist_in', 'bernoulli')
-    reducer = GradientAllReducer()
+    probes = probes_from_stim_space(take('sample_sites'), kwargs['num_sites'], include_inhibitory_neurons)
+    world = GradientAllReducer().world
     batchsize = take('batchsize')
-    assert batchsize % reducer.world == 0, 'batchsize must be divisible by the number of ranks'
-    gen = TuningCurveGenerator(
-        num_sites=num_sites, num_tcdom=len(bandwidths) * len(contrasts), smoothness=take('smoothness'),
-        J=take('J0'), D=take('D0'), S=take('S0'), k=take('k'), n=take('n'), tau_E=take('tau_E'), tau_I=take('tau_I'),
-        dt=take('dt'), io_type=take('io_type'), seqlen=take('seqlen'), skip_steps=take('skip_steps'),
-        batchsize=batchsize // reducer.world, probes=probes, include_rate_penalty=True,
-        include_time_avg=take('include_time_avg', False), unroll_scan=take('unroll_scan', False),
-        dtype=take('gen_dtype', 'float32'), z_device_seed=take('z_device_seed', None),
-        shard=(reducer.rank, reducer.world),
-        ssn_type=ssn_type, V=V, dist_in=dist_in, gen_kernel=take('gen_kernel', 'auto'), z_host_draw=take('z_host_draw', False))
-    bounds = {name: (take(name + '_min', 1e-3), take(name + '_max', 10.0)) for name in 'JDS'}
-    bounds['V'] = _v_bounds(take('V_min', 0), take('V_max', 1), ssn_type)
-    upd_cfg = {k: take(k) for k in ('learning_rate', 'update_name', 'update_config', 'reg_l2_penalty', 'reg_l2_decay',
-                                    'reg_l1_penalty', 'reg_l1_decay') if k in kwargs}
-    return dict(gen=gen, gen_updaters={name: Updater(**upd_cfg) for name in 'VJDS'}, bandwidths=bandwidths,
-                contrasts=contrasts, include_inhibitory_neurons=include_inhibitory_neurons,
-                rate_penalty_threshold=take('rate_penalty_threshold'), dynamics_cost=take('dynamics_cost', 1.0),
-                rate_cost=take('rate_cost'), param_bounds=bounds, seed=take('seed', 0))
+    assert batchsize % world == 0, 'batchsize must be divisible by the number of ranks'
+    gen, ssn_type = build_generator(kwargs, take('gen_kernel', 'auto'), len(bandwidths) * len(contrasts), batchsize // world,
+                                    probes=probes, include_rate_penalty=True)
+    parts = generator_trainer_parts(kwargs, ssn_type)
+    return dict(parts, gen=gen, bandwidths=bandwidths, contrasts=contrasts,
+                include_inhibitory_neurons=include_inhibitory_neurons,
+                rate_penalty_threshold=take('rate_penalty_threshold'), seed=take('seed', 0))
 
 
 def make_moment_matcher(config):

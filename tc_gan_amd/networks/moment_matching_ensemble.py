@@ -31,6 +31,7 @@ from .. import clib, genops
 from ..clib import libssnode
 from ..stimuli import stimulus_batch
 from ..utils import Namespace, StopWatch, to_device
+from .gen_state import flat_bounds
 from .moment_matching import DEFAULT_PARAMS, make_moment_matcher
 from .ssn import TAIL_KINDS, _ticket_finisher
 
@@ -148,15 +149,8 @@ class EnsembleGeneratorStep(object):
         mms = [self.members[i] for i in self.active]
         dev = dict(device='cuda')
         params = np.stack([np.asarray(mm.gen.get_flat_param_values(), dtype='float64') for mm in mms]).astype(np.float32)
-        lo, hi = [], []
-        for mm in mms:
-            l, h = [], []
-            for name, value in mm.gen.get_all_params():
-                b = mm.param_bounds[name]
-                size = int(np.size(value))
-                l.extend(np.broadcast_to(np.asarray(b[0], dtype='float32').ravel(), (size,)))
-                h.extend(np.broadcast_to(np.asarray(b[1], dtype='float32').ravel(), (size,)))
-            lo.append(l); hi.append(h)
+        lo, hi = zip(*[flat_bounds([np.size(value) for _, value in mm.gen.get_all_params()],
+                                   [mm.param_bounds[name] for name, _ in mm.gen.get_all_params()]) for mm in mms])
         st = dict(p=torch.as_tensor(params, **dev).contiguous(),
                   clip_lo=torch.as_tensor(np.asarray(lo, dtype=np.float32), **dev).contiguous(),
                   clip_hi=torch.as_tensor(np.asarray(hi, dtype=np.float32), **dev).contiguous(),

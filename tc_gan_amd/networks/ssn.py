@@ -346,7 +346,9 @@ class TuningCurveGenerator(object):
         # reference-stream mode (no z_device_seed): `zs = rng.rand(...)` of the caller's RandomState is generated on the device,
         # bit for bit (`device_rand`); z_host_draw = True keeps the draw on the host (numpy itself: the A/B of the tests)
         self.z_host_draw = bool(z_host_draw)
+        self._retry = None          # what `backward(exact=True)` recomputes from: kept by a backward on the fp16-split kernels
 
+    can_retry = property(lambda self: self._retry is not None)
     num_neurons = property(lambda self: 2 * self.num_sites)
     conditional = property(lambda self: self.probes is None)
     output_shape = property(lambda self: (self.batchsize, self.num_tcdom if self.conditional

@@ -14,11 +14,11 @@ whether the critic sees condition columns -- nothing else, so only that is writt
 """
 import numpy as np
 
-from ..critic import Critic, Updater
+from ..critic import Critic
 from ..utils import random_minibatches
-from ._common import DEFAULT_PARAMS, grid_stimulator_inputs, probes_from_stim_space  # noqa: F401  (re-exported)
-from .cwgan import ConditionalBPTTWassersteinGAN, GradientAllReducer, _v_bounds
-from .ssn import TuningCurveGenerator
+from ._common import (DEFAULT_PARAMS, GradientAllReducer, build_generator, generator_trainer_parts,  # noqa: F401
+                      grid_stimulator_inputs, probes_from_stim_space, updater_from)       # (the helpers are re-exported)
+from .cwgan import ConditionalBPTTWassersteinGAN
 
 
 def UnConditionalDiscriminator(shape, layers, normalization='none', nonlinearity='rectify', loss_type='WD',
@@ -105,32 +105,15 @@ def make_gan(config):
     take = kwargs.pop
 
     bandwidths, contrasts = take('bandwidths'), take('contrasts')
-    num_sites = take('num_sites')
     include_inhibitory_neurons = take('include_inhibitory_neurons')
-    probes = probes_from_stim_space(take('sample_sites'), num_sites, include_inhibitory_neurons)
-    ssn_type = take('ssn_type', 'default')
-    ssn_impl = take('ssn_impl', 'default')
-    if ssn_impl not in ('default', 'mapclone'):
-        raise ValueError('Unknown ssn_impl: {}'.format(ssn_impl))
-    if 'V0' in kwargs:                              # wgan.py:471-472
-        kwargs['V'] = kwargs.pop('V0')
-    V = kwargs.pop('V', 0)
-    dist_in = kwargs.pop('dist_in', 'bernoulli')
-    for key in ('V_min', 'V_max'):
-        kwargs.pop(key, None)
-    reducer = GradientAllReducer()
+    probes = probes_from_stim_space(take('sample_sites'), kwargs['num_sites'], include_inhibitory_neurons)
     batchsize = take('batchsize')
     gen_kernel = gen_cfg.pop('kernel', None) or take('gen_kernel', 'auto')
     kwargs.pop('gen_kernel', None)
-    gen = TuningCurveGenerator(
-        num_sites=num_sites, num_tcdom=len(bandwidths) * len(contrasts), smoothness=take('smoothness'),
-        J=take('J0'), D=take('D0'), S=take('S0'), k=take('k'), n=take('n'),
-        tau_E=take('tau_E'), tau_I=take('tau_I'), dt=take('dt'), io_type=take('io_type'),
-        seqlen=take('seqlen'), skip_steps=take('skip_steps'), batchsize=batchsize // reducer.world, probes=probes,
-        include_rate_penalty=take('include_rate_penalty', True), include_time_avg=take('include_time_avg', False),
-        unroll_scan=take('unroll_scan', False), dtype=take('gen_dtype', 'float32'),
-        z_device_seed=take('z_device_seed', None), shard=(reducer.rank, reducer.world),
-        ssn_type=ssn_type, V=V, dist_in=dist_in, gen_kernel=gen_kernel, z_host_draw=take('z_host_draw', False))
+    gen, ssn_type = build_generator(kwargs, gen_kernel, len(bandwidths) * len(contrasts),
+                                    batchsize // GradientAllReducer().world, probes=probes)
+    for key in ('V_min', 'V_max'):
+        kwargs.pop(key, None)
     rate_penalty_threshold = gen_cfg.pop('rate_penalty_threshold')
     disc_rate_penalty_bound = disc_cfg.pop('rate_penalty_bound')
     seed = take('seed', 0)
@@ -139,21 +122,13 @@ def make_gan(config):
         normalization=disc_cfg.pop('normalization', 'none'), nonlinearity=disc_cfg.pop('nonlinearity', 'rectify'),
         net_options=disc_cfg.pop('net_options', None), precision=disc_cfg.pop('precision', 'fp32'),
         seed=disc_cfg.pop('init_seed', seed))
-    upd_keys = ('learning_rate', 'update_name', 'update_config', 'reg_l2_penalty', 'reg_l2_decay', 'reg_l1_penalty',
-                'reg_l1_decay')
-    dynamics_cost = gen_cfg.pop('dynamics_cost', 1.0)
-    rate_cost = gen_cfg.pop('rate_cost')
-    bounds = {name: (gen_cfg.pop(name + '_min', 1e-3), gen_cfg.pop(name + '_max', 10.0)) for name in 'JDS'}
-    bounds['V'] = _v_bounds(gen_cfg.pop('V_min', 0), gen_cfg.pop('V_max', 1), ssn_type)   # wgan.py:263-283
-    gen_upd_cfg = {k: gen_cfg.pop(k) for k in list(gen_cfg) if k in upd_keys}
-    gen_updaters = {name: Updater(**gen_upd_cfg) for name in 'VJDS'}
-    disc_updater = Updater(**{k: disc_cfg.pop(k) for k in upd_keys if k in disc_cfg})
+    parts = generator_trainer_parts(gen_cfg, ssn_type)
+    disc_updater = updater_from(disc_cfg)
     if gen_cfg or disc_cfg:
         raise ValueError('Unknown trainer options: gen={} disc={}'.format(sorted(gen_cfg), sorted(disc_cfg)))
     gan = BPTTWassersteinGAN(
-        gen, disc, gen_updaters, disc_updater, bandwidths, contrasts,
+        gen=gen, disc=disc, disc_updater=disc_updater, bandwidths=bandwidths, contrasts=contrasts,
         include_inhibitory_neurons=include_inhibitory_neurons, rate_penalty_threshold=rate_penalty_threshold,
         batchsize=batchsize, critic_iters_init=take('critic_iters_init'), critic_iters=take('critic_iters'),
-        lipschitz_cost=take('lipschitz_cost'), disc_rate_penalty_bound=disc_rate_penalty_bound,
-        dynamics_cost=dynamics_cost, rate_cost=rate_cost, param_bounds=bounds, seed=seed)
+        lipschitz_cost=take('lipschitz_cost'), disc_rate_penalty_bound=disc_rate_penalty_bound, seed=seed, **parts)
     return gan, kwargs

@@ -354,7 +354,6 @@ def test_poisoned_generator_gradient_is_not_hidden_by_the_parameter_bounds(tail,
     monkeypatch.setattr(cwgan, '_SUBSET_RETRY', retry == 'subset')
     from argparse import Namespace
     from tc_gan_amd.networks.cwgan import make_gan
-    from tc_gan_amd.utils import StopWatch
 
     def step(kernel, poison):
         cfg = dict(TEST_PARAMS, num_sites=60, num_models=4, probes_per_model=1, seqlen=60, skip_steps=40,
@@ -365,7 +364,6 @@ def test_poisoned_generator_gradient_is_not_hidden_by_the_parameter_bounds(tail,
         if tail == 'per-parameter':
             gan.gen_updaters['J'].learning_rate *= 2          # updaters out of step with each other: the parameter-by-parameter tail
         gan.set_dataset(_fake_data(gan, 9, np.random.RandomState(4)))
-        gan.gen_forward_watch, gan.gen_train_watch, gan.disc_train_watch = StopWatch(), StopWatch(), StopWatch()
         batch = gan.next_minibatch()
         prepared = gan._prepare_gen(batch)
         assert (gan._gen_tail_fused() is not None) == (tail == 'fused')
