@@ -1,4 +1,4 @@
-"""ctypes boundary to ``ext/libssnode.so`` (HIP / gfx950 build).
+"""ctypes boundary to ``ext/libssnode.so`` and its companion ``ext/libssnode_ext.so`` (HIP / gfx950 build).
 
 Drop-in for the reference's ``tc_gan/clib.py`` (lines 7-33): same loader
 (``numpy.ctypeslib.load_library('libssnode', <pkg>/ext)`` at import time, so a
@@ -423,6 +423,24 @@ libssnode.ssn_swd_backproject_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, 
 for _name in ('ssn_swd_match_f32', 'ssn_swd_backproject_f32'):
     getattr(libssnode, _name).restype = c_int
 
+# ---- the companion library (include/ssnode_mi355x_ext.h) -----------------------
+# Entry points added after the surface of libssnode.so was pinned (DECLARED_SYMBOLS above is that surface and stays as it
+# is).  Loaded like the main library: a missing file is an OSError on import.  Its error string is its own.
+libssnode_ext = load_library('libssnode_ext')
+
+#: the functions include/ssnode_mi355x_ext.h declares, which are the dynamic symbols of libssnode_ext.so
+EXT_DECLARED_SYMBOLS = ('ssnx_abi_version', 'ssnx_last_error', 'ssnx_swd_match_sizes_f32')
+#: most truth rows `ssnx_swd_match_sizes_f32` takes (SSNX_SWD_MAX_TRUTH of the header)
+SWD_MAX_TRUTH = 16384
+
+libssnode_ext.ssnx_abi_version.argtypes = []
+libssnode_ext.ssnx_abi_version.restype = c_int
+libssnode_ext.ssnx_last_error.argtypes = []
+libssnode_ext.ssnx_last_error.restype = c_char_p
+# px, n, py, m, L, power, coef, loss_l, stream
+libssnode_ext.ssnx_swd_match_sizes_f32.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+libssnode_ext.ssnx_swd_match_sizes_f32.restype = c_int
+
 #: most members the `ssn_ens_swd_*` entries take, most rows of the match's wave form, its forms (the header's macros)
 ENS_SWD_MAX_MEMBERS = 2048
 SWD_WAVE_MAX_BATCH = 64
@@ -568,6 +586,16 @@ def check(rc, what):
     """Raise on a non-zero status of an additive-ABI call."""
     if rc != 0:
         raise SSNLibraryError('{} failed: status {} ({})'.format(what, rc, last_error()))
+
+
+def ext_last_error():
+    return libssnode_ext.ssnx_last_error().decode()
+
+
+def check_ext(rc, what):
+    """Raise on a non-zero status of a call into the companion library (its own error string)."""
+    if rc != 0:
+        raise SSNLibraryError('{} failed: status {} ({})'.format(what, rc, ext_last_error()))
 
 
 _DEVICES_SEEN = 0

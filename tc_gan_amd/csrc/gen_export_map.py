@@ -2,6 +2,7 @@
 """Linker version script of libssnode.so from the published header: the functions include/ssnode_mi355x.h declares are
 the library's dynamic symbols and nothing else is (kernel stubs, launch templates and the HIP registration objects stay
 local; the runtime finds kernels through the registration its static constructors make, not through the symbol table).
+The companion library libssnode_ext.so is linked the same way from include/ssnode_mi355x_ext.h.
 usage: gen_export_map.py <header> <out.map>"""
 import re
 import sys

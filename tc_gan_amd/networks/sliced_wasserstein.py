@@ -3,11 +3,14 @@
 Every step the minibatch of generated tuning curves x (B, D) and a minibatch y (B, D) of the truth are projected on L fresh
 random unit directions (``ssn_project_rows_f32``); per direction the two columns are sorted and matched rank by rank
 (``ssn_swd_match_f32``: the loss per direction and the coefficient of every projection), and the coefficients go back to the rows
-(``ssn_swd_backproject_f32``: the gradient `gx` the adjoint sweep starts from).  With power 1 the recorded loss is the mean over
+(``ssn_swd_backproject_f32``: the gradient `gx` the adjoint sweep starts from).  With ``swd_truth_batch`` the truth minibatch has
+a size M of its own -- a generated row costs a forward and an adjoint sweep, a truth row one projection -- and the match is the
+quantile coupling of ``ssnx_swd_match_sizes_f32`` (include/ssnode_mi355x_ext.h).  With power 1 the recorded loss is the mean over
 the directions of the W1 of the projections -- the unit of ``analyzers/distdiff.py --wasserstein``'s ``sliced_w1`` -- with power 2
 the mean of their squared W2.  Forward, adjoint sweep, penalties and update are the moment matcher's
 (`moment_matching.GeneratorStepTrainer`); the definitions are in include/ssnode_mi355x.h and DESIGN 3.11c.
 """
+import itertools
 import os
 
 import numpy as np
@@ -19,30 +22,45 @@ from ..clib import libssnode
 from ..utils import random_minibatches
 from .moment_matching import DEFAULT_PARAMS as _MM_DEFAULTS, GeneratorStepTrainer, generator_step_parts
 
-DEFAULT_PARAMS = dict(_MM_DEFAULTS, swd_directions=128, swd_power=2, swd_direction_seed=0)
+DEFAULT_PARAMS = dict(_MM_DEFAULTS, swd_directions=128, swd_power=2, swd_direction_seed=0, swd_truth_batch=0)
 del DEFAULT_PARAMS['moment_weight_type']
 
 SWD_POWERS = (1, 2)
+#: `swd_truth_batch`: the truth minibatch is `batchsize` rows (the rank matching) / is the whole truth every step
+SWD_TRUTH_BATCHSIZE, SWD_TRUTH_ALL = 0, -1
 
 
-def swd_loss_grad(x, y, theta, power):
-    """x, y (B, D), theta (L, D): device float32, contiguous -> (gx (B, D) device float32, loss, loss_l (L,) numpy fp64).
+def swd_loss_grad(x, y, theta, power, unequal=False):
+    """x (B, D), y (M, D), theta (L, D): device float32, contiguous -> (gx (B, D) device float32, loss, loss_l (L,) numpy fp64).
     Four launches (two projections, the match, the back-projection) and one read of the L doubles; the mean over the directions
-    is formed on the host, in index order."""
+    is formed on the host, in index order.  M == B: the rank matching of `ssn_swd_match_f32`.  M != B is taken only with
+    `unequal=True` (a truth minibatch of another size is a decision, not a slip of shapes): the quantile coupling of
+    `ssnx_swd_match_sizes_f32` in the companion library; projections and back-projection are the same calls."""
     B, D = x.shape
     L = theta.shape[0]
-    if tuple(y.shape) != (B, D) or theta.shape[1] != D or not (x.is_contiguous() and y.is_contiguous() and theta.is_contiguous()):
-        raise ValueError('swd_loss_grad: x, y (B, D) and theta (L, D) must be contiguous, got {}, {} and {}'
-                         .format(tuple(x.shape), tuple(y.shape), tuple(theta.shape)))
+    M = y.shape[0] if y.dim() == 2 else -1
+    if M < 0 or y.shape[1] != D or (M != B and not unequal) or theta.shape[1] != D or \
+            not (x.is_contiguous() and y.is_contiguous() and theta.is_contiguous()):
+        raise ValueError('swd_loss_grad: x, y (B, D) and theta (L, D) must be contiguous, got {}, {} and {}{}'
+                         .format(tuple(x.shape), tuple(y.shape), tuple(theta.shape),
+                                 '' if unequal else ' (y of another row count needs unequal=True)'))
+    if M != B and not 1 <= M <= clib.SWD_MAX_TRUTH:
+        raise ValueError('swd_loss_grad: {} truth rows are not in 1 .. {} (clib.SWD_MAX_TRUTH)'.format(M, clib.SWD_MAX_TRUTH))
     stream = clib.stream_ptr()
-    px = torch.empty((2, B, L), device=x.device, dtype=torch.float32)
-    for src, dst in ((x, px[0]), (y, px[1])):
-        clib.check(libssnode.ssn_project_rows_f32(src.data_ptr(), B, D, D, theta.data_ptr(), L, dst.data_ptr(), stream),
+    px = torch.empty((B, L), device=x.device, dtype=torch.float32)
+    py = torch.empty((M, L), device=x.device, dtype=torch.float32)
+    for src, rows, dst in ((x, B, px), (y, M, py)):
+        clib.check(libssnode.ssn_project_rows_f32(src.data_ptr(), rows, D, D, theta.data_ptr(), L, dst.data_ptr(), stream),
                    'ssn_project_rows_f32')
     coef = torch.empty((B, L), device=x.device, dtype=torch.float32)
     loss_l = torch.empty(L, device=x.device, dtype=torch.float64)
-    clib.check(libssnode.ssn_swd_match_f32(px[0].data_ptr(), px[1].data_ptr(), B, L, int(power), coef.data_ptr(),
-                                           loss_l.data_ptr(), stream), 'ssn_swd_match_f32')
+    if M == B:
+        clib.check(libssnode.ssn_swd_match_f32(px.data_ptr(), py.data_ptr(), B, L, int(power), coef.data_ptr(),
+                                               loss_l.data_ptr(), stream), 'ssn_swd_match_f32')
+    else:
+        clib.check_ext(clib.libssnode_ext.ssnx_swd_match_sizes_f32(px.data_ptr(), B, py.data_ptr(), M, L, int(power),
+                                                                  coef.data_ptr(), loss_l.data_ptr(), stream),
+                       'ssnx_swd_match_sizes_f32')
     gx = torch.empty((B, D), device=x.device, dtype=torch.float32)
     clib.check(libssnode.ssn_swd_backproject_f32(coef.data_ptr(), theta.data_ptr(), B, L, D, gx.data_ptr(), stream),
                'ssn_swd_backproject_f32')
@@ -50,9 +68,36 @@ def swd_loss_grad(x, y, theta, power):
     return gx, float(np.cumsum(host)[-1] / L), host           # (cumsum: the sequential sum)
 
 
+def checked_truth_batch(value):
+    """`swd_truth_batch` as an int, or a ValueError that names it."""
+    if isinstance(value, bool) or int(value) != value or not SWD_TRUTH_ALL <= value <= clib.SWD_MAX_TRUTH:
+        raise ValueError('swd_truth_batch = {!r} is not 0 (batchsize rows), -1 (the whole truth) or a row count up to {} '
+                         '(clib.SWD_MAX_TRUTH)'.format(value, clib.SWD_MAX_TRUTH))
+    return int(value)
+
+
+def truth_minibatch_rows(swd_truth_batch, batchsize, truth_rows, **kwargs):
+    """The row indices of the truth minibatches, one array per step, by the three meanings of `swd_truth_batch`: 0 --
+    `utils.random_minibatches(batchsize, ...)`, the stream of a run without the option; M > 0 -- the same with M rows; -1 --
+    None: every minibatch is the whole truth, no shuffle is drawn, and `batchsize` may exceed the truth's rows."""
+    if swd_truth_batch == SWD_TRUTH_ALL:
+        if not 1 <= truth_rows <= clib.SWD_MAX_TRUTH:
+            raise ValueError('swd_truth_batch = -1: the truth has {} rows, the match takes 1 .. {} (clib.SWD_MAX_TRUTH)'
+                             .format(truth_rows, clib.SWD_MAX_TRUTH))
+        return None
+    if swd_truth_batch > truth_rows:
+        raise ValueError('swd_truth_batch = {} > truth rows = {}; use -1 for the whole truth every step'
+                         .format(swd_truth_batch, truth_rows))
+    return random_minibatches(swd_truth_batch or batchsize, np.arange(truth_rows), **kwargs)
+
+
 class BPTTSlicedWasserstein(GeneratorStepTrainer):
     """The critic-free trainer: `set_dataset(data)`, then `learning()` yields one `info` per generator update -- step, loss
-    (with the penalties), swd (the bare sliced loss), dynamics_penalty, rate_penalty, train_time."""
+    (with the penalties), swd (the bare sliced loss), dynamics_penalty, rate_penalty, train_time.  `swd_truth_batch` (set before
+    `set_dataset`; `make_sliced_wasserstein` sets it from the config) is the size of the truth minibatch: 0 -- `batchsize` rows,
+    -1 -- the whole truth every step, M -- M rows."""
+    #: (an attribute and not a constructor argument: the constructor's call is recorded argument by argument)
+    swd_truth_batch = SWD_TRUTH_BATCHSIZE
 
     def __init__(self, gen, gen_updaters, bandwidths, contrasts, swd_directions, swd_power, swd_direction_seed,
                  include_inhibitory_neurons, rate_penalty_threshold, dynamics_cost, rate_cost, param_bounds, seed=0):
@@ -72,14 +117,17 @@ class BPTTSlicedWasserstein(GeneratorStepTrainer):
                                   rate_penalty_threshold, dynamics_cost, rate_cost, param_bounds, seed)
 
     def set_dataset(self, data, **kwargs):
-        """The truth stays on the device; the minibatches are rows of it in the order of `utils.random_minibatches` (as
+        """The truth stays on the device; the minibatches are rows of it in the order of `truth_minibatch_rows` (as
         `BPTTWassersteinGAN.set_dataset` takes them, but shuffled on `minibatch_rng`)."""
         kwargs.setdefault('seed', self.minibatch_rng)
         data = np.ascontiguousarray(data, dtype='float32')
-        self.truth = torch.as_tensor(data).to('cuda')
         # (an ensemble takes the row indices themselves from `minibatch_rows`, one gather for all its members)
-        self.minibatch_rows = rows = random_minibatches(self.gen.batchsize, np.arange(len(data)), **kwargs)
-        self.dataset = (self.truth[torch.as_tensor(idx).to('cuda')] for idx in rows)
+        self.minibatch_rows = rows = truth_minibatch_rows(self.swd_truth_batch, self.gen.batchsize, len(data), **kwargs)
+        self.truth = torch.as_tensor(data).to('cuda')
+        if rows is None:
+            self.dataset = itertools.repeat(self.truth)
+        else:
+            self.dataset = (self.truth[torch.as_tensor(idx).to('cuda')] for idx in rows)
 
     def next_minibatch(self):
         return next(self.dataset)
@@ -88,8 +136,8 @@ class BPTTSlicedWasserstein(GeneratorStepTrainer):
         return torch.as_tensor(draw_slice_directions(self.direction_rng, self.swd_directions, columns)).to('cuda')
 
     def swd_loss_grad(self, x, y, theta):
-        """x, y (B, D), theta (L, D) device float32 -> (gx, loss, loss_l)."""
-        return swd_loss_grad(x, y, theta, self.swd_power)
+        """x (B, D), y (B, D) -- or (M, D) under `swd_truth_batch` --, theta (L, D) device float32 -> (gx, loss, loss_l)."""
+        return swd_loss_grad(x, y, theta, self.swd_power, unequal=self.swd_truth_batch != SWD_TRUTH_BATCHSIZE)
 
     def train_generator(self, info):
         def loss_grad(x):
@@ -110,7 +158,9 @@ def make_sliced_wasserstein(config):
         raise ValueError('the sliced Wasserstein trainer runs on one GPU: the match kernel needs whole columns of the projections, '
                          'and the all-gather that would give them to every rank is not built (WORLD_SIZE = {})'.format(world))
     kwargs = dict(DEFAULT_PARAMS, **config)
+    truth_batch = checked_truth_batch(kwargs.pop('swd_truth_batch'))      # (refused before the generator is built)
     parts = generator_step_parts(kwargs)
     swd = BPTTSlicedWasserstein(swd_directions=kwargs.pop('swd_directions'), swd_power=kwargs.pop('swd_power'),
                                 swd_direction_seed=kwargs.pop('swd_direction_seed'), **parts)
+    swd.swd_truth_batch = truth_batch
     return swd, kwargs

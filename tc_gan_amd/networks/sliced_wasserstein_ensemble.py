@@ -106,10 +106,19 @@ class EnsembleSlicedWasserstein(EnsembleGeneratorStep):
         return dict(swd=float(row[0]), swd_per_direction=row[self.R0:self.R0 + self.L].copy())
 
 
+def refuse_truth_batch(config):
+    """The ensemble's match kernels take as many truth rows as generated ones: `swd_truth_batch` (an option of the single run,
+    in neither key set here) may only be absent or 0."""
+    if config.get('swd_truth_batch', 0) != 0:
+        raise ValueError('swd_truth_batch = {!r}: an ensemble matches batchsize truth rows per member (its kernels know equal '
+                         'sizes only); use 0 here, or tc_gan.run.bptt_swd for one run'.format(config['swd_truth_batch']))
+
+
 def ensemble_from_member_configs(configs, match_form=clib.SWD_FORM_AUTO):
     """The `EnsembleSlicedWasserstein` of fully resolved member configs (each what `make_sliced_wasserstein` takes, all naming
     the same explicit `gen_kernel`)."""
     for cfg in configs:
+        refuse_truth_batch(cfg)
         if cfg.get('gen_kernel') == 'duo-fused':
             raise ValueError("gen_kernel 'duo-fused' is not available to ensembles; use 'duo'")
     members, rests, dcosts, rcosts, kernel = mme.members_from_configs(configs, make_sliced_wasserstein)

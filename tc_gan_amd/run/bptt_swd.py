@@ -2,7 +2,8 @@
 Run BPTT training by the sliced Wasserstein distance on MI355X: no critic.
 
 The generator options of ``tc_gan.run.bptt_moments`` (generator, dynamics, bounds, updater, data set) and the loss's own:
-``--swd-directions``, ``--swd-power``, ``--swd-direction-seed``.  Outputs: the ``learning`` table (step, loss, swd,
+``--swd-directions``, ``--swd-power``, ``--swd-direction-seed``, ``--swd-truth-batch`` (truth rows per step: 0 = the batch size,
+-1 = the whole truth, M = minibatches of M rows).  Outputs: the ``learning`` table (step, loss, swd,
 dynamics_penalty, rate_penalty, train_time) and the ``generator`` table in the store, truth.npy -- a run directory that
 ``tc_gan.analyzers.distdiff --wasserstein`` scores; with ``--swd-power 1`` the ``swd`` column is in the unit of its sliced_w1.
 """
@@ -11,7 +12,7 @@ from logging import getLogger
 import numpy as np
 
 from ..drivers import SlicedWassersteinDriver
-from ..networks.sliced_wasserstein import make_sliced_wasserstein
+from ..networks.sliced_wasserstein import DEFAULT_PARAMS, make_sliced_wasserstein
 from .bptt_wgan import do_learning, generate_dataset_and_save
 
 logger = getLogger(__name__)
@@ -41,7 +42,9 @@ def init_driver(datastore, iterations, quiet, quit_JDS_threshold=-1, **run_confi
 def main(args=None):
     parser = make_parser()
     ns = parser.parse_args(args)
-    do_learning(learn, vars(ns), init_driver=init_driver, script_file=__file__)
+    run_config = vars(ns)
+    run_config.setdefault('swd_truth_batch', DEFAULT_PARAMS['swd_truth_batch'])      # (recorded in info.json like the others)
+    do_learning(learn, run_config, init_driver=init_driver, script_file=__file__)
 
 
 if __name__ == '__main__':

@@ -17,7 +17,7 @@ import numpy as np
 
 from .. import execution
 from ..drivers import SlicedWassersteinDriver
-from ..networks.sliced_wasserstein_ensemble import ensemble_from_member_configs, validate_member_overrides
+from ..networks.sliced_wasserstein_ensemble import ensemble_from_member_configs, refuse_truth_batch, validate_member_overrides
 from . import bptt_moments_ensemble as bme
 from .bptt_wgan import generate_dataset_and_save
 
@@ -38,7 +38,11 @@ def make_parser():
 
 def member_run_configs(run_config, member_overrides):
     """The run_config of every member as a single ``bptt_swd`` run with the same options would write it to info.json
-    (`bptt_moments_ensemble.member_run_configs` with this ensemble's keys): gen_kernel resolved once, for K x batchsize draws."""
+    (`bptt_moments_ensemble.member_run_configs` with this ensemble's keys): gen_kernel resolved once, for K x batchsize draws.
+    But for one key: a single run always records `swd_truth_batch` (0 unless given); a member records it only where the ensemble's
+    command line gave it, and then it is 0.
+    A `swd_truth_batch` other than 0 is refused here, before anything is written or built."""
+    refuse_truth_batch(run_config)
     return bme.member_run_configs(run_config, member_overrides, validate=validate_member_overrides)
 
 

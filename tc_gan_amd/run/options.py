@@ -137,7 +137,13 @@ SWD_OPTIONS = [
          help='Power p of the loss, the mean over directions and ranks of |difference of the sorted projections|^p.  2 '
               '(default): a gradient that is continuous in the tuning curves; 1: the unit of distdiff --wasserstein\'s sliced_w1'),
     _opt('s', '--swd-direction-seed', default=0, type='int',
-         help='Seed of the streams the directions and the truth minibatches are drawn from (apart from the noise stream).')]
+         help='Seed of the streams the directions and the truth minibatches are drawn from (apart from the noise stream).'),
+    # (no namespace entry unless given: the option namespace with no argument stays the one the tests of the older options pin;
+    # `bptt_swd.main` records the default in info.json, `sliced_wasserstein.DEFAULT_PARAMS` supplies it to the trainer)
+    _opt('s', '--swd-truth-batch', default=argparse.SUPPRESS, type='int',
+         help='Truth rows per step (default: 0).  0: as many as --batchsize, matched rank by rank; -1: the whole truth every '
+              'step, no shuffle (--batchsize may then exceed the truth); M > 0: minibatches of M rows.  Sizes other than '
+              '--batchsize are matched by the quantile coupling (at most {} rows).'.format(clib.SWD_MAX_TRUTH))]
 
 DATASTORE_TEMPLATES = {'w': 'logfiles/BPTT_WGAN_{layers_str}', 'c': 'logfiles/BPTT_CWGAN_{layers_str}', 'm': 'logfiles/BPTT_MM_{lam}',
                        's': 'logfiles/BPTT_SWD_{swd_directions}_{swd_power}'}
