@@ -1,4 +1,5 @@
-"""ctypes boundary to ``ext/libssnode.so`` and its companion ``ext/libssnode_ext.so`` (HIP / gfx950 build).
+"""ctypes boundary to ``ext/libssnode.so`` and its companions ``ext/libssnode_ext.so`` and ``ext/libssnode_ext2.so`` (HIP /
+gfx950 build).
 
 Drop-in for the reference's ``tc_gan/clib.py`` (lines 7-33): same loader
 (``numpy.ctypeslib.load_library('libssnode', <pkg>/ext)`` at import time, so a
@@ -441,6 +442,25 @@ libssnode_ext.ssnx_last_error.restype = c_char_p
 libssnode_ext.ssnx_swd_match_sizes_f32.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
 libssnode_ext.ssnx_swd_match_sizes_f32.restype = c_int
 
+# ---- the second companion library (include/ssnode_mi355x_ext2.h) ----------------
+# The first companion's surface is pinned name by name as well; this one's may grow: its test holds the header, the tuple below
+# and the dynamic symbol table equal, without a list of names.  A later entry point is declared in the header and added here.
+libssnode_ext2 = load_library('libssnode_ext2')
+
+#: the functions include/ssnode_mi355x_ext2.h declares, which are the dynamic symbols of libssnode_ext2.so
+EXT2_DECLARED_SYMBOLS = ('ssnx2_abi_version', 'ssnx2_last_error', 'ssnx2_swd_match_cells_f32')
+#: most condition cells `ssnx2_swd_match_cells_f32` takes (SSNX2_SWD_MAX_CELLS of the header)
+SWD_MAX_CELLS = 256
+
+libssnode_ext2.ssnx2_abi_version.argtypes = []
+libssnode_ext2.ssnx2_abi_version.restype = c_int
+libssnode_ext2.ssnx2_last_error.argtypes = []
+libssnode_ext2.ssnx2_last_error.restype = c_char_p
+# px, B, cell_rows, cell_start (HOST int[C + 1]), C, py, m, L, power, coef, loss_cl, stream
+libssnode_ext2.ssnx2_swd_match_cells_f32.argtypes = [c_void_p, c_int, c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_int,
+                                                     c_int, c_void_p, c_void_p, c_void_p]
+libssnode_ext2.ssnx2_swd_match_cells_f32.restype = c_int
+
 #: most members the `ssn_ens_swd_*` entries take, most rows of the match's wave form, its forms (the header's macros)
 ENS_SWD_MAX_MEMBERS = 2048
 SWD_WAVE_MAX_BATCH = 64
@@ -596,6 +616,16 @@ def check_ext(rc, what):
     """Raise on a non-zero status of a call into the companion library (its own error string)."""
     if rc != 0:
         raise SSNLibraryError('{} failed: status {} ({})'.format(what, rc, ext_last_error()))
+
+
+def ext2_last_error():
+    return libssnode_ext2.ssnx2_last_error().decode()
+
+
+def check_ext2(rc, what):
+    """Raise on a non-zero status of a call into the second companion library (its own error string)."""
+    if rc != 0:
+        raise SSNLibraryError('{} failed: status {} ({})'.format(what, rc, ext2_last_error()))
 
 
 _DEVICES_SEEN = 0

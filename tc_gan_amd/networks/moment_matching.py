@@ -106,13 +106,18 @@ class GeneratorStepTrainer(object):
             rows = (self.reducer.rank * per, (self.reducer.rank + 1) * per)
         return self.gen.gen_noise(self.rng, stimulator_bandwidths=np.empty((self.global_batchsize, 1)), rows=rows)
 
-    def generator_step(self, info, loss_grad):
+    def generator_step(self, info, loss_grad, forward_kwargs=None, noise=None):
         """One update: `loss_grad(x)` -> (gx, L0) for the tuning curves x (B_local, D) of this step's forward.  Fills
-        `info.dynamics_penalty`, `info.rate_penalty` and `info.loss` (L0 with the penalties) and returns L0."""
-        noise = self._draw_noise()
-        out = self.gen.forward(rng=self.rng, save=True, stimulator_bandwidths=self.stimulator_bandwidths,
-                               stimulator_contrasts=self.stimulator_contrasts,
-                               model_rate_penalty_threshold=self.rate_penalty_threshold, **noise)
+        `info.dynamics_penalty`, `info.rate_penalty` and `info.loss` (L0 with the penalties) and returns L0.
+        `forward_kwargs`: the stimulator (and, for a conditional generator, prober) inputs of the forward -- None: the trainer's
+        fixed stimulus grid; `noise`: the step's draw -- None: `_draw_noise()`."""
+        if noise is None:
+            noise = self._draw_noise()
+        if forward_kwargs is None:
+            forward_kwargs = dict(stimulator_bandwidths=self.stimulator_bandwidths,
+                                  stimulator_contrasts=self.stimulator_contrasts)
+        out = self.gen.forward(rng=self.rng, save=True, model_rate_penalty_threshold=self.rate_penalty_threshold,
+                               **forward_kwargs, **noise)
         gx, l0 = loss_grad(out.prober_tuning_curve)
         # L0 is a function of the GLOBAL minibatch: the local adjoint sweeps add up over ranks, whereas the
         # penalties are per-rank means -> scale gx so that the rank MEAN below is right for both

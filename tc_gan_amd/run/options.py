@@ -2,7 +2,8 @@
 
 One table, `OPTIONS`: a row per option -- flags, default, value type, help, and the scripts that take it
 (`w` = tc_gan.run.bptt_wgan, `c` = bptt_cwgan, `m` = bptt_moments) -- from which `build_parser` makes each script's
-``argparse`` parser; `s` = bptt_swd (new) takes the rows of `m` that still apply and `SWD_OPTIONS`.  The names, aliases and defaults are the reference's (tc_gan/run/bptt_wgan.py:46-172,
+``argparse`` parser; `s` = bptt_swd (new) takes the rows of `m` that still apply and `SWD_OPTIONS`, `k` = bptt_cswd (new) the rows
+of `s` that still apply and the sampling rows of `c`.  The names, aliases and defaults are the reference's (tc_gan/run/bptt_wgan.py:46-172,
 bptt_cwgan.py:17-53, bptt_moments.py:36-101, run/gan.py:1109-1152, execution.py:290-317); `run_config` keys follow from the
 first long flag as argparse derives them, and the CLI tests (tests/test_run_bptt_cwgan_gpu.py: option cases, the key set of
 the paper's run.json through --load-config) are the contract.  Options this build adds say "(new)".
@@ -145,8 +146,14 @@ SWD_OPTIONS = [
               'step, no shuffle (--batchsize may then exceed the truth); M > 0: minibatches of M rows.  Sizes other than '
               '--batchsize are matched by the quantile coupling (at most {} rows).'.format(clib.SWD_MAX_TRUTH))]
 
+#: `k` = tc_gan.run.bptt_cswd (new), the conditional sliced Wasserstein trainer: the rows of `s` that still apply -- what a step
+#: samples is the conditional GAN's (`CSWD_SAMPLING`, rows of `c`), and the whole truth is used every step
+CSWD_DROPPED = ('--batchsize', '--sample-sites', '--swd-truth-batch')
+CSWD_SAMPLING = ('--num-models', '--probes-per-model', '--norm-probes')
+
 DATASTORE_TEMPLATES = {'w': 'logfiles/BPTT_WGAN_{layers_str}', 'c': 'logfiles/BPTT_CWGAN_{layers_str}', 'm': 'logfiles/BPTT_MM_{lam}',
-                       's': 'logfiles/BPTT_SWD_{swd_directions}_{swd_power}'}
+                       's': 'logfiles/BPTT_SWD_{swd_directions}_{swd_power}',
+                       'k': 'logfiles/BPTT_CSWD_{swd_directions}_{swd_power}'}
 
 
 class _Formatter(argparse.RawDescriptionHelpFormatter, argparse.ArgumentDefaultsHelpFormatter):
@@ -155,9 +162,12 @@ class _Formatter(argparse.RawDescriptionHelpFormatter, argparse.ArgumentDefaults
 
 def options_of(script):
     """The rows of `OPTIONS` the script takes ('w', 'c' or 'm'), in table order; for 's' the rows of 'm' without `SWD_DROPPED`,
-    then `SWD_OPTIONS`."""
+    then `SWD_OPTIONS`; for 'k' the rows of 's' without `CSWD_DROPPED`, then the `CSWD_SAMPLING` rows of 'c'."""
     if script == 's':
         return [o for o in options_of('m') if o['flags'][0] not in SWD_DROPPED] + SWD_OPTIONS
+    if script == 'k':
+        return [o for o in options_of('s') if o['flags'][0] not in CSWD_DROPPED] + \
+            [o for o in options_of('c') if o['flags'][0] in CSWD_SAMPLING]
     return [o for o in OPTIONS if script in o['scripts']]
 
 
